@@ -9,12 +9,16 @@ the metric is quoted on; it fits one GPU).  With N GPUs (one process per GPU) ev
 solves shard `rank` of N of the step's columns (granules of 32 columns of the cost-ordered
 work list dealt round-robin; RCCL only for the one-off broadcast of R and the gather of the
 learned columns).  Default: B = 8192 columns per GPU and step => weak scaling (at N = 8 a
-step covers 65 536 of the 100 000 columns).  --scaling strong fixes the columns per step
+step covers 65 536 of the 100 000 columns).  At N = 1 every timed step is a from-scratch
+SLIM_Learn on a fresh handle with the engine's own kernel choice (item space, G = R^T R built
+inside the step); the residual kernel's from-scratch step (~60 s) is reported once beside it
+(residual_step) and compared with the timed step's model.  --scaling strong fixes the columns per step
 (--batch 0: the whole matrix, north_star's target; 555 s per step on one GPU, which is why
 it is not the default under the driver's 25-step run).
 
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py ... --dump-outputs DIR     (+ the last timed step's model columns, dump_outputs)
 
 Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
   roofline      algorithmic bytes (8G + 12D + 4U + 8 nnzW per column, from
@@ -30,8 +34,10 @@ and, at N = 1 on the default workload, two secondary figures under their own key
   item_space_grid  the first pairs of the C5 model-selection grid (BASELINE.json configs[4])
                    on the path the engine takes for a grid
   item_space_whole_matrix  every item column of the matrix once (north_star's target at N = 1)
-The command budgets itself against the driver's 1800 s (SLIM_BENCH_WALL_BUDGET): the extras
-and the CPU leg shrink or drop out, with a note, rather than overrun.
+The command budgets itself (SLIM_BENCH_WALL_BUDGET, 480 s of the RUN_LIMIT_S = 600 s a run of
+20 + 5 steps is given): the extras and the CPU leg shrink or drop out, with a note, rather than
+overrun.  Progress goes to stderr,
+one line per step and phase.
 """
 import argparse
 import json
@@ -44,9 +50,20 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s HBM3E (spec)
 T_START = time.time()
-# the driver gives the whole command 1800 s; the CPU leg (last thing in the run) fits itself
-# into what the timed steps left of this
-WALL_BUDGET_S = float(os.environ.get("SLIM_BENCH_WALL_BUDGET", "1680"))
+# the time one run of `bench.py --steps 20 --warmup 5` is given in all; the extras after the timed
+# steps (the CPU leg last) fit themselves into what the timed steps left of WALL_BUDGET_S, which
+# keeps two minutes of it for start-up and the end of the last extra
+RUN_LIMIT_S = 600.0
+WALL_BUDGET_S = float(os.environ.get("SLIM_BENCH_WALL_BUDGET", str(RUN_LIMIT_S - 120.0)))
+
+
+def progress(msg):
+    """One line on stderr (rank 0) as each step and each phase ends: a full run lasts many
+    minutes, and a command that stays silent that long cannot be told from a hung one.  stdout
+    keeps the one JSON line."""
+    if os.environ.get("RANK", "0") == "0":
+        sys.stderr.write("bench.py [%5.0f s] %s\n" % (time.time() - T_START, msg))
+        sys.stderr.flush()
 
 
 def parse_args():
@@ -94,7 +111,13 @@ def parse_args():
     ap.add_argument("--backend", default=os.environ.get("SLIM_BENCH_BACKEND", "nccl"),
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo lets several "
                          "ranks share one GPU in tests)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the model columns the last one learned to "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB; e.g. bench_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # Columns per GPU and step: 8192 = 256 tiles of 32.  (Round 2 used 8960, the size that fills the
@@ -127,7 +150,8 @@ def main():
                "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess   # (a child process, never exec: this one has imported the HIP runtime)
+        raise SystemExit(subprocess.call(cmd))
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: one rank per GPU" % (args.gpus, world))
     if not torch.cuda.is_available():
@@ -152,21 +176,30 @@ def main():
     from slim_amd.distributed import broadcast_csr, gather_model
     from slim_amd.engine import DeviceMatrix
 
-    # The timed steps are from-scratch solves by the residual kernels (SURVEY.md 8(d) prices
-    # THEIR traffic): nothing is carried from one step to the next -- neither the screen sums a
-    # second solve of the same columns could reuse (steps over ml100k or the whole matrix repeat
-    # their work list) nor the engine's switch to item-space CD for repeated solves.  --kernel 5
-    # asks for item-space CD explicitly; it is reported under its own key otherwise.
-    if args.kernel != 5:
+    # One process on a synthetic workload (the single-GPU line): every timed step is what a caller
+    # of SLIM_Learn gets from scratch -- a fresh handle on the resident R, the engine's own kernel
+    # choice (SLIMGPU_KERNEL_AUTO: item-space CD for 8192 columns of C4, G = R^T R built inside the
+    # step), the handle freed after it: nothing is carried from one step to the next.  A step
+    # pinned to the residual kernel takes ~60 s, so 20 of them and the warm-up cannot end inside
+    # RUN_LIMIT_S; that step is reported once, under its own key (residual_step), and its model is
+    # compared with the timed step's.
+    engine_path = (args.kernel == 0 and world == 1 and args.workload != "ml100k"
+                   and args.dry_run_world <= 1)
+    # Otherwise the timed steps are from-scratch solves by the residual kernels (SURVEY.md 8(d)
+    # prices THEIR traffic): nothing is carried from one step to the next -- neither the screen
+    # sums a second solve of the same columns could reuse (steps over ml100k or the whole matrix
+    # repeat their work list) nor the engine's switch to item-space CD for repeated solves.
+    # --kernel 5 asks for item-space CD explicitly.
+    if args.kernel != 5 and not engine_path:
         os.environ["SLIM_GPU_NO_GRAM"] = "1"
-    # `value` and `roofline` price the RESIDUAL kernel (SURVEY.md 8(d)'s formula is its traffic):
-    # it is pinned explicitly for the timed steps of the synthetic workloads, because the
+    # Off that path `value` and `roofline` price the RESIDUAL kernel (SURVEY.md 8(d)'s formula is its
+    # traffic): it is pinned explicitly for the timed steps of the synthetic workloads, because the
     # engine's own choice (SLIMGPU_KERNEL_AUTO, what SLIM_Learn takes by default) is item space
     # there since round 5 -- that path is reported beside it as item_space_step / item_space_grid
     # with its own byte model.  --kernel 5 times item space itself; --kernel 0 on ml100k is the
     # one-wavefront-per-item kernel.
     timed_kernel = args.kernel
-    if timed_kernel == 0 and args.workload != "ml100k":
+    if timed_kernel == 0 and args.workload != "ml100k" and not engine_path:
         timed_kernel = 3
 
     # ---- the workload, resident in HBM before anything is timed ---------------------
@@ -208,6 +241,7 @@ def main():
                                         keepalive=(rowptr, rowind, rowval), device=dev.index)
     t_stage = time.time() - t_stage
     ncols = mat.ncols
+    progress("workload resident: %s, nnz %d (generated in %.1f s)" % (name, nnz, t_gen))
 
     # One step = one SLIMGPU_Learn per rank over shard `rank` of `world` of a range of item
     # columns (granules of 32 columns of the range's cost-ordered work list dealt round-robin:
@@ -221,6 +255,8 @@ def main():
     else:
         span = min(ncols, per_gpu * world)
     warm_span = min(span, world * (args.warmup_batch or max(256, per_gpu // 32)))
+    if engine_path and not args.warmup_batch:
+        warm_span = span   # (a smaller first solve would take the residual kernel: not this path)
     opts = dict(l1r=1.0, l2r=1.0, optTol=1e-7, niters=10000, seed=args.seed, kernel=timed_kernel)
     if args.cluster:
         opts["cluster"] = args.cluster
@@ -228,6 +264,15 @@ def main():
     def step(i, width):
         """Solve range i; with N > 1 also gather the learned columns on rank 0."""
         b = (i * span) % max(1, ncols - width + 1)
+        if engine_path:   # from scratch: a fresh handle on the resident R, freed with its G after the solve
+            fresh = DeviceMatrix.from_device_ptrs(nrows, ncols, rowptr.data_ptr(), rowind.data_ptr(),
+                                                  rowval.data_ptr() if rowval is not None else 0,
+                                                  keepalive=(rowptr, rowind, rowval), device=dev.index)
+            try:
+                W, st = fresh.learn(col_begin=b, col_end=b + width, **opts)
+            finally:
+                fresh.close()
+            return W, st, b
         W, st = mat.learn(col_begin=b, col_end=b + width, shard=(rank, world), **opts)
         if world > 1:
             W = gather_model(W, dst=0)  # the learned columns end up on rank 0
@@ -246,8 +291,10 @@ def main():
     for i in range(args.warmup):  # untimed: same code path on a smaller range
         step(i, warm_span)
     fence()
+    progress("warm-up: %d step(s) of %d columns" % (args.warmup, warm_span))
     t0 = time.perf_counter()
-    acc = dict(kernel_ms=0.0, alg_bytes=0.0, G=0, D=0, U=0, nnzW=0, sweeps=0, gather_ms=0.0)
+    acc = dict(kernel_ms=0.0, alg_bytes=0.0, G=0, D=0, U=0, nnzW=0, sweeps=0, gather_ms=0.0,
+               gram_bytes=0.0)
     last_b = None
     step_begins = []
     for i in range(args.steps):
@@ -256,6 +303,8 @@ def main():
         step_begins.append(b)
         for k in acc:
             acc[k] += st[k]
+        progress("timed step %d of %d: columns [%d, %d), kernel %.0f ms"
+                 % (i + 1, args.steps, b, b + span, st["kernel_ms"]))
     fence()
     elapsed = time.perf_counter() - t0
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -269,6 +318,11 @@ def main():
         all_kt = [torch.zeros_like(kt) for _ in range(world)]
         dist.all_gather(all_kt, kt)
         rank_kernel_ms = [float(t.item()) for t in all_kt]
+    progress("timed steps done: %.1f ms per step" % (1e3 * elapsed / args.steps))
+    dumped = None
+    if args.dump_outputs and rank == 0:   # (outside the timed region; W is the last step's model)
+        dumped = dump_outputs(args.dump_outputs, W, last_b, span, args.seed)
+        progress("outputs of the last timed step written to %s" % args.dump_outputs)
 
     # N >= 4: north_star's target itself as a secondary figure -- ONE step over the whole
     # matrix, its columns split over the GPUs (strong scaling), outside the timed region
@@ -329,6 +383,7 @@ def main():
                     else:
                         os.environ[k] = v
         strong_whole = whole(opts["kernel"], {})
+        progress("whole-matrix step over %d GPUs done" % world)
         strong_whole["note"] = ("one untimed-by-contract step: all item columns of the matrix, sharded "
                                 "over the %d GPUs (strong scaling), residual kernel" % world)
         # the same step in item space (every rank builds G = R^T R for itself, then solves its shard)
@@ -339,11 +394,14 @@ def main():
             if float(room.item()) > 0.0:
                 strong_whole["item_space"] = whole(5, {"SLIM_GPU_NO_GRAMCD": None, "SLIM_GPU_NO_GRAM": None},
                                                    shard_gram=args.shard_gram)
+                progress("whole-matrix step in item space over %d GPUs done" % world)
 
     if rank == 0:
         cols_total = args.steps * span
         kname = KERNEL_NAMES.get(st["kernel"], st["kernel"])
-        achieved = acc["alg_bytes"] / (acc["kernel_ms"] * 1e-3) / 1e9 if acc["kernel_ms"] > 0 else 0.0
+        # (item space: the kernel's own byte model, the bytes of G it streamed)
+        step_bytes = acc["gram_bytes"] if kname == "gram" else acc["alg_bytes"]
+        achieved = step_bytes / (acc["kernel_ms"] * 1e-3) / 1e9 if acc["kernel_ms"] > 0 else 0.0
         kernel_s = acc["kernel_ms"] * 1e-3 / max(1, args.steps)
         traffic = os.environ.get("SLIM_BENCH_TRAFFIC_BYTES") or pmc_traffic(
             args, span if strong else per_gpu, kname, rowval is None, world)
@@ -378,7 +436,10 @@ def main():
                 "parallelism": "shards of the cost-ordered work list (32-column granules, "
                                "round-robin) over %d GPU(s), R replicated" % world,
                 "kernel": kname,
-                "carried_between_steps": "nothing (screen-sum cache and the automatic switch to "
+                "carried_between_steps": "nothing (every step: a fresh handle on the resident R, the "
+                                         "engine's own kernel choice, G = R^T R built inside the step)"
+                                         if engine_path else
+                                         "nothing (screen-sum cache and the automatic switch to "
                                          "item-space CD are off for the timed steps: kernel pinned)"
                                          if args.kernel != 5 else "G = R^T R, built by the first step",
                 "generate_s": round(t_gen, 2), "stage_s": round(t_stage, 2),
@@ -392,35 +453,59 @@ def main():
                 "frac_physical": float(traffic) / kernel_s / 1e9 / HBM_PEAK_GBS
                                  if traffic and kernel_s > 0 else None,
                 "kernel_ms_per_launch": acc["kernel_ms"] / max(1, args.steps),
-                "alg_bytes_per_launch": acc["alg_bytes"] / max(1, args.steps),
-                "alg_bytes_per_column": acc["alg_bytes"] * world / max(1, args.steps * span),
+                "alg_bytes_per_launch": step_bytes / max(1, args.steps),
+                "alg_bytes_per_column": step_bytes * world / max(1, args.steps * span),
                 "G": acc["G"], "D": acc["D"], "U": acc["U"], "nnzW": acc["nnzW"],
-                "sweeps": acc["sweeps"], "kernel_hash": kernel_hash(),
-                "note": "rank 0's launches; algorithmic bytes = 8G+12D+4U+8nnzW per column "
-                        "(binary: 4G+8D+4U+8nnzW), SURVEY.md 8(d)",
+                "sweeps": acc["sweeps"], "kernel_hash": kernel_hash("gram" if kname == "gram" else "tile"),
+                "note": "rank 0's launches; algorithmic bytes = " +
+                        ("the bytes of G the item-space kernel streamed (SLIMGPU_LastStats.gram_bytes)"
+                         if kname == "gram" else
+                         "8G+12D+4U+8nnzW per column (binary: 4G+8D+4U+8nnzW), SURVEY.md 8(d)"),
             },
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if strong_whole is not None:
             out["strong_whole_matrix"] = strong_whole
         if world == 1:
             out["parity"] = ml100k_parity(dev.index)
+            progress("ml100k parity done")
+        if engine_path:
+            if WALL_BUDGET_S - (time.time() - T_START) > 150:
+                out["residual_step"] = residual_step(args, mat, last_b, span, opts, rowval is None, W)
+                progress("residual_step done")
+            else:
+                out["residual_step"] = {"skipped": "the command's wall budget (%d s) was nearly spent"
+                                                   % WALL_BUDGET_S}
         # the engine's default path on this workload, under its own keys (~60 s together; they run
         # BEFORE the CPU leg, which fits itself into whatever is left of the wall budget)
         if world == 1 and args.workload == "c4" and args.scale == 1 and args.kernel != 5 \
                 and not args.no_item_space and WALL_BUDGET_S - (time.time() - T_START) > 200:
-            out["item_space_step"] = item_space_step(args, mat, step_begins, span, opts, W)
+            if engine_path:
+                out["item_space_step"] = {"skipped": "the timed steps are this path (from scratch, G built "
+                                                     "inside each step): `value` and `roofline`"}
+            else:
+                out["item_space_step"] = item_space_step(args, mat, step_begins, span, opts, W)
+                progress("item_space_step done")
             out["item_space_grid"] = item_space_grid(args, dev)
+            progress("item_space_grid done")
             # north_star's literal target at N = 1: every item column of the matrix, on the path
             # SLIM_Learn takes (G is on the handle by now: its cost is item_space_step's G_build_s)
             left = WALL_BUDGET_S - (time.time() - T_START)
             if left > 150 and not args.no_whole_matrix:
                 out["item_space_whole_matrix"] = item_space_whole_matrix(args, mat, ncols, opts,
                                                                          out["item_space_step"])
+                progress("item_space_whole_matrix done")
             else:
                 out["item_space_whole_matrix"] = {"skipped": "%.0f s of the wall budget left (needs 150)" % left}
         if world == 1 and args.cpu_seconds > 0 and args.workload != "ml100k":
-            out["cpu_baseline"] = cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols,
-                                               last_b, span, opts, W)
+            if WALL_BUDGET_S - (time.time() - T_START) > 150:   # (its fixed modes and checks: ~110 s)
+                out["cpu_baseline"] = cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols,
+                                                   last_b, span, opts, W)
+                progress("cpu_baseline done")
+            else:
+                out["cpu_baseline"] = {"value": None, "skipped": "the command's wall budget (%d s) was "
+                                                                 "nearly spent" % WALL_BUDGET_S}
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
@@ -433,7 +518,7 @@ def dry_run(args, mat, ncols, per_gpu, opts, nnz):
     solved one after the other.  Reports the solver-kernel time of every rank-to-be, their
     spread (how even the interleaved 32-column granules are) and the projected length of the
     driver's command (warm-up + timed steps at the slowest rank's pace, the extra whole-matrix
-    step, the broadcast of R at one xGMI link's rate) against its 1800 s limit."""
+    step, the broadcast of R at one xGMI link's rate) against RUN_LIMIT_S."""
     N = args.dry_run_world
     span = min(ncols, per_gpu * N)
     ranks = []
@@ -445,6 +530,7 @@ def dry_run(args, mat, ncols, per_gpu, opts, nnz):
         ranks.append({"rank": r, "columns": int(st["ncols_solved"]), "kernel_ms": round(st["kernel_ms"], 1),
                       "wall_ms": round(1e3 * (time.perf_counter() - t0), 1),
                       "alg_bytes": st["alg_bytes"]})
+        progress("dry run: shard %d of %d solved" % (r + 1, N))
     # the same for the N >= 4 extra in item space (strong_whole_matrix.item_space): every rank builds
     # G = R^T R for itself (measured once here) and solves shard r of ALL the columns
     item = None
@@ -467,6 +553,7 @@ def dry_run(args, mat, ncols, per_gpu, opts, nnz):
                 ir.append({"rank": r, "columns": int(st["ncols_solved"]), "kernel_ms": round(st["kernel_ms"], 1),
                            "G_build_ms": round(st["gram_build_ms"], 1),
                            "wall_ms": round(1e3 * (time.perf_counter() - t0), 1)})
+                progress("dry run: shard %d of %d solved in item space" % (r + 1, N))
             g_ms = max(x["G_build_ms"] for x in ir)
             solve_ms = max(x["wall_ms"] - x["G_build_ms"] for x in ir)
             free_b, total_b = __import__("torch").cuda.mem_get_info()
@@ -503,7 +590,7 @@ def dry_run(args, mat, ncols, per_gpu, opts, nnz):
                                     "warmup": round(warm_s, 1), "timed_steps": round(steps * step_s, 1),
                                     "whole_matrix_step": round(whole_s, 1),
                                     "whole_matrix_step_item_space": round(item_s, 1), "total": round(total, 1),
-                                    "limit": 1800.0, "fits": bool(total < 1800.0),
+                                    "limit": RUN_LIMIT_S, "fits": bool(total < RUN_LIMIT_S),
                                     "whole_matrix_step_runs": bool(total < WALL_BUDGET_S)},
             "note": "one device, ranks solved one after the other: no RCCL, no peer copies -- what "
                     "is measured is the evenness of the shards and the step time they imply"}
@@ -518,6 +605,82 @@ def gram_split(st):
             "sums": round(st.get("gram_sums_ms", 0.0) * 1e-3, 2),
             "sums_kernel": round(st.get("gram_sums_kernel_ms", 0.0) * 1e-3, 2),
             "byte_planes": round(st.get("gram_pack_ms", 0.0) * 1e-3, 2)}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, W, b, span, seed):
+    """--dump-outputs: what the last timed step handed its caller -- the model columns
+    [b, b + span) of W (scipy CSC, column j = regressors of item j) -- as .npy files under
+    `dirname`, DUMP_LIMIT_BYTES at most in all:
+      W_column_nnz / _sum / _sqnorm   float64, one entry per column of the step
+      W_columns                       float32 (n, k): the dense columns W[:, W_column_ids]
+      W_column_ids                    float64 (k,): every column of the step when they fit, else a
+                                      sorted sample of k drawn with `seed`
+    Same arguments, same inputs (the matrix and the ranges are seeded): two builds of the project
+    compare file for file."""
+    import numpy as np
+    import scipy.sparse as sp
+    S = sp.csc_matrix(W)[:, b:b + span].astype(np.float64)
+    S.sort_indices()
+    n = S.shape[0]
+    arrays = {"W_column_nnz": np.diff(S.indptr).astype(np.float64),
+              "W_column_sum": np.asarray(S.sum(axis=0)).ravel(),
+              "W_column_sqnorm": np.asarray(S.multiply(S).sum(axis=0)).ravel()}
+    header = 128   # bytes of one .npy header (format 1.0, these shapes)
+    left = DUMP_LIMIT_BYTES - sum(a.nbytes + header for a in arrays.values()) - 2 * header
+    k = int(min(span, left // (4 * n + 8)))
+    pick = np.arange(span) if k == span else \
+        np.sort(np.random.default_rng(seed).choice(span, size=k, replace=False))
+    arrays["W_column_ids"] = (b + pick).astype(np.float64)
+    arrays["W_columns"] = S[:, pick].toarray().astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    nbytes = 0
+    for name, a in arrays.items():
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, a)
+        nbytes += os.path.getsize(path)
+    assert nbytes <= DUMP_LIMIT_BYTES, nbytes
+    return {"dir": os.path.abspath(dirname), "files": sorted(n_ + ".npy" for n_ in arrays),
+            "bytes": nbytes, "columns": [int(b), int(b + span)], "dense_columns": k,
+            "sample": "all" if k == span else "seeded (--seed %d)" % seed}
+
+
+def residual_step(args, mat, b, span, opts, binary, W_timed):
+    """Secondary figure at N = 1, under its own key: the last timed step's columns once more, from
+    scratch on the residual (tile) kernel -- what `value` measured before the timed steps took the
+    engine's own path -- with SURVEY.md 8(d)'s byte model and the PMC bytes of that configuration,
+    and the largest difference of its model from the timed step's (the two kernels walk the same
+    visiting order: fp32 rounding only)."""
+    import scipy.sparse as sp
+    saved = os.environ.get("SLIM_GPU_NO_GRAM")
+    os.environ["SLIM_GPU_NO_GRAM"] = "1"   # (nothing carried: no screen sums from G)
+    try:
+        t0 = time.perf_counter()
+        Wr, st = mat.learn(col_begin=b, col_end=b + span, **dict(opts, kernel=3))
+        dt = time.perf_counter() - t0
+        d = abs(sp.csc_matrix(Wr) - sp.csc_matrix(W_timed))
+        del Wr
+        ks = st["kernel_ms"] * 1e-3
+        gbps = st["alg_bytes"] / max(ks, 1e-9) / 1e9
+        traffic = pmc_traffic(args, span, "tile32", binary)
+        return {"columns": int(span), "seconds": round(dt, 2), "value": span / dt, "unit": "item-columns/s",
+                "kernel": KERNEL_NAMES.get(st["kernel"], st["kernel"]), "kernel_s": round(ks, 2),
+                "nnzW": int(st["nnzW"]), "max_abs_dW_vs_the_timed_step": float(d.max()) if d.nnz else 0.0,
+                "roofline": {"bound": "hbm", "achieved": gbps, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": gbps / HBM_PEAK_GBS, "traffic": float(traffic) if traffic else None,
+                             "achieved_physical": float(traffic) / ks / 1e9 if traffic and ks > 0 else None,
+                             "alg_bytes_per_launch": st["alg_bytes"], "kernel_hash": kernel_hash(),
+                             "note": "algorithmic bytes = 8G+12D+4U+8nnzW per column (binary: "
+                                     "4G+8D+4U+8nnzW), SURVEY.md 8(d)"}}
+    except Exception as e:   # noqa: BLE001 -- an extra must not cost the line
+        return {"error": "%s: %s" % (type(e).__name__, e)}
+    finally:
+        if saved is None:
+            os.environ.pop("SLIM_GPU_NO_GRAM", None)
+        else:
+            os.environ["SLIM_GPU_NO_GRAM"] = saved
 
 
 def item_space_step(args, mat, begins, span, opts, W_res, nmax=5):
@@ -839,7 +1002,7 @@ def cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols, b, span, opts,
     import scipy.sparse as sp
     import slim_oracle as O
 
-    # the whole command has to end inside the driver's 1800 s: what is left of WALL_BUDGET_S
+    # the whole command has to end inside RUN_LIMIT_S: what is left of WALL_BUDGET_S
     # bounds this leg (the modes below shrink or are skipped, and say so)
     def left():
         return WALL_BUDGET_S - (time.time() - T_START)
@@ -849,6 +1012,7 @@ def cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols, b, span, opts,
     R = sp.csr_matrix((vals, rowind.cpu().numpy(), rowptr.cpu().numpy()), shape=(nrows, ncols))
     cores, threads = O.physical_cores()
     O.cache_setup(True)   # one transpose of R for all the oracle calls below (setup is untimed)
+    progress("cpu_baseline: R on the host (%d cores, %d threads)" % (cores, threads))
     kw = dict(l1r=opts["l1r"], l2r=opts["l2r"], optTol=opts["optTol"], maxniters=opts["niters"],
               binary=binary, chunk=1)
     gram = dict(order=O.ORDER_LOCAL, seed=opts["seed"], aty=O.ATY_GRAM)
@@ -861,6 +1025,8 @@ def cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols, b, span, opts,
             O.set_time_budget(budget)
         Wc, stc, _, _ = O.learn_cd(R, cols=np.sort(cols).astype(np.int32), nthreads=nthreads,
                                    return_stats=True, **kw, **mode)
+        progress("cpu_baseline: %d column(s) on %d thread(s) in %.1f s"
+                 % (len(cols), nthreads, O.learn_seconds()))
         return Wc, O.learn_seconds(), stc
 
     # one column on one thread sizes everything else
@@ -938,6 +1104,7 @@ def cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols, b, span, opts,
                              l1r=opts["l1r"], l2r=opts["l2r"], optTol=opts["optTol"])
         dt = abs(Wg[:, tile] - Wt[:, tile])
         d_tile = float(dt.max()) if dt.nnz else 0.0
+        progress("cpu_baseline: tile %d of the last step checked against the oracle" % g)
     # (2) eight columns of the timing sample once more at optTol 1e-12, GPU (its own kernel and
     # order) against the oracle in its per-item order: no order-to-order noise left, so the
     # stated tolerance applies as it is -- no constant fitted to a sample
@@ -949,6 +1116,7 @@ def cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols, b, span, opts,
                      nthreads=min(8, cores), **ktight)
     dtt = abs(sp.csc_matrix(Wgt)[:, tight] - Wot[:, tight])
     d_tight = float(dtt.max()) if dtt.nnz else 0.0
+    progress("cpu_baseline: eight columns at optTol 1e-12 checked against the oracle")
 
     # ---- all physical cores: one column per core, bounded by a time budget --
     # 128 concurrent columns take ~3 minutes per round on these hosts; the sample is bounded

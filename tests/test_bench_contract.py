@@ -55,7 +55,7 @@ def test_dry_run_projection_adds_up():
     """bench.py --dry-run-world N on a stand-in matrix: every shard of the step
     is solved once after one warm-up, the spread is (max - min) / mean of the kernel times, and the
     projected command = start-up + broadcast + warm-up + 20 steps at the slowest shard's wall
-    time + the whole-matrix step, held against the driver's 1800 s."""
+    time + the whole-matrix step, held against the run's limit (bench.RUN_LIMIT_S)."""
     calls = []
 
     class Mat(object):
@@ -76,4 +76,35 @@ def test_dry_run_projection_adds_up():
     p = out["projected_command_s"]
     assert abs(p["total"] - (p["start_up_and_generate"] + p["broadcast_R"] + p["warmup"] + p["timed_steps"]
                              + p["whole_matrix_step"] + p["whole_matrix_step_item_space"])) < 0.2
-    assert p["limit"] == 1800.0 and isinstance(p["fits"], bool)
+    assert p["limit"] == bench.RUN_LIMIT_S and isinstance(p["fits"], bool)
+    # one limit governs the run and the projection: the command's own budget keeps room inside it
+    assert bench.WALL_BUDGET_S < bench.RUN_LIMIT_S
+
+
+def test_dump_outputs_writes_the_step_columns_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: per-column summaries of every column of the step, the dense columns
+    themselves (all when they fit, else a sample fixed by the seed), float32 / float64 only,
+    and never more than the limit in all."""
+    import numpy as np
+    import scipy.sparse as sp
+    n, b, span = 300, 40, 100
+    W = sp.hstack([sp.csc_matrix((n, b), dtype=np.float32),
+                   sp.random(n, span, density=0.05, format="csc", dtype=np.float32, random_state=3),
+                   sp.csc_matrix((n, n - b - span), dtype=np.float32)], format="csc")
+    info = bench.dump_outputs(str(tmp_path / "all"), W, b, span, 1)
+    ids = np.load(str(tmp_path / "all" / "W_column_ids.npy"))
+    assert info["dense_columns"] == span and np.array_equal(ids, np.arange(b, b + span))
+    assert np.array_equal(np.load(str(tmp_path / "all" / "W_columns.npy")), W[:, b:b + span].toarray())
+    assert np.array_equal(np.load(str(tmp_path / "all" / "W_column_nnz.npy")), np.diff(W.indptr)[b:b + span])
+    assert np.allclose(np.load(str(tmp_path / "all" / "W_column_sum.npy")),
+                       np.asarray(W[:, b:b + span].sum(axis=0)).ravel())
+    # a limit that holds 20 dense columns: a seeded sample, the same on every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * (8 * span + 128) + 3 * 128 + 20 * (4 * n + 8))
+    runs = [bench.dump_outputs(str(tmp_path / d), W, b, span, 7) for d in ("s1", "s2")]
+    assert runs[0]["dense_columns"] == 20 and runs[0]["bytes"] <= bench.DUMP_LIMIT_BYTES
+    for name in runs[0]["files"]:
+        a, a2 = np.load(str(tmp_path / "s1" / name)), np.load(str(tmp_path / "s2" / name))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, a2)
+    ids = np.load(str(tmp_path / "s1" / "W_column_ids.npy")).astype(int)
+    assert ids.size == 20 and np.all(np.diff(ids) > 0) and b <= ids[0] and ids[-1] < b + span
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "W_columns.npy")), W[:, ids].toarray())

@@ -1,10 +1,7 @@
 """Host-side mirror of the reference's Python package (slim_amd.SLIM / SLIMatrix):
-parameter handling, id mapping, marshalling -- the parts that run without a GPU --
-and, in the build container only, the reference's own wrapper loaded against this
-repo's libslim.so to confirm the Py_* ABI."""
+parameter handling, id mapping, marshalling -- the parts that run without a GPU."""
 import ctypes as C
 import os
-import sys
 import types
 
 import numpy as np
@@ -139,45 +136,3 @@ def test_load_predict_export_without_gpu(tmp_path, ml100k):
     s2 = SLIM()
     s2.load_model(str(tmp_path / "m2.csr"), str(tmp_path / "map2.csv"))
     assert abs(s2.to_csr() - back).max() == 0
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/python-package/SLIM"),
-                    reason="the reference tree exists only in the build container")
-def test_reference_python_wrapper_binds_to_this_library(tmp_path, monkeypatch, ml100k):
-    """Import the reference's unmodified Python package with its libslim.so lookup
-    (site-packages/SLIM/libslim.so, core.py:31-43) pointed at this repo's library and
-    drive the Py_* entry points that need no GPU."""
-    import site
-    fake = tmp_path / "site"
-    (fake / "SLIM").mkdir(parents=True)
-    os.symlink(_lib.LIB_PATH, str(fake / "SLIM" / "libslim.so"))
-    monkeypatch.setattr(site, "getsitepackages", lambda: [str(fake)])
-    monkeypatch.syspath_prepend("/root/reference/python-package")
-    monkeypatch.setattr(sp, "csr", types.SimpleNamespace(csr_matrix=sp.csr_matrix), raising=False)
-    for k in [k for k in sys.modules if k == "SLIM" or k.startswith("SLIM.")]:
-        monkeypatch.delitem(sys.modules, k)
-    ref = pytest.importorskip("SLIM")
-    R, _ = ml100k
-    mat = ref.SLIMatrix(R)
-    assert mat.nUsers == 934
-    import slim_oracle as O
-    from slim_amd.io import write_csr_text
-    W = O.learn_cd(R, order=O.ORDER_PERM, aty=O.ATY_GRAM, cols=np.arange(0, 1683, 4, dtype=np.int32),
-                   nthreads=4)
-    write_csr_text(str(tmp_path / "m.csr"), sp.csr_matrix(W))
-    np.savetxt(str(tmp_path / "map.csv"), np.arange(1683), fmt="%s")
-    model = ref.SLIM()
-    model.load_model(str(tmp_path / "m.csr"), str(tmp_path / "map.csv"))
-    out = model.predict(mat, nrcmds=10)
-    ids, _ = O.predict(W, R, 10)
-    filled = ids[7] >= 0
-    assert np.array_equal(np.asarray(out[7])[filled], ids[7][filled])
-    assert abs(model.to_csr() - sp.csr_matrix(W)).max() == 0
-    # training through the reference wrapper reaches the engine and, without a GPU,
-    # fails loudly instead of falling back
-    from conftest import has_gpu
-    if not has_gpu():
-        with pytest.raises(RuntimeError):
-            model.train({"niters": 5}, mat)
-    for k in [k for k in sys.modules if k == "SLIM" or k.startswith("SLIM.")]:
-        sys.modules.pop(k, None)
