@@ -33,30 +33,12 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "hip_check.hpp"
 #include "host_csr.hpp"
 
 namespace slimamd {
 
 namespace {
-
-struct HipFail {
-  hipError_t code;
-  const char* where;
-};
-#define ADMM_TRY(expr)                                          \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) throw HipFail{_e, #expr};             \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  explicit DevBuf(size_t n) { ADMM_TRY(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * (n ? n : 1))); }
-  ~DevBuf() { (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
 
 // ---- the two libraries, resolved at first use ------------------------------------------
 struct DenseLibs {
@@ -290,11 +272,11 @@ slim_csr_t* learn_admm(int32_t nrows, const ssize_t* rowptr, const int32_t* rowi
   try {
     (void)hipGetLastError();
     int ndev = 0;
-    ADMM_TRY(hipGetDeviceCount(&ndev));
+    HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
-    if (opt.device >= 0) ADMM_TRY(hipSetDevice(opt.device));
+    if (opt.device >= 0) HIP_TRY(hipSetDevice(opt.device));
     size_t free_b = 0, total_b = 0;
-    ADMM_TRY(hipMemGetInfo(&free_b, &total_b));
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     if ((double)n2 * 8.0 * 6.5 > (double)free_b)
       return fail(SLIM_ERROR_MEMORY, "SLIM_Learn(admm): six " + std::to_string(m) + " x " +
                                          std::to_string(m) + " fp64 matrices do not fit this GPU");
@@ -307,11 +289,11 @@ slim_csr_t* learn_admm(int32_t nrows, const ssize_t* rowptr, const int32_t* rowi
     mark("libraries resolved");
     hipDeviceProp_t prop;
     int dev = 0;
-    ADMM_TRY(hipGetDevice(&dev));
-    ADMM_TRY(hipGetDeviceProperties(&prop, dev));
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipGetDeviceProperties(&prop, dev));
     const int cap = prop.multiProcessorCount * 8;
     hipStream_t st = nullptr;
-    ADMM_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     void* handle = nullptr;
     if (libs.create_handle(&handle) != 0) {
       (void)hipStreamDestroy(st);
@@ -330,39 +312,39 @@ slim_csr_t* learn_admm(int32_t nrows, const ssize_t* rowptr, const int32_t* rowi
     } cleanup{libs, handle, st};
 
     // R on the device
-    DevBuf<int64_t> d_ptr((size_t)nrows + 1), d_cnt((size_t)m + 1);
-    DevBuf<int32_t> d_ind((size_t)nnz), d_info(1);
-    DevBuf<float> d_val(rowval ? (size_t)nnz : 1);
+    DeviceBuffer<int64_t> d_ptr((size_t)nrows + 1), d_cnt((size_t)m + 1);
+    DeviceBuffer<int32_t> d_ind((size_t)nnz), d_info(1);
+    DeviceBuffer<float> d_val(rowval ? (size_t)nnz : 1);
     static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
-    ADMM_TRY(hipMemcpyAsync(d_ptr.p, rowptr, sizeof(int64_t) * ((size_t)nrows + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_ptr.get(), rowptr, sizeof(int64_t) * ((size_t)nrows + 1), hipMemcpyHostToDevice, st));
     if (nnz) {
-      ADMM_TRY(hipMemcpyAsync(d_ind.p, rowind, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_ind.get(), rowind, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
       if (rowval)
-        ADMM_TRY(hipMemcpyAsync(d_val.p, rowval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_val.get(), rowval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
     }
-    DevBuf<double> T((size_t)n2), A((size_t)n2), P((size_t)n2), W((size_t)n2), C((size_t)n2), gam((size_t)m);
-    ADMM_TRY(hipMemsetAsync(T.p, 0, sizeof(double) * (size_t)n2, st));
-    ADMM_TRY(hipMemsetAsync(W.p, 0, sizeof(double) * (size_t)n2, st));
-    ADMM_TRY(hipMemsetAsync(C.p, 0, sizeof(double) * (size_t)n2, st));
+    DeviceBuffer<double> T((size_t)n2), A((size_t)n2), P((size_t)n2), W((size_t)n2), C((size_t)n2), gam((size_t)m);
+    HIP_TRY(hipMemsetAsync(T.get(), 0, sizeof(double) * (size_t)n2, st));
+    HIP_TRY(hipMemsetAsync(W.get(), 0, sizeof(double) * (size_t)n2, st));
+    HIP_TRY(hipMemsetAsync(C.get(), 0, sizeof(double) * (size_t)n2, st));
 
     const double rho = 10000.0;  // estimate.c:48
     const int maxiters = 30;     // estimate.c:49
     // T = R^T R
     hipLaunchKernelGGL(k_gram_dense, dim3(grid_for((int64_t)nrows * 64, 256, cap)), dim3(256), 0, st,
-                       nrows, m, d_ptr.p, d_ind.p, rowval ? d_val.p : nullptr, T.p);
-    ADMM_TRY(hipGetLastError());
+                       nrows, m, d_ptr.get(), d_ind.get(), rowval ? d_val.get() : nullptr, T.get());
+    HIP_TRY(hipGetLastError());
     // P = (T + (l2 + rho) I)^-1 (estimate.c:139-163)
-    hipLaunchKernelGGL(k_copy_add_diag, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, m, T.p, P.p,
+    hipLaunchKernelGGL(k_copy_add_diag, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, m, T.get(), P.get(),
                        opt.l2r + rho);
-    ADMM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // Blocked right-looking Cholesky of P in place (column-major lower == the row-major upper
     // triangle LAPACKE_dpotrf(ROW_MAJOR, 'U') fills, estimate.c:150), then the inverse.
     const double one = 1.0, zero = 0.0, minus_one = -1.0;
-    ADMM_TRY(hipMemsetAsync(d_info.p, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(d_info.get(), 0, sizeof(int32_t), st));
     for (int32_t k = 0; k < m; k += kNB) {
       const int32_t kb = std::min(kNB, m - k), rest = m - k - kb;
-      double* Akk = P.p + (int64_t)k * m + k;
-      hipLaunchKernelGGL(k_potf2, dim3(1), dim3(kNB), 0, st, kb, k, m, Akk, d_info.p);
+      double* Akk = P.get() + (int64_t)k * m + k;
+      hipLaunchKernelGGL(k_potf2, dim3(1), dim3(kNB), 0, st, kb, k, m, Akk, d_info.get());
       if (rest > 0) {
         double* A21 = Akk + kb;                    // rows k+kb.., columns k..k+kb
         double* A22 = Akk + (int64_t)kb * m + kb;  // trailing block
@@ -371,53 +353,53 @@ slim_csr_t* learn_admm(int32_t nrows, const ssize_t* rowptr, const int32_t* rowi
           return fail(SLIM_ERROR, "SLIM_Learn(admm): rocBLAS dtrsm / dsyrk failed");
       }
     }
-    ADMM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     int32_t info = 0;
-    ADMM_TRY(hipMemcpyAsync(&info, d_info.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    ADMM_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&info, d_info.get(), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (info != 0) return fail(SLIM_ERROR, "SLIM_Learn(admm): R^T R + (l2 + rho) I is not positive definite");
     mark("R^T R + Cholesky");
     // X = L^-1 (W's storage is free until the iterations start), P^-1 = X^T X
-    hipLaunchKernelGGL(k_identity, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, m, W.p);
-    if (libs.dtrsm(handle, kSideLeft, kFillLower, kOpNone, kNonUnit, m, m, &one, P.p, m, W.p, m) != 0 ||
-        libs.dgemm(handle, kOpTrans, kOpNone, m, m, m, &one, W.p, m, W.p, m, &zero, P.p, m) != 0)
+    hipLaunchKernelGGL(k_identity, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, m, W.get());
+    if (libs.dtrsm(handle, kSideLeft, kFillLower, kOpNone, kNonUnit, m, m, &one, P.get(), m, W.get(), m) != 0 ||
+        libs.dgemm(handle, kOpTrans, kOpNone, m, m, m, &one, W.get(), m, W.get(), m, &zero, P.get(), m) != 0)
       return fail(SLIM_ERROR, "SLIM_Learn(admm): rocBLAS dtrsm / dgemm failed");
-    ADMM_TRY(hipMemsetAsync(W.p, 0, sizeof(double) * (size_t)n2, st));
-    hipLaunchKernelGGL(k_symmetrize, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, m, P.p);  // :160-163
-    ADMM_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(W.get(), 0, sizeof(double) * (size_t)n2, st));
+    hipLaunchKernelGGL(k_symmetrize, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, m, P.get());  // :160-163
+    HIP_TRY(hipGetLastError());
     // A = P T (row-major): column-major A^T = T^T P^T -> dgemm(T, P)
-    if (libs.dgemm(handle, kOpNone, kOpNone, m, m, m, &one, T.p, m, P.p, m, &zero, A.p, m) != 0)
+    if (libs.dgemm(handle, kOpNone, kOpNone, m, m, m, &one, T.get(), m, P.get(), m, &zero, A.get(), m) != 0)
       return fail(SLIM_ERROR, "SLIM_Learn(admm): rocblas_dgemm failed");
-    ADMM_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     mark("inverse + A = P T");
     const double irho = 1.0 / rho, kappa = opt.l1r / rho;
     for (int it = 0; it < maxiters; ++it) {
-      hipLaunchKernelGGL(k_w_pre, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, rho, W.p, C.p);
+      hipLaunchKernelGGL(k_w_pre, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, rho, W.get(), C.get());
       // T = P W
-      if (libs.dgemm(handle, kOpNone, kOpNone, m, m, m, &one, W.p, m, P.p, m, &zero, T.p, m) != 0)
+      if (libs.dgemm(handle, kOpNone, kOpNone, m, m, m, &one, W.get(), m, P.get(), m, &zero, T.get(), m) != 0)
         return fail(SLIM_ERROR, "SLIM_Learn(admm): rocblas_dgemm failed");
-      hipLaunchKernelGGL(k_gamma, dim3((m + 255) / 256), dim3(256), 0, st, m, T.p, A.p, P.p, gam.p);
+      hipLaunchKernelGGL(k_gamma, dim3((m + 255) / 256), dim3(256), 0, st, m, T.get(), A.get(), P.get(), gam.get());
       hipLaunchKernelGGL(k_iterate, dim3(grid_for(n2, 256, cap)), dim3(256), 0, st, n2, m, rho, irho,
-                         kappa, T.p, A.p, P.p, gam.p, W.p, C.p);
-      ADMM_TRY(hipGetLastError());
+                         kappa, T.get(), A.get(), P.get(), gam.get(), W.get(), C.get());
+      HIP_TRY(hipGetLastError());
     }
     // the model's row view: positive entries of W, ascending j in every row
-    hipLaunchKernelGGL(k_count_rows, dim3(grid_for((int64_t)m * 64, 256, cap)), dim3(256), 0, st, m, W.p,
-                       d_cnt.p);
-    ADMM_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_count_rows, dim3(grid_for((int64_t)m * 64, 256, cap)), dim3(256), 0, st, m, W.get(),
+                       d_cnt.get());
+    HIP_TRY(hipGetLastError());
     std::vector<int64_t> h_cnt((size_t)m + 1, 0);
-    ADMM_TRY(hipMemcpyAsync(h_cnt.data(), d_cnt.p, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, st));
-    ADMM_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h_cnt.data(), d_cnt.get(), sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     mark("30 iterations + row counts");
     std::vector<int64_t> h_ptr((size_t)m + 1, 0);
     for (int32_t i = 0; i < m; ++i) h_ptr[(size_t)i + 1] = h_ptr[(size_t)i] + h_cnt[(size_t)i];
     const int64_t wnnz = h_ptr[(size_t)m];
-    DevBuf<int32_t> d_wind((size_t)wnnz);
-    DevBuf<float> d_wval((size_t)wnnz);
-    ADMM_TRY(hipMemcpyAsync(d_cnt.p, h_ptr.data(), sizeof(int64_t) * ((size_t)m + 1), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_emit_rows, dim3(grid_for((int64_t)m * 64, 256, cap)), dim3(256), 0, st, m, W.p,
-                       d_cnt.p, d_wind.p, d_wval.p);
-    ADMM_TRY(hipGetLastError());
+    DeviceBuffer<int32_t> d_wind((size_t)wnnz);
+    DeviceBuffer<float> d_wval((size_t)wnnz);
+    HIP_TRY(hipMemcpyAsync(d_cnt.get(), h_ptr.data(), sizeof(int64_t) * ((size_t)m + 1), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_emit_rows, dim3(grid_for((int64_t)m * 64, 256, cap)), dim3(256), 0, st, m, W.get(),
+                       d_cnt.get(), d_wind.get(), d_wval.get());
+    HIP_TRY(hipGetLastError());
     slim_csr_t* model = csr_new();
     if (!model) return fail(SLIM_ERROR_MEMORY, "SLIM_Learn(admm): out of host memory");
     model->nrows = model->ncols = m;
@@ -430,15 +412,15 @@ slim_csr_t* learn_admm(int32_t nrows, const ssize_t* rowptr, const int32_t* rowi
     }
     for (int32_t i = 0; i <= m; ++i) model->rowptr[i] = (ssize_t)h_ptr[(size_t)i];
     if (wnnz) {
-      ADMM_TRY(hipMemcpyAsync(model->rowind, d_wind.p, sizeof(int32_t) * (size_t)wnnz, hipMemcpyDeviceToHost, st));
-      ADMM_TRY(hipMemcpyAsync(model->rowval, d_wval.p, sizeof(float) * (size_t)wnnz, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(model->rowind, d_wind.get(), sizeof(int32_t) * (size_t)wnnz, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(model->rowval, d_wval.get(), sizeof(float) * (size_t)wnnz, hipMemcpyDeviceToHost, st));
     }
-    ADMM_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     csr_build_index(model, 0);  // + the column view every model handle of this library carries
     if (status) *status = SLIM_OK;
     return model;
   } catch (const HipFail& e) {
-    return fail(e.code == hipErrorOutOfMemory ? SLIM_ERROR_MEMORY : SLIM_ERROR,
+    return fail(status_of(e),
                 std::string("SLIM_Learn(admm): HIP error '") + hipGetErrorString(e.code) + "' in " +
                     e.where + " -- training needs a gfx950 GPU; there is no CPU fallback");
   }

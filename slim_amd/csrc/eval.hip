@@ -19,33 +19,12 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "hip_check.hpp"
 #include "host_csr.hpp"
 
 namespace slimamd {
 
 namespace {
-
-struct HipFail {
-  hipError_t code;
-  const char* where;
-};
-#define EVAL_TRY(expr)                                          \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) throw HipFail{_e, #expr};             \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  explicit DevBuf(size_t n) { EVAL_TRY(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * (n ? n : 1))); }
-  ~DevBuf() { (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void upload(const T* src, size_t n) {
-    if (n) EVAL_TRY(hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice));
-  }
-};
 
 // ---- HR / ARHR -------------------------------------------------------------------------
 
@@ -238,9 +217,14 @@ int cu_count() {
   return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 }
 
+template <class T>
+void upload(DeviceBuffer<T>& b, const T* src, size_t n) {
+  if (n) HIP_TRY(hipMemcpy(b.get(), src, sizeof(T) * n, hipMemcpyHostToDevice));
+}
+
 int32_t fail(const char* who, const HipFail& e) {
   set_error(std::string(who) + ": HIP error '" + hipGetErrorString(e.code) + "' in " + e.where);
-  return e.code == hipErrorOutOfMemory ? SLIM_ERROR_MEMORY : SLIM_ERROR;
+  return status_of(e);
 }
 
 }  // namespace
@@ -258,27 +242,27 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
   try {
     (void)hipGetLastError();
     const int64_t tnnz = tst->rowptr[nusers];
-    DevBuf<int32_t> d_lists((size_t)nusers * nrcmds), d_counts((size_t)nusers), d_tind((size_t)tnnz),
+    DeviceBuffer<int32_t> d_lists((size_t)nusers * nrcmds), d_counts((size_t)nusers), d_tind((size_t)tnnz),
         d_fm((size_t)std::max(fm_ncols, 1)), d_n(3);
-    DevBuf<int64_t> d_tptr((size_t)nusers + 1);
-    DevBuf<UserTerms> d_terms((size_t)nusers);
-    DevBuf<float> d_f(4);
-    d_lists.upload(lists, (size_t)nusers * nrcmds);
-    d_counts.upload(counts, (size_t)nusers);
+    DeviceBuffer<int64_t> d_tptr((size_t)nusers + 1);
+    DeviceBuffer<UserTerms> d_terms((size_t)nusers);
+    DeviceBuffer<float> d_f(4);
+    upload(d_lists, lists, (size_t)nusers * nrcmds);
+    upload(d_counts, counts, (size_t)nusers);
     static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
-    d_tptr.upload(reinterpret_cast<const int64_t*>(tst->rowptr), (size_t)nusers + 1);
-    d_tind.upload(tst->rowind, (size_t)tnnz);
-    d_fm.upload(fmarker, (size_t)fm_ncols);
+    upload(d_tptr, reinterpret_cast<const int64_t*>(tst->rowptr), (size_t)nusers + 1);
+    upload(d_tind, tst->rowind, (size_t)tnnz);
+    upload(d_fm, fmarker, (size_t)fm_ncols);
     const int blocks = std::max(1, std::min((nusers + 255) / 256, cu_count() * 8));
-    hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, 0, nusers, nrcmds, d_lists.p,
-                       d_counts.p, d_tptr.p, d_tind.p, d_fm.p, fm_ncols, d_terms.p);
-    EVAL_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sum_in_user_order, dim3(1), dim3(64), 0, 0, nusers, d_terms.p, d_f.p, d_n.p);
-    EVAL_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, 0, nusers, nrcmds, d_lists.get(),
+                       d_counts.get(), d_tptr.get(), d_tind.get(), d_fm.get(), fm_ncols, d_terms.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sum_in_user_order, dim3(1), dim3(64), 0, 0, nusers, d_terms.get(), d_f.get(), d_n.get());
+    HIP_TRY(hipGetLastError());
     float f[4];
     int32_t n[3];
-    EVAL_TRY(hipMemcpy(f, d_f.p, sizeof(f), hipMemcpyDeviceToHost));
-    EVAL_TRY(hipMemcpy(n, d_n.p, sizeof(n), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(f, d_f.get(), sizeof(f), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n, d_n.get(), sizeof(n), hipMemcpyDeviceToHost));
     out->nvalid = n[0];
     out->nvalid_head = n[1];
     out->nvalid_tail = n[2];
@@ -305,39 +289,39 @@ int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t
   try {
     (void)hipGetLastError();
     const int64_t wnnz = W->rowptr[W->nrows], hnnz = hist->rowptr[nusers];
-    DevBuf<int64_t> d_wptr((size_t)W->nrows + 1), d_hptr((size_t)nusers + 1);
-    DevBuf<int32_t> d_wind((size_t)wnnz), d_hind((size_t)hnnz), d_neg((size_t)nusers * nnegs),
+    DeviceBuffer<int64_t> d_wptr((size_t)W->nrows + 1), d_hptr((size_t)nusers + 1);
+    DeviceBuffer<int32_t> d_wind((size_t)wnnz), d_hind((size_t)hnnz), d_neg((size_t)nusers * nnegs),
         d_oid((size_t)nusers * nrcmds), d_bad(1);
-    DevBuf<float> d_wval((size_t)wnnz), d_hval(hist->rowval ? (size_t)hnnz : 1),
+    DeviceBuffer<float> d_wval((size_t)wnnz), d_hval(hist->rowval ? (size_t)hnnz : 1),
         d_osc((size_t)nusers * nrcmds);
-    d_wptr.upload(reinterpret_cast<const int64_t*>(W->rowptr), (size_t)W->nrows + 1);
-    d_hptr.upload(reinterpret_cast<const int64_t*>(hist->rowptr), (size_t)nusers + 1);
-    d_wind.upload(W->rowind, (size_t)wnnz);
-    d_wval.upload(W->rowval, (size_t)wnnz);
-    d_hind.upload(hist->rowind, (size_t)hnnz);
-    if (hist->rowval) d_hval.upload(hist->rowval, (size_t)hnnz);
-    d_neg.upload(negitems, (size_t)nusers * nnegs);
-    EVAL_TRY(hipMemset(d_bad.p, 0, sizeof(int32_t)));
+    upload(d_wptr, reinterpret_cast<const int64_t*>(W->rowptr), (size_t)W->nrows + 1);
+    upload(d_hptr, reinterpret_cast<const int64_t*>(hist->rowptr), (size_t)nusers + 1);
+    upload(d_wind, W->rowind, (size_t)wnnz);
+    upload(d_wval, W->rowval, (size_t)wnnz);
+    upload(d_hind, hist->rowind, (size_t)hnnz);
+    if (hist->rowval) upload(d_hval, hist->rowval, (size_t)hnnz);
+    upload(d_neg, negitems, (size_t)nusers * nnegs);
+    HIP_TRY(hipMemset(d_bad.get(), 0, sizeof(int32_t)));
     const int cus = cu_count();
     hipLaunchKernelGGL(k_rows_ascending, dim3(std::max(1, std::min(W->nrows / 256 + 1, cus * 8))),
-                       dim3(256), 0, 0, W->nrows, d_wptr.p, d_wind.p, d_bad.p);
-    EVAL_TRY(hipGetLastError());
+                       dim3(256), 0, 0, W->nrows, d_wptr.get(), d_wind.get(), d_bad.get());
+    HIP_TRY(hipGetLastError());
     int32_t bad = 0;
-    EVAL_TRY(hipMemcpy(&bad, d_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&bad, d_bad.get(), sizeof(int32_t), hipMemcpyDeviceToHost));
     if (bad) {
       set_error("SLIMGPU_Predict1vsK: model rows are not ascending by item id");
       return SLIM_ERROR_INPUT;
     }
     hipLaunchKernelGGL(k_topn_1vsk, dim3(std::max(1, std::min(nusers, cus * 16))), dim3(64), 0, 0,
-                       nusers, W->nrows, W->ncols, nrcmds, nnegs, d_wptr.p, d_wind.p, d_wval.p,
-                       d_hptr.p, d_hind.p, hist->rowval ? d_hval.p : nullptr, d_neg.p, d_oid.p,
-                       d_osc.p);
-    EVAL_TRY(hipGetLastError());
+                       nusers, W->nrows, W->ncols, nrcmds, nnegs, d_wptr.get(), d_wind.get(), d_wval.get(),
+                       d_hptr.get(), d_hind.get(), hist->rowval ? d_hval.get() : nullptr, d_neg.get(), d_oid.get(),
+                       d_osc.get());
+    HIP_TRY(hipGetLastError());
     const int32_t n = std::min(nnegs, nrcmds);
     std::vector<int32_t> h_id((size_t)nusers * nrcmds);
     std::vector<float> h_sc((size_t)nusers * nrcmds);
-    EVAL_TRY(hipMemcpy(h_id.data(), d_oid.p, sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost));
-    EVAL_TRY(hipMemcpy(h_sc.data(), d_osc.p, sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_id.data(), d_oid.get(), sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_sc.data(), d_osc.get(), sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost));
     for (int32_t u = 0; u < nusers; ++u)
       for (int32_t r = 0; r < n; ++r) {
         output[(int64_t)u * nrcmds + r] = h_id[(size_t)u * nrcmds + r];

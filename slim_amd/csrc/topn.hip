@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "hip_check.hpp"
 #include "host_csr.hpp"
 
 namespace slimamd {
@@ -478,25 +479,6 @@ __global__ __launch_bounds__(64 * NW) void topn_chunk_kernel(const TopN2Args T) 
   }
 }
 
-struct HipFail {
-  hipError_t code;
-  const char* where;
-};
-#define TOPN_TRY(expr)                                          \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) throw HipFail{_e, #expr};             \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  explicit DevBuf(size_t n) { TOPN_TRY(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * (n ? n : 1))); }
-  ~DevBuf() { (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 }  // namespace
 
 // Top-N lists of every history row.  output/scores are [nusers][nrcmds], slots beyond a
@@ -516,28 +498,28 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
   try {
     (void)hipGetLastError();  // a failure of an earlier call must not be reported by this one
     int ndev = 0;
-    TOPN_TRY(hipGetDeviceCount(&ndev));
+    HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
     hipDeviceProp_t prop;
     int dev = 0;
-    TOPN_TRY(hipGetDevice(&dev));
-    TOPN_TRY(hipGetDeviceProperties(&prop, dev));
-    struct { const int64_t* p; } d_wptr{W.d_ptr};
-    struct { const int32_t* p; } d_wind{W.d_ind};
-    struct { const float* p; } d_wval{W.d_val};
-    DevBuf<int64_t> d_hptr((size_t)nusers + 1);
-    DevBuf<int32_t> d_hind((size_t)hnnz);
-    DevBuf<float> d_hval(hist->rowval ? (size_t)hnnz : 1);
-    DevBuf<float> d_oscore((size_t)nusers * nrcmds);
-    DevBuf<int32_t> d_oid((size_t)nusers * nrcmds), d_ocnt((size_t)nusers), d_queue(2);
-    TOPN_TRY(hipMemcpy(d_hptr.p, hist->rowptr, sizeof(int64_t) * ((size_t)nusers + 1), hipMemcpyHostToDevice));
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    const int64_t* d_wptr = W.d_ptr;
+    const int32_t* d_wind = W.d_ind;
+    const float* d_wval = W.d_val;
+    DeviceBuffer<int64_t> d_hptr((size_t)nusers + 1);
+    DeviceBuffer<int32_t> d_hind((size_t)hnnz);
+    DeviceBuffer<float> d_hval(hist->rowval ? (size_t)hnnz : 1);
+    DeviceBuffer<float> d_oscore((size_t)nusers * nrcmds);
+    DeviceBuffer<int32_t> d_oid((size_t)nusers * nrcmds), d_ocnt((size_t)nusers), d_queue(2);
+    HIP_TRY(hipMemcpy(d_hptr.get(), hist->rowptr, sizeof(int64_t) * ((size_t)nusers + 1), hipMemcpyHostToDevice));
     if (hnnz) {
-      TOPN_TRY(hipMemcpy(d_hind.p, hist->rowind, sizeof(int32_t) * (size_t)hnnz, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_hind.get(), hist->rowind, sizeof(int32_t) * (size_t)hnnz, hipMemcpyHostToDevice));
       if (hist->rowval)
-        TOPN_TRY(hipMemcpy(d_hval.p, hist->rowval, sizeof(float) * (size_t)hnnz, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hval.get(), hist->rowval, sizeof(float) * (size_t)hnnz, hipMemcpyHostToDevice));
     }
-    TOPN_TRY(hipMemset(d_queue.p, 0, 2 * sizeof(int32_t)));
-    TOPN_TRY(hipMemset(d_ocnt.p, 0, sizeof(int32_t) * (size_t)nusers));
+    HIP_TRY(hipMemset(d_queue.get(), 0, 2 * sizeof(int32_t)));
+    HIP_TRY(hipMemset(d_ocnt.get(), 0, sizeof(int32_t) * (size_t)nusers));
 
     // kernel choice: score chunks in LDS (lists of up to 64, rows of W sorted by id), else the
     // one-wavefront-per-user kernel with its vectors in HBM.  SLIM_TOPN_KERNEL=wave|chunk and
@@ -549,9 +531,9 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
       int32_t unsorted = 0;
       if (wnnz > 0) {
         hipLaunchKernelGGL(k_rows_sorted, dim3(std::max(1, std::min(W.nrows / 4 + 1, prop.multiProcessorCount * 8))),
-                           dim3(256), 0, 0, W.nrows, d_wptr.p, d_wind.p, d_queue.p + 1);
-        TOPN_TRY(hipGetLastError());
-        TOPN_TRY(hipMemcpy(&unsorted, d_queue.p + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+                           dim3(256), 0, 0, W.nrows, d_wptr, d_wind, d_queue.get() + 1);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&unsorted, d_queue.get() + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
       }
       if (unsorted) chunked = false;
     }
@@ -586,12 +568,12 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
     }
 
     if (chunked) {
-      DevBuf<uint32_t> d_split((size_t)std::max(W.nrows, 1) * ((size_t)nchunks + 1));
+      DeviceBuffer<uint32_t> d_split((size_t)std::max(W.nrows, 1) * ((size_t)nchunks + 1));
       if (W.nrows > 0) {
         const int64_t total = (int64_t)W.nrows * (nchunks + 1);
         hipLaunchKernelGGL(k_row_split, dim3((unsigned)std::min<int64_t>((total + 255) / 256, prop.multiProcessorCount * 16)),
-                           dim3(256), 0, 0, W.nrows, nchunks, cw, d_wptr.p, d_wind.p, d_split.p);
-        TOPN_TRY(hipGetLastError());
+                           dim3(256), 0, 0, W.nrows, nchunks, cw, d_wptr, d_wind, d_split.get());
+        HIP_TRY(hipGetLastError());
       }
       TopN2Args T;
       T.nusers = nusers;
@@ -602,22 +584,22 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
       T.nchunks = nchunks;
       T.pos_bits = pos_bits;
       T.wlast = wnnz > 0 ? (uint32_t)(wnnz - 1) : 0u;
-      T.wptr = d_wptr.p; T.wind = d_wind.p; T.wval = d_wval.p; T.wsplit = d_split.p;
-      T.hptr = d_hptr.p; T.hind = d_hind.p; T.hval = hist->rowval ? d_hval.p : nullptr;
-      T.out_ids = d_oid.p; T.out_scores = d_oscore.p; T.out_cnt = d_ocnt.p; T.queue = d_queue.p;
+      T.wptr = d_wptr; T.wind = d_wind; T.wval = d_wval; T.wsplit = d_split.get();
+      T.hptr = d_hptr.get(); T.hind = d_hind.get(); T.hval = hist->rowval ? d_hval.get() : nullptr;
+      T.out_ids = d_oid.get(); T.out_scores = d_oscore.get(); T.out_cnt = d_ocnt.get(); T.queue = d_queue.get();
       const size_t lds = (size_t)t2w * cw * item_bytes + (size_t)t2w * kT2MaxN * 16 + t2w * sizeof(int);
       auto kfn = key32 ? (t2w == 16 ? topn_chunk_kernel<16, uint32_t> : topn_chunk_kernel<8, uint32_t>)
                        : (t2w == 16 ? topn_chunk_kernel<16, unsigned long long>
                                     : topn_chunk_kernel<8, unsigned long long>);
       if (lds > 64 * 1024)
-        TOPN_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / t2w, (160 * 1024) / (lds + 64)));
       const int nwg = std::max(1, std::min<int>(nusers, prop.multiProcessorCount * per_cu));
       const auto t_k0 = std::chrono::steady_clock::now();
       hipLaunchKernelGGL(kfn, dim3(nwg), dim3(64 * t2w), lds, 0, T);
-      TOPN_TRY(hipGetLastError());
-      TOPN_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
       if (std::getenv("SLIM_GPU_TRACE"))
         std::fprintf(stderr, "[trace] top-N chunk kernel: %d users, %d workgroups of %d wavefronts, chunks of %d ids, "
                              "%d-bit keys: %.1f ms (upload + split table before it: %.1f ms)\n",
@@ -628,30 +610,30 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
       const size_t lds = (size_t)nrcmds * 64 * (sizeof(float) + sizeof(unsigned long long) + sizeof(int));
       int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (128 * 1024) / lds));
       const int nwaves = std::max(1, std::min<int>(nusers, prop.multiProcessorCount * per_cu));
-      DevBuf<float> d_score((size_t)nwaves * ncols);
-      DevBuf<unsigned long long> d_disc((size_t)nwaves * ncols);
+      DeviceBuffer<float> d_score((size_t)nwaves * ncols);
+      DeviceBuffer<unsigned long long> d_disc((size_t)nwaves * ncols);
       TopNArgs T;
       T.nusers = nusers;
       T.nitems_rows = W.nrows;
       T.ncols = ncols;
       T.nrcmds = nrcmds;
-      T.wptr = d_wptr.p; T.wind = d_wind.p; T.wval = d_wval.p;
-      T.hptr = d_hptr.p; T.hind = d_hind.p; T.hval = hist->rowval ? d_hval.p : nullptr;
-      T.score = d_score.p; T.disc = d_disc.p;
-      T.out_ids = d_oid.p; T.out_scores = d_oscore.p; T.out_cnt = d_ocnt.p; T.queue = d_queue.p;
+      T.wptr = d_wptr; T.wind = d_wind; T.wval = d_wval;
+      T.hptr = d_hptr.get(); T.hind = d_hind.get(); T.hval = hist->rowval ? d_hval.get() : nullptr;
+      T.score = d_score.get(); T.disc = d_disc.get();
+      T.out_ids = d_oid.get(); T.out_scores = d_oscore.get(); T.out_cnt = d_ocnt.get(); T.queue = d_queue.get();
       if (lds > 64 * 1024)
-        TOPN_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(topn_kernel),
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(topn_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(topn_kernel, dim3(nwaves), dim3(64), lds, 0, T);
-      TOPN_TRY(hipGetLastError());
-      TOPN_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
     }
 
     std::vector<int32_t> h_id((size_t)nusers * nrcmds), h_cnt((size_t)nusers);
     std::vector<float> h_sc((size_t)nusers * nrcmds);
-    TOPN_TRY(hipMemcpy(h_id.data(), d_oid.p, sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost));
-    TOPN_TRY(hipMemcpy(h_sc.data(), d_oscore.p, sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost));
-    TOPN_TRY(hipMemcpy(h_cnt.data(), d_ocnt.p, sizeof(int32_t) * h_cnt.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_id.data(), d_oid.get(), sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_sc.data(), d_oscore.get(), sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_cnt.data(), d_ocnt.get(), sizeof(int32_t) * h_cnt.size(), hipMemcpyDeviceToHost));
     for (int32_t u = 0; u < nusers; ++u) {
       for (int32_t r = 0; r < h_cnt[u]; ++r) {
         output[(int64_t)u * nrcmds + r] = h_id[(size_t)u * nrcmds + r];
@@ -663,7 +645,7 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
   } catch (const HipFail& e) {
     set_error(std::string("SLIMGPU_Predict: HIP error '") + hipGetErrorString(e.code) + "' in " +
               e.where);
-    return e.code == hipErrorOutOfMemory ? SLIM_ERROR_MEMORY : SLIM_ERROR;
+    return status_of(e);
   } catch (const std::bad_alloc&) {
     set_error("SLIMGPU_Predict: out of host memory");
     return SLIM_ERROR_MEMORY;
@@ -680,29 +662,29 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
   try {
     (void)hipGetLastError();
     int ndev = 0;
-    TOPN_TRY(hipGetDeviceCount(&ndev));
+    HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
     const int64_t wnnz = W->rowptr[W->nrows];
-    DevBuf<int64_t> d_wptr((size_t)W->nrows + 1);
-    DevBuf<int32_t> d_wind((size_t)wnnz);
-    DevBuf<float> d_wval((size_t)wnnz);
-    TOPN_TRY(hipMemcpy(d_wptr.p, W->rowptr, sizeof(int64_t) * ((size_t)W->nrows + 1), hipMemcpyHostToDevice));
+    DeviceBuffer<int64_t> d_wptr((size_t)W->nrows + 1);
+    DeviceBuffer<int32_t> d_wind((size_t)wnnz);
+    DeviceBuffer<float> d_wval((size_t)wnnz);
+    HIP_TRY(hipMemcpy(d_wptr.get(), W->rowptr, sizeof(int64_t) * ((size_t)W->nrows + 1), hipMemcpyHostToDevice));
     if (wnnz) {
-      TOPN_TRY(hipMemcpy(d_wind.p, W->rowind, sizeof(int32_t) * (size_t)wnnz, hipMemcpyHostToDevice));
-      TOPN_TRY(hipMemcpy(d_wval.p, W->rowval, sizeof(float) * (size_t)wnnz, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_wind.get(), W->rowind, sizeof(int32_t) * (size_t)wnnz, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_wval.get(), W->rowval, sizeof(float) * (size_t)wnnz, hipMemcpyHostToDevice));
     }
     DeviceRowView v;
     v.nrows = W->nrows;
     v.ncols = W->ncols;
     v.nnz = wnnz;
-    v.d_ptr = d_wptr.p;
-    v.d_ind = d_wind.p;
-    v.d_val = d_wval.p;
+    v.d_ptr = d_wptr.get();
+    v.d_ind = d_wind.get();
+    v.d_val = d_wval.get();
     for (int32_t r = 0; r < W->nrows; ++r) v.max_row = std::max<int64_t>(v.max_row, W->rowptr[r + 1] - W->rowptr[r]);
     return predict_device_view(v, hist, nrcmds, output, scores, counts);
   } catch (const HipFail& e) {
     set_error(std::string("SLIMGPU_Predict: HIP error '") + hipGetErrorString(e.code) + "' in " + e.where);
-    return e.code == hipErrorOutOfMemory ? SLIM_ERROR_MEMORY : SLIM_ERROR;
+    return status_of(e);
   }
 }
 
