@@ -2,7 +2,7 @@
 """bench.py -- item-columns solved per second by the MI355X SLIM engine.
 
 A "step" is one pass of the hot path (SLIMGPU_Learn: EstimateModelCD + SaveModel,
-/root/reference/src/libslim/estimate.c:328-593) over one batch of B item columns of a
+the reference's src/libslim/estimate.c:328-593) over one batch of B item columns of a
 synthetic rating matrix that is already resident in HBM.  Default workload: BASELINE.json
 configs[3], 1M users x 100K items, ~1e9 nnz, l1 = l2 = 1, optTol 1e-7 (the configuration
 the metric is quoted on; it fits one GPU).  With N GPUs (one process per GPU) every rank
@@ -11,30 +11,40 @@ work list dealt round-robin; RCCL only for the one-off broadcast of R and the ga
 learned columns).  Default: B = 8192 columns per GPU and step => weak scaling (at N = 8 a
 step covers 65 536 of the 100 000 columns).  At N = 1 every timed step is a from-scratch
 SLIM_Learn on a fresh handle with the engine's own kernel choice (item space, G = R^T R built
-inside the step); the residual kernel's from-scratch step (~60 s) is reported once beside it
-(residual_step) and compared with the timed step's model.  --scaling strong fixes the columns per step
+inside the step); with --full the residual kernel's from-scratch step (~60 s) is reported once
+beside it (residual_step) and compared with the timed step's model.  --scaling strong fixes the columns per step
 (--batch 0: the whole matrix, north_star's target; 555 s per step on one GPU, which is why
 it is not the default under the driver's 25-step run).
 
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
   python bench.py ... --dump-outputs DIR     (+ the last timed step's model columns, dump_outputs)
+  python bench.py ... --full                 (+ every figure and check that takes runs of its own)
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run does what the headline figure needs and nothing else: it makes the workload resident,
+warms up, times the steps, writes --dump-outputs, and rank 0 prints ONE JSON line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, the configuration) with one extra object that costs
+no run of its own:
   roofline      algorithmic bytes (8G + 12D + 4U + 8 nnzW per column, from
-                the engine's per-column counters) / solver-kernel time measured with HIP
-                events on the engine's stream, against the 8 TB/s HBM peak
+                the engine's per-column counters; item space: the bytes of G streamed) / solver-kernel
+                time of the TIMED steps measured with HIP events on the engine's stream, against the
+                8 TB/s HBM peak
+--full (off by default; `full` in the line says which it was) adds, after the timed steps and
+outside them, under their own keys (never `value`):
+  parity        HR@10 / ARHR on ml100k against the reference's figures (N = 1)
   cpu_baseline  the CPU oracle (a port of the reference's OpenMP CD path; the reference
                 itself cannot be built here) timed on a bounded sample of the same columns
-and, at N = 1 on the default workload, two secondary figures under their own keys (never
-`value`; SURVEY.md 8(d)'s formula does not price them):
+                (`value`: item-columns/s), and its parity checks of the GPU's columns
+  residual_step    the last timed step's columns once more on the residual kernel (N = 1)
+and, at N = 1 on the default workload (SURVEY.md 8(d)'s formula does not price them):
   item_space_step  up to five of the timed steps' column ranges once more, from scratch, in item
                    space (cd_gramr.hpp; G = R^T R built inside the first one's measured time and
                    reported apart and amortised), with the difference of the models
   item_space_grid  the first pairs of the C5 model-selection grid (BASELINE.json configs[4])
                    on the path the engine takes for a grid
   item_space_whole_matrix  every item column of the matrix once (north_star's target at N = 1)
-The command budgets itself (SLIM_BENCH_WALL_BUDGET, 480 s of the RUN_LIMIT_S = 600 s a run of
+  strong_whole_matrix      N >= 4: one step over all item columns, sharded over the GPUs
+A --full run budgets itself (SLIM_BENCH_WALL_BUDGET, 480 s of the RUN_LIMIT_S = 600 s a run of
 20 + 5 steps is given): the extras and the CPU leg shrink or drop out, with a note, rather than
 overrun.  Progress goes to stderr,
 one line per step and phase.
@@ -89,7 +99,7 @@ def parse_args():
     ap.add_argument("--cluster", type=int, default=int(os.environ.get("SLIM_BENCH_CLUSTER", "0")),
                     help="tile kernels: workgroups per tile, 1/2/4/8 (0 = auto)")
     ap.add_argument("--cpu-seconds", type=float, default=30.0,
-                    help="CPU-baseline budget of each one-thread mode (0 disables the whole leg)")
+                    help="--full: CPU-baseline budget of each one-thread mode (0 disables the whole leg)")
     ap.add_argument("--cpu-columns", type=int, default=int(os.environ.get("SLIM_BENCH_CPU_COLUMNS", "512")),
                     help="columns of the last step timed by the parallel CPU-baseline mode (rounds of "
                          "--cpu-threads columns each)")
@@ -101,12 +111,12 @@ def parse_args():
                          "in a step, one after the other, and report the per-rank kernel times, their "
                          "spread and the projected length of the driver's N-GPU command")
     ap.add_argument("--no-item-space", action="store_true",
-                    help="N = 1: skip the secondary figure (first pairs of the C5 grid in item space)")
+                    help="--full at N = 1: skip the secondary figure (first pairs of the C5 grid in item space)")
     ap.add_argument("--shard-gram", action="store_true",
-                    help="N >= 4, the whole-matrix step in item space: form G = R^T R once by all ranks (row blocks + "
+                    help="--full at N >= 4, the whole-matrix step in item space: form G = R^T R once by all ranks (row blocks + "
                          "one RCCL broadcast per block, slim_amd.distributed.build_gram_sharded) instead of once per rank")
     ap.add_argument("--no-whole-matrix", action="store_true",
-                    help="N >= 4: skip the extra whole-matrix (strong-scaling) step")
+                    help="--full: skip the extra whole-matrix (strong-scaling) step")
     ap.add_argument("--replicate", default="broadcast", choices=["broadcast", "generate"])
     ap.add_argument("--backend", default=os.environ.get("SLIM_BENCH_BACKEND", "nccl"),
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo lets several "
@@ -114,6 +124,11 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the model columns the last one learned to "
                          "DIR/<name>.npy (float32 / float64, at most 64 MB; e.g. bench_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything that takes runs of its own: ml100k "
+                         "parity, residual_step, the item_space_* figures, the CPU baseline with its parity "
+                         "checks and, at N >= 4, the whole-matrix steps (off: set up, warm up, time the "
+                         "steps, print the line)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -330,7 +345,8 @@ def main():
     # (only when the command's wall budget has room for it: its length is the timed step's times
     # the ratio of the columns per GPU, and the CPU-free N > 1 run ends right after it)
     whole_est = (elapsed / max(1, args.steps)) * (ncols / float(world)) / max(1, per_gpu) * 1.25
-    go_whole = world >= 4 and not strong and args.workload != "ml100k" and not args.no_whole_matrix
+    go_whole = (args.full and world >= 4 and not strong and args.workload != "ml100k"
+                and not args.no_whole_matrix)
     if go_whole:  # one decision for all ranks (their clocks started at different moments)
         room = torch.tensor([WALL_BUDGET_S - (time.time() - T_START) - whole_est - 60.0],
                             dtype=torch.float64, device=cdev)
@@ -415,6 +431,7 @@ def main():
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True,
             "scaling": args.scaling,
+            "full": bool(args.full),   # False: the figures that take runs of their own were not asked for
             "ranks": {"world": world, "backend": ("nccl (RCCL)" if args.backend == "nccl" else args.backend)
                       if world > 1 else "none (one process)",
                       "kernel_ms_per_rank": [round(v, 1) for v in rank_kernel_ms]},
@@ -467,10 +484,10 @@ def main():
             out["dump_outputs"] = dumped
         if strong_whole is not None:
             out["strong_whole_matrix"] = strong_whole
-        if world == 1:
+        if args.full and world == 1:
             out["parity"] = ml100k_parity(dev.index)
             progress("ml100k parity done")
-        if engine_path:
+        if args.full and engine_path:
             if WALL_BUDGET_S - (time.time() - T_START) > 150:
                 out["residual_step"] = residual_step(args, mat, last_b, span, opts, rowval is None, W)
                 progress("residual_step done")
@@ -479,7 +496,7 @@ def main():
                                                    % WALL_BUDGET_S}
         # the engine's default path on this workload, under its own keys (~60 s together; they run
         # BEFORE the CPU leg, which fits itself into whatever is left of the wall budget)
-        if world == 1 and args.workload == "c4" and args.scale == 1 and args.kernel != 5 \
+        if args.full and world == 1 and args.workload == "c4" and args.scale == 1 and args.kernel != 5 \
                 and not args.no_item_space and WALL_BUDGET_S - (time.time() - T_START) > 200:
             if engine_path:
                 out["item_space_step"] = {"skipped": "the timed steps are this path (from scratch, G built "
@@ -498,7 +515,7 @@ def main():
                 progress("item_space_whole_matrix done")
             else:
                 out["item_space_whole_matrix"] = {"skipped": "%.0f s of the wall budget left (needs 150)" % left}
-        if world == 1 and args.cpu_seconds > 0 and args.workload != "ml100k":
+        if args.full and world == 1 and args.cpu_seconds > 0 and args.workload != "ml100k":
             if WALL_BUDGET_S - (time.time() - T_START) > 150:   # (its fixed modes and checks: ~110 s)
                 out["cpu_baseline"] = cpu_baseline(args, mat, rowptr, rowind, rowval, nrows, ncols,
                                                    last_b, span, opts, W)

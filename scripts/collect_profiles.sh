@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collect the judged artifacts of one bench configuration on the GPU box (run through gpurun):
-#   1. rocprofv3 --kernel-trace --stats of `python bench.py ARGS`          -> kernel stats csv
+#   1. rocprofv3 --kernel-trace --stats of `python bench.py --full ARGS`         -> kernel stats csv
 #   2. one --pmc pass per counter (FETCH_SIZE, WRITE_SIZE) of one timed step of the same
 #      configuration, plus the same counters on calibration launches of known size
 #      (scripts/micro/gather_bw c) -- counters are collected in their own runs, with
@@ -21,11 +21,11 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ -z "${SKIP_STATS:-}" ]; then
   export SLIM_GPU_TRACE=1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o run -- python $R/bench.py --steps ${STEPS:-2} --warmup ${WARMUP:-0} --no-item-space $ARGS > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o run -- python $R/bench.py --steps ${STEPS:-2} --warmup ${WARMUP:-0} --full --no-item-space $ARGS > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
   unset SLIM_GPU_TRACE
 fi
 for c in ${SKIP_PMC:+} $( [ -z "${SKIP_PMC:-}" ] && echo FETCH_SIZE WRITE_SIZE ); do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/${TAG}_pmc_$c -o run -- python $R/bench.py --warmup 0 --steps 1 --cpu-seconds 0 $ARGS > $O/${TAG}_pmc_$c.json 2> $O/${TAG}_pmc_$c.err
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/${TAG}_pmc_$c -o run -- python $R/bench.py --warmup 0 --steps 1 --full --cpu-seconds 0 $ARGS > $O/${TAG}_pmc_$c.json 2> $O/${TAG}_pmc_$c.err
   [ -f $O/cal_$c/cal_counter_collection.csv ] || rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/cal_$c -o cal -- $R/scripts/micro/gather_bw c > /dev/null 2>&1
 done
 cd $R

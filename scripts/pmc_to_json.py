@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turn rocprofv3 --pmc passes of the default bench into profiles/pmc_traffic.json.
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d D1 -o c4 -- python bench.py --warmup 0 --steps 1 --cpu-seconds 0
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d D1 -o c4 -- python bench.py --warmup 0 --steps 1 --full --cpu-seconds 0
   rocprofv3 --pmc WRITE_SIZE ... -d D2 ...
   rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE ... -- scripts/micro/gather_bw c      (calibration, known bytes)
   python scripts/pmc_to_json.py D1/c4_counter_collection.csv D2/c4_counter_collection.csv \
@@ -59,7 +59,7 @@ def main():
                   "kernel": cfg["kernel"], "binary": "binary values" in cfg["workload"]},
         "kernel_hash": bench["roofline"].get("kernel_hash"),
         "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- "
-                   "python bench.py --warmup 0 --steps 1 --cpu-seconds 0 (one pass per counter)",
+                   "python bench.py --warmup 0 --steps 1 --full --cpu-seconds 0 (one pass per counter)",
         "launches": nf, "FETCH_SIZE_kb": f / max(nf, 1), "WRITE_SIZE_kb": w / max(nw, 1),
         "calibration": {"known_bytes_per_launch": known, "gather128_FETCH_SIZE_kb": gf,
                         "scatter128_WRITE_SIZE_kb": sw, "scatter128_FETCH_SIZE_kb": sf},

@@ -8,6 +8,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -108,3 +110,74 @@ def test_dump_outputs_writes_the_step_columns_within_the_limit(tmp_path, monkeyp
     ids = np.load(str(tmp_path / "s1" / "W_column_ids.npy")).astype(int)
     assert ids.size == 20 and np.all(np.diff(ids) > 0) and b <= ids[0] and ids[-1] < b + span
     assert np.array_equal(np.load(str(tmp_path / "s1" / "W_columns.npy")), W[:, ids].toarray())
+
+
+EXTRA_KEYS = ("parity", "residual_step", "item_space_step", "item_space_grid", "item_space_whole_matrix",
+              "cpu_baseline", "strong_whole_matrix")
+
+
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """Everything that takes runs of its own waits behind --full; a plain command line leaves it off."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse_args()
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.parse_args().full is True
+
+
+def _run_bench(*argv):
+    import subprocess
+    import time
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + list(argv)
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines          # stdout: the one JSON line
+    return json.loads(lines[0]), wall
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600, method="thread")
+def test_plain_run_spends_at_most_30_s_outside_its_steps(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` on the default workload, in a process of its own:
+    the whole run from start to exit, less (N + W) x ms_per_step, is at most 30 s (start-up, the
+    matrix, whatever the first step compiles or loads, the dump and the exit all count), and the
+    line carries the headline fields and none of the figures that take runs of their own."""
+    out, wall = _run_bench("--gpus", "1", "--steps", "1", "--warmup", "1",
+                           "--dump-outputs", str(tmp_path / "dump"))
+    outside = wall - 2 * out["ms_per_step"] * 1e-3
+    print("plain run: %.1f s in all, %.1f ms per step, %.1f s outside the steps"
+          % (wall, out["ms_per_step"], outside))
+    assert out["full"] is False and not [k for k in EXTRA_KEYS if k in out]
+    assert out["metric"] == "item-columns solved/sec (whole node)" and out["unit"] == "item-columns/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["n_gpus"] == 1
+    assert out["steps"] == 1 and out["warmup"] == 1 and out["config"]["columns_per_step"] == 8192
+    assert abs(out["value"] - 8192 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert sorted(os.listdir(str(tmp_path / "dump"))) == out["dump_outputs"]["files"]
+    assert outside <= 30.0, outside
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600, method="thread")
+def test_full_run_keeps_what_moved_behind_it():
+    """--full on a 1/50-scale C4: the same timed steps, then the figures and checks that take runs
+    of their own -- ml100k parity, the residual kernel's step compared with the timed step's model,
+    the CPU baseline with its parity checks of the GPU's columns.  (That they are there and ran is
+    what is checked here; how close the models are is the parity tests' business.)"""
+    argv = ("--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c4", "--scale", "0.02",
+            "--batch", "256", "--cpu-seconds", "2")
+    plain, _ = _run_bench(*argv)
+    assert plain["full"] is False and not [k for k in EXTRA_KEYS if k in plain]
+    out, _ = _run_bench(*(argv + ("--full",)))
+    assert out["full"] is True and out["steps"] == 2 and out["value"] > 0
+    assert out["config"] == dict(plain["config"], generate_s=out["config"]["generate_s"],
+                                 stage_s=out["config"]["stage_s"])
+    assert out["roofline"]["nnzW"] == plain["roofline"]["nnzW"] > 0      # the same steps either way
+    assert out["parity"]["match"] is True, out["parity"]
+    rs = out["residual_step"]
+    assert rs["columns"] == 256 and rs["kernel"] == "tile32" and rs["seconds"] > 0, rs
+    assert rs["max_abs_dW_vs_the_timed_step"] >= 0.0, rs
+    cb = out["cpu_baseline"]
+    assert cb["value"] > 0 and isinstance(cb["parity"]["parity_ok"], bool), cb

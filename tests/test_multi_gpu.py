@@ -423,7 +423,7 @@ def test_bench_plain_command_launches_its_own_ranks():
 @pytest.mark.timeout(900, method="thread")
 def test_bench_four_ranks_whole_matrix_extras():
     """The N >= 4 branch of bench.py as the driver will run it at N = 4 / 8, on a 1/50-scale C4
-    (20 000 x 2 000): after the timed steps one step over ALL item columns sharded over the ranks
+    (20 000 x 2 000) with --full: after the timed steps one step over ALL item columns sharded over the ranks
     (`strong_whole_matrix`) and the same step in item space (`item_space`: G = R^T R formed in row
     blocks by the ranks together, --shard-gram, then every rank solves its shard) -- both agreed on by all ranks before any collective, so a
     failure in an extra step costs its key, not the line.  On a one-GPU box the four ranks share
@@ -435,7 +435,7 @@ def test_bench_four_ranks_whole_matrix_extras():
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1",
            "--workload", "c4", "--scale", "0.02", "--batch", "256", "--cluster", "1",
-           "--backend", backend, "--cpu-seconds", "0", "--shard-gram"]
+           "--backend", backend, "--cpu-seconds", "0", "--shard-gram", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
