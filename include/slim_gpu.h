@@ -298,4 +298,8 @@ const char *SLIMGPU_LastError(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* Evaluation of resident models without leaving HBM (eval sets, top-N of the staged rows). */
+#include "slim_gpu_eval.h"
+
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

@@ -1,0 +1,194 @@
+#!/usr/bin/env python3
+"""Learn + evaluate per pair of a model-selection grid with everything resident in HBM (reference loop:
+src/programs/slim_mselect.c:99-196): the tests/golden/l12file grid on a synthetic configuration, one
+held-out item per user as the test set.  Per pair: the solve (SLIMGPU_LearnResident, warm-started from
+the previous model), then the evaluation two ways on the same model, interleaved A / B:
+
+  A  lists through the host: SLIMGPU_ModelPredict on the host handle of the training rows (uploads the
+     history, brings the lists down) + SLIMGPU_Evaluate (uploads the lists again) -- what
+     Py_SLIM_Mselect does with SLIM_GPU_EVAL_RESIDENT=0
+  B  SLIMGPU_ModelEvaluate on an eval set staged once (the fused kernel: 40 bytes come down)
+
+and checks that both give the same figures.  Writes the per-pair table, the totals and the achieved
+w_bytes / kernel_ms against the 8 TB/s HBM peak to --out.
+
+  python scripts/grid_eval.py [--workload c5] [--scale 1.0] [--pairs 0] [--budget-s 900] [--out FILE]
+
+--pairs 0 (default): the short grid -- the cold pair, three l2 steps and one l1 change; N > 0: the first
+N pairs of the file; -1: all of them (each warm-started from the one before it in the list).  The run stops adding pairs when --budget-s is used up and says so.
+"""
+import argparse
+import ctypes as C
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK_GBS = 8000.0
+
+
+def head_tail(pop, nnz):
+    """SLIM_DetermineHeadAndTail (api.c:215-245) from the items' popularity: 0 head, 1 tail."""
+    import numpy as np
+    order = np.argsort(-pop, kind="stable")
+    before = np.concatenate([[0], np.cumsum(pop[order])[:-1]])
+    fm = np.ones(pop.size, np.int32)
+    fm[order[(nnz // 2 - before) > 0]] = 0
+    return fm
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="c5")
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--pairs", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--nrcmds", type=int, default=10)
+    ap.add_argument("--budget-s", type=float, default=900.0)
+    ap.add_argument("--no-a", action="store_true", help="skip path A (no host copy of the training rows)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_eval_c5.txt"))
+    args = ap.parse_args()
+    import numpy as np
+    import scipy.sparse as sp
+    import torch
+    from slim_amd import _lib as _l
+    from slim_amd import synth
+    from slim_amd.constants import SLIM_OK
+    from slim_amd.engine import DeviceMatrix
+
+    t_start = time.time()
+    lines = []
+
+    def say(msg):
+        print(msg, flush=True)
+        lines.append(msg)
+
+    dev = torch.device("cuda", 0)
+    nrows, ncols, target = synth.scaled(args.workload, args.scale) if args.scale != 1 \
+        else synth.CONFIGS[args.workload]
+    rowptr, rowind, _ = synth.generate_csr(nrows, ncols, target, seed=args.seed, device=dev)
+    # one held-out item per user with at least two
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed + 1000)
+    deg = rowptr[1:] - rowptr[:-1]
+    has = deg >= 2
+    off = (torch.rand(nrows, generator=gen, device=dev, dtype=torch.float64) * deg.to(torch.float64)).to(torch.int64)
+    pick = (rowptr[:-1] + torch.minimum(off, torch.clamp(deg - 1, min=0)))[has]
+    keep = torch.ones(rowind.numel(), dtype=torch.bool, device=dev)
+    keep[pick] = False
+    tst_ind = rowind[pick].cpu().numpy()
+    trn_ind = rowind[keep].contiguous()
+    trn_ptr = torch.zeros(nrows + 1, dtype=torch.int64, device=dev)
+    trn_ptr[1:] = torch.cumsum(deg - has.to(torch.int64), 0)
+    has_h = has.cpu().numpy()
+    del rowptr, rowind, keep, pick, off, deg, has
+    torch.cuda.synchronize()
+    nnz = int(trn_ind.numel())
+    T = sp.csr_matrix((np.ones(tst_ind.size, np.float32), tst_ind,
+                       np.concatenate([[0], np.cumsum(has_h)]).astype(np.int64)), shape=(nrows, ncols))
+    pop = torch.bincount(trn_ind.to(torch.int64), minlength=ncols).cpu().numpy().astype(np.int64)
+    fm = head_tail(pop, nnz)
+    say("# grid_eval: %s x %.3g: %d users x %d items, %d training entries, %d test entries (one held out per user)"
+        % (args.workload, args.scale, nrows, ncols, nnz, T.nnz))
+    say("# data ready after %.1f s" % (time.time() - t_start))
+
+    mat = DeviceMatrix.from_device_ptrs(nrows, ncols, trn_ptr.data_ptr(), trn_ind.data_ptr(), 0,
+                                        keepalive=(trn_ptr, trn_ind), device=0)
+    lib = mat._lib
+    t0 = time.time()
+    ev = mat.evaluator(T, nrcmds=args.nrcmds, fmarker=fm)
+    say("# eval set staged once: %.2f s" % (time.time() - t0))
+    hr = ht = None
+    if not args.no_a:
+        t0 = time.time()
+        hp = np.ascontiguousarray(trn_ptr.cpu().numpy(), dtype=np.intp)
+        hi = trn_ind.cpu().numpy()
+        hr = C.c_void_p()
+        assert lib.Py_csr_wrapper(nrows, hp, hi, None, C.byref(hr)) == SLIM_OK
+        del hp, hi
+        from slim_amd.engine import _wrap_rows
+        ht = _wrap_rows(lib, T)
+        say("# host handles for path A (not timed below): %.1f s" % (time.time() - t0))
+
+    allp = [tuple(map(float, l.split())) for l in open(os.path.join(ROOT, "tests", "golden", "l12file")) if l.strip()]
+    if args.pairs == 0:
+        first_l1_change = next(k for k, p in enumerate(allp) if p[0] != allp[0][0])
+        pairs = allp[:3] + allp[first_l1_change:first_l1_change + 2]
+        say("# short grid: the cold pair, two l2 steps, one l1 change, one more l2 step (%d of the file's %d pairs)"
+            % (len(pairs), len(allp)))
+    else:
+        pairs = allp if args.pairs < 0 else allp[:args.pairs]
+    mat.expect_solves(len(allp))
+
+    say("# %-5s %-5s %9s | %8s | %8s %9s %4s %6s %5s %9s %7s | %8s | %s"
+        % ("l1", "l2", "nnzW", "learn_s", "B eval_s", "kernel_ms", "path", "allocs", "d2h", "w_GB", "TB/s", "A eval_s", "hr arhr"))
+    prev = None
+    rows = []
+    for k, (l1, l2) in enumerate(pairs):
+        if time.time() - t_start > args.budget_s:
+            say("# budget of %.0f s used up after %d pairs: the remaining %d were not run"
+                % (args.budget_s, k, len(pairs) - k))
+            break
+        t0 = time.time()
+        cur, st = mat.learn_resident(warm=prev, l1r=l1, l2r=l2, optTol=1e-7, niters=10000, seed=args.seed)
+        learn_s = time.time() - t0
+        if prev is not None:
+            prev.free()
+        prev = cur
+        a_s = float("nan")
+        want = None
+        if hr is not None:     # A first, then B: over the pairs the two alternate A / B / A / B
+            ids = np.full(nrows * args.nrcmds, -1, np.int32)
+            sc = np.zeros(nrows * args.nrcmds, np.float32)
+            met, nv = np.zeros(4), np.zeros(3, np.int32)
+            t0 = time.time()
+            rc = lib.SLIMGPU_ModelPredict(args.nrcmds, cur.handle, hr, ids.ctypes.data_as(C.c_void_p),
+                                          sc.ctypes.data_as(C.c_void_p))
+            a1 = time.time() - t0
+            assert rc == SLIM_OK, _l.last_error()
+            cnt = (ids.reshape(-1, args.nrcmds) >= 0).sum(1).astype(np.int32)   # (the library has them: not timed)
+            t0 = time.time()
+            rc = lib.SLIMGPU_Evaluate(nrows, args.nrcmds, ids, cnt, ht, fm, fm.size, met, nv)
+            a_s = a1 + time.time() - t0
+            assert rc == SLIM_OK, _l.last_error()
+            want = (met.tolist(), nv.tolist())
+            del ids, sc, cnt
+        t0 = time.time()
+        got = ev.evaluate(cur)
+        b_s = time.time() - t0
+        es = ev.stats()
+        if want is not None:
+            have = ([got["hr"], got["hr_head"], got["hr_tail"], got["arhr"]],
+                    [got["nvalid"], got["nvalid_head"], got["nvalid_tail"]])
+            assert have == want, "A and B disagree: %r vs %r" % (want, have)
+        tbs = es["w_bytes"] / max(es["kernel_ms"], 1e-9) / 1e9
+        rows.append((learn_s, b_s, a_s, es["w_bytes"], es["kernel_ms"]))
+        say("  %-5g %-5g %9d | %8.2f | %8.2f %9.1f %4d %6d %5d %9.1f %7.3f | %8.2f | %.4f %.4f"
+            % (l1, l2, cur.nnz, learn_s, b_s, es["kernel_ms"], es["path"], es["device_allocs"], es["d2h_bytes"],
+               es["w_bytes"] / 1e9, tbs, a_s, got["hr"], got["arhr"]))
+    if rows:
+        L, B, A = (sum(r[i] for r in rows) for i in range(3))
+        wb, km = sum(r[3] for r in rows), sum(r[4] for r in rows)
+        say("# totals over %d pairs: learn %.2f s, evaluate B %.2f s%s" %
+            (len(rows), L, B, "" if hr is None else ", evaluate A %.2f s; B / A = %.3f (accepted: <= 1.05); A and B gave "
+             "equal figures on every pair" % (A, B / A)))
+        say("# scorer: %.1f GB of model rows streamed in %.1f ms of kernel = %.3f TB/s, %.1f %% of the %.0f TB/s HBM peak"
+            % (wb / 1e9, km, wb / km / 1e9, 100.0 * wb / km / 1e6 / HBM_PEAK_GBS, HBM_PEAK_GBS / 1e3))
+        say("# evaluation is %.0f %% of learn + evaluate (B)" % (100.0 * B / (L + B)))
+    say("# whole run: %.1f s" % (time.time() - t_start))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    if prev is not None:
+        prev.free()
+    ev.close()
+    for h in (hr, ht):
+        if h is not None:
+            lib.Py_csr_free(h)
+    mat.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -36,6 +36,16 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class EvalStats(C.Structure):
+    """slimgpu_eval_stats_t (include/slim_gpu_eval.h)."""
+    _fields_ = [("path", C.c_int32), ("device_allocs", C.c_int32), ("h2d_bytes", C.c_int64),
+                ("d2h_bytes", C.c_int64), ("kernel_ms", C.c_double), ("total_ms", C.c_double),
+                ("w_rows_read", C.c_int64), ("w_bytes", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CsrView(C.Structure):
     """slim_csr_t (include/slim_gpu.h): the object behind every handle."""
     _fields_ = ([("nrows", C.c_int32), ("ncols", C.c_int32),
@@ -117,6 +127,18 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# evaluation in HBM (include/slim_gpu_eval.h)
+_EVAL_SIGNATURES = {
+    "SLIMGPU_EvalSetCreate": (C.c_void_p, [C.c_void_p, C.c_void_p, i32_1d, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_int32)]),
+    "SLIMGPU_EvalSetFree": (None, [C.POINTER(C.c_void_p)]),
+    "SLIMGPU_ModelEvaluate": (C.c_int32, [C.c_void_p, C.c_void_p, f64_1d, i32_1d]),
+    "SLIMGPU_MatrixPredict": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, i32_1d, f32_1d]),
+    "SLIMGPU_LastEvalStats": (C.c_int32, [C.POINTER(EvalStats)]),
+}
+
+EVAL_SYMBOLS = tuple(_EVAL_SIGNATURES)
+
 _lib = None
 
 
@@ -130,7 +152,7 @@ def load():
             "slim_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for SLIM training." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

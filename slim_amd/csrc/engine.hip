@@ -59,6 +59,7 @@ struct slimgpu_matrix {
   bool owns_csr = false;
   bool exact_gram = false;  // ratings are not small integers: aTy sums formed in a fixed order
   bool nonpositive = false;  // some rating is <= 0: a co-rating sum can cancel to exactly 0
+  bool merged = false;  // SLIM_GPU_DUPLICATES=sum merged repeated pairs: the rows are no longer the caller's
   // CSR (the caller's of SLIMGPU_MatrixFromDevice unless owns_csr)
   int64_t* d_rowptr = nullptr;
   int32_t* d_rowind = nullptr;
@@ -132,6 +133,10 @@ struct slimgpu_model {
   int device = 0;
   int32_t n = 0;      // nrows = ncols of W
   int64_t nnz = 0;
+  // facts of the row view, found on the device when it is built (k_row_facts): the scorers size
+  // their discovery keys by the longest row and need ids ascending inside every row
+  int32_t max_row = 0;
+  bool rows_sorted = true;
   DeviceBuffer<int64_t> d_colptr, d_rowptr;
   DeviceBuffer<int32_t> d_colind, d_rowind;
   DeviceBuffer<float> d_colval, d_rowval;
@@ -669,6 +674,7 @@ slimgpu_matrix_t* matrix_from_host(int32_t nrows, const ssize_t* rowptr, const i
     m->nrows = nrows;
     m->nnz = rowptr[nrows];
     m->binary = rowval == nullptr;
+    m->merged = !mptr.empty() && rowptr == reinterpret_cast<const ssize_t*>(mptr.data());
     m->ncols = max_index_plus_one(m->nnz, rowind);  // setup.c:117
     if (m->ncols <= 0) m->ncols = 1;
     m->owns_csr = true;
@@ -748,6 +754,7 @@ slimgpu_matrix_t* matrix_clone_to_device(const slimgpu_matrix_t* src, int32_t de
     m->binary = src->binary;
     m->exact_gram = src->exact_gram;
     m->nonpositive = src->nonpositive;
+    m->merged = src->merged;
     m->owns_csr = true;
     m->h_cost = src->h_cost;
     const size_t nz = (size_t)std::max<int64_t>(m->nnz, 1);
@@ -2158,9 +2165,19 @@ std::unique_ptr<slimgpu_model> assemble_resident_model(slimgpu_matrix* m, const 
     HIP_TRY(hipGetLastError());
   }
   *t_columns_done = now_ms();
-  if (row_view)
+  if (row_view) {
     transpose_on_device(m, ncols, tnnz, dm->d_colptr.get(), dm->d_colind.get(), dm->d_colval.get(), dm->d_rowptr,
                         dm->d_rowind, dm->d_rowval);
+    // the longest row and the order inside the rows, for the scorers (8 bytes come down, once per model)
+    int32_t* d_facts = m->ws_misc.reserve(2);
+    int32_t facts[2] = {0, 0};
+    HIP_TRY(hipMemsetAsync(d_facts, 0, sizeof(facts), stream));
+    queue_row_facts(stream, m->num_cus, ncols, dm->d_rowptr.get(), dm->d_rowind.get(), d_facts);
+    HIP_TRY(hipMemcpyAsync(facts, d_facts, sizeof(facts), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    dm->max_row = facts[0];
+    dm->rows_sorted = facts[1] == 0;
+  }
   HIP_TRY(hipStreamSynchronize(stream));
   if (L.carry.get()) {
     dm->d_gsave = std::move(L.carry);
@@ -2378,22 +2395,33 @@ int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out) {
     set_error("resident model: no row view");
     return SLIM_ERROR_INPUT;
   }
-  try {
-    HIP_TRY(hipSetDevice(w->device));
-    std::vector<int64_t> rp((size_t)w->n + 1);
-    HIP_TRY(hipMemcpy(rp.data(), w->d_rowptr.get(), sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
-    out->nrows = out->ncols = w->n;
-    out->nnz = w->nnz;
-    out->max_row = 0;
-    for (int32_t r = 0; r < w->n; ++r) out->max_row = std::max<int64_t>(out->max_row, rp[(size_t)r + 1] - rp[(size_t)r]);
-    out->d_ptr = w->d_rowptr.get();
-    out->d_ind = w->d_rowind.get();
-    out->d_val = w->d_rowval.get();
-    return SLIM_OK;
-  } catch (const HipFail& e) {
-    report(e, "resident model");
-    return status_of(e);
+  out->nrows = out->ncols = w->n;
+  out->nnz = w->nnz;
+  out->max_row = w->max_row;  // recorded when the row view was built: nothing is copied here
+  out->rows_sorted = w->rows_sorted;
+  out->device = w->device;
+  out->d_ptr = w->d_rowptr.get();
+  out->d_ind = w->d_rowind.get();
+  out->d_val = w->d_rowval.get();
+  return SLIM_OK;
+}
+
+int32_t matrix_csr_view(const slimgpu_matrix_t* m, DeviceCsrView* out) {
+  if (!m || !m->d_rowptr || !out) {
+    set_error("staged matrix: no CSR on the device");
+    return SLIM_ERROR_INPUT;
   }
+  out->device = m->device;
+  out->stream = m->stream;
+  out->num_cus = m->num_cus;
+  out->nrows = m->nrows;
+  out->ncols = m->ncols;
+  out->nnz = m->nnz;
+  out->merged = m->merged;
+  out->d_ptr = m->d_rowptr;
+  out->d_ind = m->d_rowind;
+  out->d_val = m->binary ? nullptr : m->d_rowval;
+  return SLIM_OK;
 }
 
 int64_t model_nnz(const slimgpu_model* w) { return w ? w->nnz : -1; }

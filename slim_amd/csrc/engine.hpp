@@ -8,6 +8,8 @@
 
 namespace slimamd {
 
+struct EvalResult;  // host_csr.hpp
+
 // Decoded SLIM_Learn options (reference src/libslim/api.c:42-52 + slim_gpu.h).
 struct LearnOptions {
   int32_t nthreads = 1, nnbrs = 0, simtype = 0, dbglvl = 0, algo = SLIM_ALGO_CD;
@@ -119,6 +121,8 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
 struct DeviceRowView {
   int32_t nrows = 0, ncols = 0;
   int64_t nnz = 0, max_row = 0;  // max_row: entries of the longest row
+  bool rows_sorted = false;      // ids known to ascend inside every row (a resident model records it)
+  int32_t device = -1;           // where the arrays live (-1: the current device)
   const int64_t* d_ptr = nullptr;
   const int32_t* d_ind = nullptr;
   const float* d_val = nullptr;
@@ -126,6 +130,33 @@ struct DeviceRowView {
 int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
                             int32_t* output, float* scores, int32_t* counts);
 int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out);
+// the CSR of a staged matrix where it lies (the history of the resident scorer)
+struct DeviceCsrView {
+  int32_t device = -1, num_cus = 256;
+  void* stream = nullptr;  // hipStream_t of the handle
+  int32_t nrows = 0, ncols = 0;
+  int64_t nnz = 0;
+  bool merged = false;     // SLIM_GPU_DUPLICATES=sum changed the rows: they are not the caller's
+  const int64_t* d_ptr = nullptr;
+  const int32_t* d_ind = nullptr;
+  const float* d_val = nullptr;  // nullptr: binary
+};
+int32_t matrix_csr_view(const slimgpu_matrix_t* m, DeviceCsrView* out);
+
+// topn.hip: a resident model scored and evaluated against the resident matrix (slim_gpu_eval.h:
+// SLIMGPU_EvalSetCreate & co).  Per evaluation only the four sums and three counts come down.
+slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                  int32_t fm_ncols, int32_t nrcmds, int32_t* status);
+void evalset_free(slimgpu_evalset_t* es);
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, EvalResult* out);
+int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
+                       float* scores);
+slimgpu_eval_stats_t& last_eval_stats();
+// facts of a row view, for the scorers: d_facts[0] = entries of its longest row, d_facts[1] = 1 when the
+// ids of some row do not ascend strictly (both preset to 0 by the caller).  Queues one kernel on
+// `stream` (a hipStream_t); throws HipFail when the launch fails.
+void queue_row_facts(void* stream, int num_cus, int32_t nrows, const int64_t* d_ptr, const int32_t* d_ind,
+                     int32_t* d_facts);
 
 // admm.hip: SLIM_Learn(algo = admm), the reference's dense ADMM solver (estimate.c:38-304) with
 // rocBLAS for the panel solves, updates and products and HIP kernels for the rest.
@@ -134,7 +165,6 @@ slim_csr_t* learn_admm(int32_t nrows, const ssize_t* rowptr, const int32_t* rowi
 
 // eval.hip: HR / ARHR of top-N lists against a test matrix on the GPU (the host loop's figures,
 // bit for bit), and the 1-vs-k protocol (every user ranks its own nnegs candidates).
-struct EvalResult;
 int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, const int32_t* counts,
                         const slim_csr_t* tst, const int32_t* fmarker, int32_t fm_ncols,
                         EvalResult* out);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "eval_terms.hpp"
 #include "hip_check.hpp"
 #include "host_csr.hpp"
 
@@ -27,12 +28,6 @@ namespace slimamd {
 namespace {
 
 // ---- HR / ARHR -------------------------------------------------------------------------
-
-struct UserTerms {      // what one user adds to the accumulators of pyapi.c:309-366
-  double hr_all, hr_head, hr_tail;
-  float arhr;
-  int32_t flags;        // 1 valid, 2 has a head test item, 4 has a tail test item
-};
 
 __global__ void k_user_terms(int32_t nusers, int32_t nrcmds, const int32_t* __restrict__ lists,
                              const int32_t* __restrict__ counts,
@@ -229,6 +224,21 @@ int32_t fail(const char* who, const HipFail& e) {
 
 }  // namespace
 
+void launch_user_terms(hipStream_t stream, int num_cus, int32_t nusers, int32_t nrcmds, const int32_t* lists,
+                       const int32_t* counts, const int64_t* tptr, const int32_t* tind, const int32_t* fmarker,
+                       int32_t fm_ncols, UserTerms* terms) {
+  const int blocks = std::max(1, std::min((nusers + 255) / 256, num_cus * 8));
+  hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, stream, nusers, nrcmds, lists, counts, tptr,
+                     tind, fmarker, fm_ncols, terms);
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_sum_in_user_order(hipStream_t stream, int32_t nusers, const UserTerms* terms, float* out_f,
+                              int32_t* out_n) {
+  hipLaunchKernelGGL(k_sum_in_user_order, dim3(1), dim3(64), 0, stream, nusers, terms, out_f, out_n);
+  HIP_TRY(hipGetLastError());
+}
+
 int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, const int32_t* counts,
                         const slim_csr_t* tst, const int32_t* fmarker, int32_t fm_ncols,
                         EvalResult* out) {
@@ -253,12 +263,9 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
     upload(d_tptr, reinterpret_cast<const int64_t*>(tst->rowptr), (size_t)nusers + 1);
     upload(d_tind, tst->rowind, (size_t)tnnz);
     upload(d_fm, fmarker, (size_t)fm_ncols);
-    const int blocks = std::max(1, std::min((nusers + 255) / 256, cu_count() * 8));
-    hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, 0, nusers, nrcmds, d_lists.get(),
-                       d_counts.get(), d_tptr.get(), d_tind.get(), d_fm.get(), fm_ncols, d_terms.get());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sum_in_user_order, dim3(1), dim3(64), 0, 0, nusers, d_terms.get(), d_f.get(), d_n.get());
-    HIP_TRY(hipGetLastError());
+    launch_user_terms(nullptr, cu_count(), nusers, nrcmds, d_lists.get(), d_counts.get(), d_tptr.get(),
+                      d_tind.get(), d_fm.get(), fm_ncols, d_terms.get());
+    launch_sum_in_user_order(nullptr, nusers, d_terms.get(), d_f.get(), d_n.get());
     float f[4];
     int32_t n[3];
     HIP_TRY(hipMemcpy(f, d_f.get(), sizeof(f), hipMemcpyDeviceToHost));

@@ -68,6 +68,15 @@ int main(int argc, char** argv) {
   const char* res_env = std::getenv("SLIM_GPU_RESIDENT");
   const bool resident = !(a.has("ngpus") && a.integer("ngpus", 1) > 1) && !(ng_env && std::atoi(ng_env) > 1) &&
                         !(res_env && std::atoi(res_env) == 0);
+  // resident models are evaluated where they lie: the test rows and the marker go to HBM once, a pair
+  // brings down its figures only (SLIM_GPU_EVAL_RESIDENT=0, or a refusal: lists through the host)
+  const char* evr_env = std::getenv("SLIM_GPU_EVAL_RESIDENT");
+  slimgpu_evalset_t* evalset = nullptr;
+  if (resident && nrcmds >= 1 && nrcmds <= 128 && !(evr_env && std::atoi(evr_env) == 0)) {
+    slim_t* th = to_handle(tst);
+    evalset = SLIMGPU_EvalSetCreate(R, th, fmarker, ncols, nrcmds, &status);
+    Py_csr_free(th);
+  }
   double best_hr = 0, best_ar = 0, bh_l1 = 0, bh_l2 = 0, ba_l1 = 0, ba_l2 = 0;
   while (std::fgets(line, sizeof line, lf)) {
     double l1, l2;
@@ -105,6 +114,14 @@ int main(int argc, char** argv) {
       while (!name.empty() && (name.back() == '\n' || name.back() == '\r')) name.pop_back();
       write_matrix(static_cast<slim_csr_t*>(model), name + ".model", fmt == Fmt::csrnv ? Fmt::csr : fmt);
     }
+    Eval e;
+    double em[4];
+    int32_t env[3];
+    const bool evaluated = evalset && SLIMGPU_ModelEvaluate(evalset, dmodel, em, env) == SLIM_OK;
+    if (evaluated) {
+      e.hr = em[0]; e.hr_head = em[1]; e.hr_tail = em[2]; e.arhr = em[3];
+      e.nvalid = env[0]; e.nvalid_head = env[1]; e.nvalid_tail = env[2];
+    } else {
     std::vector<int32_t> lists((size_t)trn.nrows * nrcmds, -1), lens(trn.nrows, 0);
     std::vector<float> scores((size_t)trn.nrows * nrcmds, 0.0f);
     if (!resident) {
@@ -115,7 +132,8 @@ int main(int argc, char** argv) {
     }
     for (int32_t u = 0; u < trn.nrows; ++u)
       while (lens[u] < nrcmds && lists[(size_t)u * nrcmds + lens[u]] >= 0) ++lens[u];
-    const Eval e = evaluate_lists(tst, lists, lens, nrcmds, fmarker, ncols);
+    e = evaluate_lists(tst, lists, lens, nrcmds, fmarker, ncols);
+    }
     std::printf("l1r: %.2le l2r: %.2le nnz: %7zd hr: %.4f hr_head: %.4f hr_tail: %.4f arhr: %.4f time: %.2lf\n",
                 l1, l2, resident ? (ssize_t)SLIMGPU_ModelNnz(dmodel) : static_cast<slim_csr_t*>(model)->rowptr[static_cast<slim_csr_t*>(model)->nrows], e.hr, e.hr_head, e.hr_tail, e.arhr, st.total_ms / 1e3);
     if (e.hr > best_hr) { best_hr = e.hr; bh_l1 = l1; bh_l2 = l2; }
@@ -127,6 +145,7 @@ int main(int argc, char** argv) {
   std::printf("\nDone.\n------------------------------------------------------------------\n");
   SLIM_FreeModel(&model);
   SLIMGPU_ModelFree(&dmodel);
+  SLIMGPU_EvalSetFree(&evalset);
   std::free(fmarker);
   Py_csr_free(hold);
   SLIMGPU_MatrixFree(&R);

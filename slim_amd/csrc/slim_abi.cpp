@@ -226,6 +226,15 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   const bool resident = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 && nrcmds <= 128 &&
                         !(res_env && std::atoi(res_env) == 0);
   slimgpu_model* dmodel = nullptr;
+  // ... and evaluated where they lie: the test rows and the marker go to HBM once (evalset_create), a
+  // pair brings down its four sums and three counts.  SLIM_GPU_EVAL_RESIDENT=0, or a refusal (a matrix
+  // whose repeated pairs were merged), keeps the lists-through-the-host path below.
+  const char* evr_env = std::getenv("SLIM_GPU_EVAL_RESIDENT");
+  slimgpu_evalset_t* evalset = nullptr;
+  if (resident && !(evr_env && std::atoi(evr_env) == 0)) {
+    evalset = evalset_create(mat, tst, fmarker, ncols, nrcmds, &status);
+    if (!evalset) set_error("");
+  }
   int32_t rc = SLIM_OK;
   for (int32_t a = 0; a < nl1 && rc == SLIM_OK; ++a) {
     for (int32_t b = 0; b < nl2; ++b) {
@@ -236,9 +245,15 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
       opt.l2r = arrayl2[b];
       slim_csr_t* prev = model;  // warm start from the previous cell
       // top-N of every user on the GPU (bit-identical to the host scorer), hits on the host
-      std::vector<int32_t> lists((size_t)trn->nrows * nrcmds, -1), lens((size_t)trn->nrows, 0);
-      std::vector<float> lsc((size_t)trn->nrows * nrcmds, 0.0f);
-      bool on_gpu = false;
+      std::vector<int32_t> lists, lens;
+      std::vector<float> lsc;
+      auto host_lists = [&] {  // (not needed while the eval set serves)
+        lists.assign((size_t)trn->nrows * nrcmds, -1);
+        lens.assign((size_t)trn->nrows, 0);
+        lsc.assign((size_t)trn->nrows * nrcmds, 0.0f);
+      };
+      bool on_gpu = false, evaluated = false;
+      EvalResult ev;
       ssize_t model_nnz_now = 0;
       if (resident) {
         slimgpu_model* dprev = dmodel;
@@ -249,10 +264,14 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
           break;
         }
         model_nnz_now = (ssize_t)model_nnz(dmodel);
+        evaluated = evalset && model_evaluate(evalset, dmodel, &ev) == SLIM_OK;
         DeviceRowView wv;
-        on_gpu = model_row_view(dmodel, &wv) == SLIM_OK &&
-                 predict_device_view(wv, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK;
-        if (!on_gpu) {  // (the scorer refused: the host loop needs the host model)
+        if (!evaluated) {
+          host_lists();
+          on_gpu = model_row_view(dmodel, &wv) == SLIM_OK &&
+                   predict_device_view(wv, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK;
+        }
+        if (!evaluated && !on_gpu) {  // (the scorer refused: the host loop needs the host model)
           model = model_fetch(dmodel, &status);
           if (!model) {
             rc = status;
@@ -269,13 +288,15 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
         break;
       }
       model_nnz_now = model->rowptr[model->nrows];
+      host_lists();
       on_gpu = nrcmds <= 128 && predict_device(model, trn, nrcmds, lists.data(),
                                                lsc.data(), lens.data()) == SLIM_OK;
       }
-      EvalResult ev;
-      if (!on_gpu)
+      if (evaluated) {
+        // the figures came from the device: no lists, no host loop
+      } else if (!on_gpu) {
         ev = evaluate(model, trn, tst, nrcmds, fmarker, ncols);
-      else if (evaluate_device(std::min(trn->nrows, tst->nrows), nrcmds, lists.data(), lens.data(),
+      } else if (evaluate_device(std::min(trn->nrows, tst->nrows), nrcmds, lists.data(), lens.data(),
                                tst, fmarker, ncols, &ev) != SLIM_OK) {  // hit counting on the GPU
         if (resident && !model) model = model_fetch(dmodel, &status);  // (the host loop sizes by the model)
         if (!model) {
@@ -315,6 +336,7 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   std::printf("\nDone.\n------------------------------------------------------------------\n");
   csr_free(model);
   model_free(dmodel);
+  evalset_free(evalset);
   std::free(fmarker);
   matrix_free(mat);
   return rc;
@@ -524,6 +546,45 @@ int32_t SLIMGPU_ModelPredict(int32_t nrcmds, const slimgpu_model_t* model, slim_
   const int32_t rc = model_row_view(model, &v);
   if (rc != SLIM_OK) return rc;
   return predict_device_view(v, as_csr(trnhandle), nrcmds, output, scores, nullptr);
+}
+
+slimgpu_evalset_t* SLIMGPU_EvalSetCreate(slimgpu_matrix_t* mat, slim_t* tsthandle, const int32_t* fmarker,
+                                         int32_t fm_ncols, int32_t nrcmds, int32_t* r_status) {
+  set_error("");
+  int32_t status = SLIM_ERROR;
+  slimgpu_evalset_t* es = evalset_create(mat, as_csr(tsthandle), fmarker, fm_ncols, nrcmds, &status);
+  if (r_status) *r_status = status;
+  return es;
+}
+
+void SLIMGPU_EvalSetFree(slimgpu_evalset_t** es) {
+  if (!es || !*es) return;
+  evalset_free(*es);
+  *es = nullptr;
+}
+
+int32_t SLIMGPU_ModelEvaluate(slimgpu_evalset_t* es, const slimgpu_model_t* model, double* metrics,
+                              int32_t* nvalid) {
+  set_error("");
+  if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
+  EvalResult ev;
+  const int32_t rc = model_evaluate(es, model, &ev);
+  if (rc != SLIM_OK) return rc;
+  metrics[0] = ev.hr; metrics[1] = ev.hr_head; metrics[2] = ev.hr_tail; metrics[3] = ev.arhr;
+  nvalid[0] = ev.nvalid; nvalid[1] = ev.nvalid_head; nvalid[2] = ev.nvalid_tail;
+  return SLIM_OK;
+}
+
+int32_t SLIMGPU_MatrixPredict(int32_t nrcmds, const slimgpu_model_t* model, slimgpu_matrix_t* mat,
+                              int32_t* output, float* scores) {
+  set_error("");
+  return matrix_predict(nrcmds, model, mat, output, scores);
+}
+
+int32_t SLIMGPU_LastEvalStats(slimgpu_eval_stats_t* out) {
+  if (!out) return SLIM_ERROR_INPUT;
+  *out = last_eval_stats();
+  return SLIM_OK;
 }
 
 slim_t* SLIMGPU_LearnColumns(slimgpu_matrix_t* mat, int32_t ncolumns, const int32_t* columns,

@@ -30,8 +30,49 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "eval_terms.hpp"
 #include "hip_check.hpp"
 #include "host_csr.hpp"
+
+namespace slimamd {
+
+// Device buffers of the scorers, grow-only: a second run of the same shape allocates nothing.
+struct ScorerWorkspace {
+  DeviceBuffer<uint32_t> split;            // chunk kernel: where every chunk starts in every model row
+  DeviceBuffer<int32_t> queue, oid, ocnt;  // work queue; lists and their lengths (when they are wanted)
+  DeviceBuffer<float> osc, score;          // list scores; wave kernel: score vectors
+  DeviceBuffer<unsigned long long> disc;   // wave kernel: discovery vectors
+  int allocs = 0;                          // device allocations since the caller last cleared it
+  template <class T>
+  T* need(DeviceBuffer<T>& b, size_t n) {
+    if (b.bytes() < sizeof(T) * (n ? n : 1)) ++allocs;
+    return b.reserve(n);
+  }
+};
+
+}  // namespace slimamd
+
+// What an evaluation needs besides the model (slim_gpu_eval.h: SLIMGPU_EvalSetCreate).  Owns its buffers;
+// borrows the matrix.
+struct slimgpu_evalset {
+  slimgpu_matrix_t* mat = nullptr;
+  int device = 0;
+  int32_t nusers = 0, nrcmds = 0, fm_ncols = 0;
+  int64_t hist_begin = 0;    // offset of user 0's history in the matrix's CSR
+  int64_t hist_entries = 0;  // history entries of users [0, nusers): the model rows one evaluation streams
+  int64_t max_hist = 0;      // the longest of those histories
+  slimamd::DeviceBuffer<int64_t> d_tptr;
+  slimamd::DeviceBuffer<int32_t> d_tind, d_fm;
+  slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;
+  slimamd::DeviceBuffer<unsigned long long> d_out;  // EvalOut
+  slimamd::ScorerWorkspace ws;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~slimgpu_evalset() {
+    (void)hipSetDevice(device);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+};
 
 namespace slimamd {
 
@@ -226,6 +267,12 @@ struct TopN2Args {
   float* out_scores;
   int32_t* out_cnt;
   int32_t* queue;
+  // fused evaluation (EVAL instantiations only): the test rows, the head / tail marker, one record per user
+  const int64_t* tptr = nullptr;
+  const int32_t* tind = nullptr;
+  const int32_t* fmarker = nullptr;
+  int32_t fm_ncols = 0;
+  UserTerms* terms = nullptr;
 };
 
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
@@ -286,8 +333,14 @@ __global__ void k_row_split(int32_t nrows, int32_t nchunks, int32_t cw,
 // KeyT: discovery key (history index << pos_bits | position in the model row).  32 bits when
 // the longest history and the longest model row allow it (8 bytes of LDS per item: chunks of
 // 2304 ids), else 64.
-template <int NW, typename KeyT>
-__global__ __launch_bounds__(64 * NW) void topn_chunk_kernel(const TopN2Args T) {
+// EVAL: the fused epilogue of the resident evaluation.  Once wavefront 0 has merged the lists, lane t
+// holds rank t; the user's test row sits in LDS (loaded by the whole workgroup into wavefront 0's score
+// chunk, which is free by then; what does not fit is walked from HBM), every lane tests its id against
+// it, one ballot gives the hit mask, and the user's UserTerms record is formed exactly as k_user_terms
+// (eval.hip) forms it -- gain added in rank order, ideal in test-row order, float accumulators fed with
+// double terms.  Lists are written only when an output pointer is given.
+template <int NW, typename KeyT, bool EVAL>
+__device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
   constexpr KeyT kUnt = ~KeyT(0), kExc = ~KeyT(0) - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int D = kT2Depth;
@@ -459,6 +512,16 @@ __global__ __launch_bounds__(64 * NW) void topn_chunk_kernel(const TopN2Args T) 
     }
     if (lane == 0) m_cnt[wave] = count;
     __syncthreads();
+    int64_t t0 = 0, t1 = 0;
+    int tl = 0;
+    // (every wavefront is past its chunks: wavefront 0's score chunk is free until the next user)
+    int* s_test = reinterpret_cast<int*>(smem + (size_t)NW * CW * sizeof(KeyT));
+    if constexpr (EVAL) {
+      t0 = uni64(T.tptr[u]);
+      t1 = uni64(T.tptr[u + 1]);
+      tl = (t1 - t0) < (int64_t)CW ? (int)(t1 - t0) : CW;
+      for (int z = tid; z < tl; z += 64 * NW) s_test[z] = T.tind[t0 + z];
+    }
     if (wave == 0) {
       for (int w = 1; w < NW; ++w) {
         const int cw_ = __builtin_amdgcn_readfirstlane(m_cnt[w]);
@@ -469,15 +532,139 @@ __global__ __launch_bounds__(64 * NW) void topn_chunk_kernel(const TopN2Args T) 
           offer(cs, cd, cid);
         }
       }
-      if (lane < count) {
-        T.out_ids[(int64_t)u * N + lane] = lid;
-        T.out_scores[(int64_t)u * N + lane] = ls;
+      if (!EVAL || T.out_ids != nullptr) {
+        if (lane < count) {
+          T.out_ids[(int64_t)u * N + lane] = lid;
+          T.out_scores[(int64_t)u * N + lane] = ls;
+        }
+        if (lane == 0) T.out_cnt[u] = count;
       }
-      if (lane == 0) T.out_cnt[u] = count;
+    }
+    if constexpr (EVAL) {
+      __syncthreads();  // the test row is in LDS
+      if (wave == 0) {
+        UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
+        const int64_t tlen = t1 - t0;
+        if (tlen >= 1) {
+          int ntrue0 = 0, ntrue1 = 0, flags = 1;
+          float ideal = 0.0f;
+          bool hit = false;
+          for (int64_t z = 0; z < tlen; ++z) {
+            const int it = z < tl ? s_test[z] : T.tind[t0 + z];
+            const int cls = (it >= 0 && it < T.fm_ncols) ? T.fmarker[it] : 1;
+            if (cls) ++ntrue1; else ++ntrue0;
+            flags |= cls ? 4 : 2;
+            ideal = (float)((double)ideal + 1.0 / (1.0 + double(z)));
+            hit = hit || it == lid;
+          }
+          unsigned long long mask = __ballot(hit && lane < count);
+          int nh0 = 0, nh1 = 0, nh2 = 0;
+          float gain = 0.0f;
+          while (mask) {  // set bits = ranks that hit, walked in rank order
+            const int r = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int id = __builtin_amdgcn_readlane(lid, r);
+            const int cls = (id >= 0 && id < T.fm_ncols) ? T.fmarker[id] : 1;
+            if (cls) ++nh1; else ++nh0;
+            ++nh2;
+            gain = (float)((double)gain + 1.0 / (1.0 + r));
+          }
+          t.hr_head = nh0 > 0 ? 1.0 * nh0 / ntrue0 : 0.0;
+          t.hr_tail = nh1 > 0 ? 1.0 * nh1 / ntrue1 : 0.0;
+          t.hr_all = 1.0 * nh2 / double(tlen);
+          t.arhr = gain / ideal;
+          t.flags = flags;
+        }
+        if (lane == 0) T.terms[u] = t;
+      }
     }
     __syncthreads();
   }
 }
+
+template <int NW, typename KeyT>
+__global__ __launch_bounds__(64 * NW) void topn_chunk_kernel(const TopN2Args T) {
+  topn_chunk_body<NW, KeyT, false>(T);
+}
+template <int NW, typename KeyT>
+__global__ __launch_bounds__(64 * NW) void topn_chunk_eval_kernel(const TopN2Args T) {
+  topn_chunk_body<NW, KeyT, true>(T);
+}
+
+// facts[0] = entries of the longest row, facts[1] = 1 when some row's ids are not strictly ascending
+// (both preset to 0)
+__global__ void k_row_facts(int32_t nrows, const int64_t* __restrict__ ptr, const int32_t* __restrict__ ind,
+                            int32_t* __restrict__ facts) {
+  int32_t mx = 0;
+  bool bad = false;
+  for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) {
+    const int64_t s = ptr[r], e = ptr[r + 1];
+    mx = max(mx, (int32_t)(e - s));
+    for (int64_t j = s + 1; j < e; ++j) bad |= ind[j - 1] >= ind[j];
+  }
+  for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
+  if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(facts, mx);
+  if (bad) atomicExch(facts + 1, 1);
+}
+
+// entries of the longest row of a CSR (out preset to 0)
+__global__ void k_longest_row(int32_t nrows, const int64_t* __restrict__ ptr, int32_t* __restrict__ out) {
+  int32_t mx = 0;
+  for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x)
+    mx = max(mx, (int32_t)(ptr[r + 1] - ptr[r]));
+  for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
+  if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(out, mx);
+}
+
+// the scorer's byte model: entries of the model rows that the histories of users [0, nusers) stream
+// (out preset to 0)
+__global__ void k_streamed_entries(int64_t h0, int64_t h1, const int32_t* __restrict__ hind, int32_t wrows,
+                                   const int64_t* __restrict__ wptr, unsigned long long* __restrict__ out) {
+  unsigned long long sum = 0;
+  for (int64_t h = h0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < h1; h += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t i = hind[h];
+    if (i >= 0 && i < wrows) sum += (unsigned long long)(wptr[i + 1] - wptr[i]);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)sum, off), hi = __shfl_xor((uint32_t)(sum >> 32), off);
+    sum += ((unsigned long long)hi << 32) | lo;
+  }
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(out, sum);
+}
+
+// Geometry of the chunk kernel for a model / history pair: key width, chunk width, LDS.
+struct ChunkPlan {
+  bool key32 = false;
+  int pos_bits = 32, item_bytes = 12, t2w = kT2Waves, cw = 64, nchunks = 1;
+  size_t lds = 0;
+};
+// force_key64: the worst case of a model not seen yet (the smallest chunks, hence the largest split table)
+ChunkPlan plan_chunks(int32_t ncols, int64_t max_row, int64_t max_hist, bool force_key64) {
+  ChunkPlan P;
+  if (const char* e = std::getenv("SLIM_TOPN_WAVES")) P.t2w = std::atoi(e) == 16 ? 16 : 8;
+  const int t2w = P.t2w;
+  // discovery keys: 32 bits when (longest history, longest model row) fit, else 64
+  auto bits_for = [](int64_t v) { int b = 0; while ((int64_t(1) << b) <= v) ++b; return b; };
+  P.key32 = !force_key64 && bits_for(max_row) + bits_for(max_hist) <= 31;
+  if (const char* e = std::getenv("SLIM_TOPN_KEY")) P.key32 = P.key32 && std::atoi(e) != 64;
+  P.pos_bits = P.key32 ? bits_for(max_row) : 32;
+  P.item_bytes = P.key32 ? 8 : 12;
+  // chunk width: round 1's footprint (1536 ids x 12 bytes x 8 wavefronts), less whatever the
+  // merge area of this geometry needs beyond it, so that chunks + lists always fit the 160 KB
+  const size_t merge_bytes = (size_t)t2w * kT2MaxN * 16 + (size_t)t2w * sizeof(int) + 256;
+  const size_t chunk_bytes = std::min<size_t>((size_t)kT2MaxCW * 12 * kT2Waves,
+                                              (size_t)160 * 1024 - merge_bytes);
+  const int max_cw = (int)(chunk_bytes / ((size_t)P.item_bytes * t2w)) / 64 * 64;
+  P.cw = std::max(64, std::min(max_cw, ((ncols + t2w - 1) / t2w + 63) / 64 * 64));
+  if (const char* e = std::getenv("SLIM_TOPN_CW")) {
+    const int v = std::atoi(e);
+    if (v >= 64 && v <= max_cw && v % 64 == 0) P.cw = v;
+  }
+  P.nchunks = (ncols + P.cw - 1) / P.cw;
+  P.lds = (size_t)t2w * P.cw * P.item_bytes + (size_t)t2w * kT2MaxN * 16 + t2w * sizeof(int);
+  return P;
+}
+constexpr size_t kSplitLimit = size_t(2) << 30;  // bytes of split table beyond which the wave kernel serves
 
 }  // namespace
 
@@ -529,7 +716,7 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
                    !(kenv && std::strcmp(kenv, "wave") == 0);
     if (chunked) {
       int32_t unsorted = 0;
-      if (wnnz > 0) {
+      if (wnnz > 0 && !W.rows_sorted) {
         hipLaunchKernelGGL(k_rows_sorted, dim3(std::max(1, std::min(W.nrows / 4 + 1, prop.multiProcessorCount * 8))),
                            dim3(256), 0, 0, W.nrows, d_wptr, d_wind, d_queue.get() + 1);
         HIP_TRY(hipGetLastError());
@@ -537,30 +724,12 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
       }
       if (unsorted) chunked = false;
     }
-    int t2w = kT2Waves;
-    if (const char* e = std::getenv("SLIM_TOPN_WAVES")) t2w = std::atoi(e) == 16 ? 16 : 8;
-    // discovery keys: 32 bits when (longest history, longest model row) fit, else 64
-    int64_t max_hist = 0, max_row = 0;
+    int64_t max_hist = 0;
     for (int32_t u = 0; u < nusers; ++u) max_hist = std::max<int64_t>(max_hist, hist->rowptr[u + 1] - hist->rowptr[u]);
-    max_row = W.max_row;
-    auto bits_for = [](int64_t v) { int b = 0; while ((int64_t(1) << b) <= v) ++b; return b; };
-    bool key32 = bits_for(max_row) + bits_for(max_hist) <= 31;
-    if (const char* e = std::getenv("SLIM_TOPN_KEY")) key32 = key32 && std::atoi(e) != 64;
-    const int pos_bits = key32 ? bits_for(max_row) : 32;
-    const int item_bytes = key32 ? 8 : 12;
-    // chunk width: round 1's footprint (1536 ids x 12 bytes x 8 wavefronts), less whatever the
-    // merge area of this geometry needs beyond it, so that chunks + lists always fit the 160 KB
-    const size_t merge_bytes = (size_t)t2w * kT2MaxN * 16 + (size_t)t2w * sizeof(int) + 256;
-    const size_t chunk_bytes = std::min<size_t>((size_t)kT2MaxCW * 12 * kT2Waves,
-                                                (size_t)160 * 1024 - merge_bytes);
-    const int max_cw = (int)(chunk_bytes / ((size_t)item_bytes * t2w)) / 64 * 64;
-    int cw = std::max(64, std::min(max_cw, ((ncols + t2w - 1) / t2w + 63) / 64 * 64));
-    if (const char* e = std::getenv("SLIM_TOPN_CW")) {
-      const int v = std::atoi(e);
-      if (v >= 64 && v <= max_cw && v % 64 == 0) cw = v;
-    }
-    const int nchunks = (ncols + cw - 1) / cw;
-    if (chunked && (size_t)W.nrows * ((size_t)nchunks + 1) * sizeof(uint32_t) > (size_t(2) << 30))
+    const ChunkPlan P = plan_chunks(ncols, W.max_row, max_hist, false);
+    const int t2w = P.t2w, pos_bits = P.pos_bits, cw = P.cw, nchunks = P.nchunks;
+    const bool key32 = P.key32;
+    if (chunked && (size_t)W.nrows * ((size_t)nchunks + 1) * sizeof(uint32_t) > kSplitLimit)
       chunked = false;
     if (kenv && std::strcmp(kenv, "chunk") == 0 && !chunked) {
       set_error("SLIMGPU_Predict: SLIM_TOPN_KERNEL=chunk needs nrcmds <= 64 and model rows sorted by id");
@@ -575,7 +744,7 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
                            dim3(256), 0, 0, W.nrows, nchunks, cw, d_wptr, d_wind, d_split.get());
         HIP_TRY(hipGetLastError());
       }
-      TopN2Args T;
+      TopN2Args T{};
       T.nusers = nusers;
       T.nitems_rows = W.nrows;
       T.ncols = ncols;
@@ -587,7 +756,7 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
       T.wptr = d_wptr; T.wind = d_wind; T.wval = d_wval; T.wsplit = d_split.get();
       T.hptr = d_hptr.get(); T.hind = d_hind.get(); T.hval = hist->rowval ? d_hval.get() : nullptr;
       T.out_ids = d_oid.get(); T.out_scores = d_oscore.get(); T.out_cnt = d_ocnt.get(); T.queue = d_queue.get();
-      const size_t lds = (size_t)t2w * cw * item_bytes + (size_t)t2w * kT2MaxN * 16 + t2w * sizeof(int);
+      const size_t lds = P.lds;
       auto kfn = key32 ? (t2w == 16 ? topn_chunk_kernel<16, uint32_t> : topn_chunk_kernel<8, uint32_t>)
                        : (t2w == 16 ? topn_chunk_kernel<16, unsigned long long>
                                     : topn_chunk_kernel<8, unsigned long long>);
@@ -686,6 +855,400 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
     set_error(std::string("SLIMGPU_Predict: HIP error '") + hipGetErrorString(e.code) + "' in " + e.where);
     return status_of(e);
   }
+}
+
+// ---- a resident model against the resident matrix ----------------------------------------------
+//
+// The evaluate half of a model-selection cell without the host: the history is the staged matrix's CSR
+// where it lies, the model is a resident model's row view, the test rows and the head / tail marker
+// were staged once (slimgpu_evalset).  One fused kernel scores, selects and forms every user's terms;
+// k_sum_in_user_order adds them; 40 bytes come down.
+namespace {
+
+thread_local slimgpu_eval_stats_t g_eval_stats;
+
+struct EvalOut {  // what one evaluation brings down
+  float f[4];
+  int32_t n[3];
+  int32_t pad;
+  unsigned long long streamed;  // entries of the model rows streamed
+};
+
+struct HistoryView {
+  int32_t nusers = 0;
+  const int64_t* ptr = nullptr;
+  const int32_t* ind = nullptr;
+  const float* val = nullptr;
+  int64_t max_hist = 0;
+};
+struct EvalTargets {  // the fused epilogue's inputs and output
+  const int64_t* tptr;
+  const int32_t* tind;
+  const int32_t* fmarker;
+  int32_t fm_ncols;
+  UserTerms* terms;
+};
+
+int wave_kernel_waves(int32_t nusers, int32_t nrcmds, int num_cus, size_t* lds_out) {
+  const size_t lds = (size_t)nrcmds * 64 * (sizeof(float) + sizeof(unsigned long long) + sizeof(int));
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (128 * 1024) / lds));
+  if (lds_out) *lds_out = lds;
+  return std::max(1, std::min<int>(nusers, num_cus * per_cu));
+}
+
+// which kernel serves: 1 the chunk kernel, 2 the wave kernel (lists of more than 64, a split table
+// beyond 2 GB, model rows not sorted, SLIM_TOPN_KERNEL=wave)
+int scorer_path(const DeviceRowView& W, int32_t nrcmds, const ChunkPlan& P) {
+  const char* kenv = std::getenv("SLIM_TOPN_KERNEL");
+  const bool chunked = nrcmds <= kT2MaxN && W.nnz < (int64_t(1) << 31) && (W.rows_sorted || W.nnz == 0) &&
+                       !(kenv && std::strcmp(kenv, "wave") == 0) &&
+                       (size_t)std::max(W.nrows, 1) * ((size_t)P.nchunks + 1) * sizeof(uint32_t) <= kSplitLimit;
+  return chunked ? 1 : 2;
+}
+
+void reserve_scorer(ScorerWorkspace& ws, int path, int32_t wrows, int32_t ncols, const ChunkPlan& P, int32_t nusers,
+                    int32_t nrcmds, int num_cus, bool lists) {
+  ws.need(ws.queue, 2);
+  if (path == 1) {
+    ws.need(ws.split, (size_t)std::max(wrows, 1) * ((size_t)P.nchunks + 1));
+  } else {
+    const int nwaves = wave_kernel_waves(nusers, nrcmds, num_cus, nullptr);
+    ws.need(ws.score, (size_t)nwaves * ncols);
+    ws.need(ws.disc, (size_t)nwaves * ncols);
+  }
+  if (lists || path == 2) {
+    ws.need(ws.oid, (size_t)nusers * nrcmds);
+    ws.need(ws.osc, (size_t)nusers * nrcmds);
+    ws.need(ws.ocnt, (size_t)nusers);
+  }
+}
+
+// Queues the scorer on `stream`: lists into ws.oid / osc / ocnt when `lists` (always on path 2), the
+// users' terms into ev->terms when ev is given.  Returns the path taken.
+int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, int num_cus, hipStream_t stream,
+                 ScorerWorkspace& ws, const EvalTargets* ev, bool lists) {
+  const int32_t ncols = std::max(W.ncols, 1);
+  const ChunkPlan P = plan_chunks(ncols, W.max_row, H.max_hist, false);
+  const int path = scorer_path(W, nrcmds, P);
+  reserve_scorer(ws, path, W.nrows, ncols, P, H.nusers, nrcmds, num_cus, lists);
+  HIP_TRY(hipMemsetAsync(ws.queue.get(), 0, 2 * sizeof(int32_t), stream));
+  if (lists || path == 2) HIP_TRY(hipMemsetAsync(ws.ocnt.get(), 0, sizeof(int32_t) * (size_t)H.nusers, stream));
+  if (path == 1) {
+    if (W.nrows > 0) {
+      const int64_t total = (int64_t)W.nrows * (P.nchunks + 1);
+      hipLaunchKernelGGL(k_row_split, dim3((unsigned)std::min<int64_t>((total + 255) / 256, num_cus * 16)), dim3(256),
+                         0, stream, W.nrows, P.nchunks, P.cw, W.d_ptr, W.d_ind, ws.split.get());
+      HIP_TRY(hipGetLastError());
+    }
+    TopN2Args T{};
+    T.nusers = H.nusers;
+    T.nitems_rows = W.nrows;
+    T.ncols = ncols;
+    T.nrcmds = nrcmds;
+    T.cw = P.cw;
+    T.nchunks = P.nchunks;
+    T.pos_bits = P.pos_bits;
+    T.wlast = W.nnz > 0 ? (uint32_t)(W.nnz - 1) : 0u;
+    T.wptr = W.d_ptr; T.wind = W.d_ind; T.wval = W.d_val; T.wsplit = ws.split.get();
+    T.hptr = H.ptr; T.hind = H.ind; T.hval = H.val;
+    T.out_ids = lists ? ws.oid.get() : nullptr;
+    T.out_scores = lists ? ws.osc.get() : nullptr;
+    T.out_cnt = lists ? ws.ocnt.get() : nullptr;
+    T.queue = ws.queue.get();
+    if (ev) {
+      T.tptr = ev->tptr; T.tind = ev->tind; T.fmarker = ev->fmarker; T.fm_ncols = ev->fm_ncols; T.terms = ev->terms;
+    }
+    const bool w16 = P.t2w == 16;
+    auto kfn = ev ? (P.key32 ? (w16 ? topn_chunk_eval_kernel<16, uint32_t> : topn_chunk_eval_kernel<8, uint32_t>)
+                             : (w16 ? topn_chunk_eval_kernel<16, unsigned long long>
+                                    : topn_chunk_eval_kernel<8, unsigned long long>))
+                  : (P.key32 ? (w16 ? topn_chunk_kernel<16, uint32_t> : topn_chunk_kernel<8, uint32_t>)
+                             : (w16 ? topn_chunk_kernel<16, unsigned long long>
+                                    : topn_chunk_kernel<8, unsigned long long>));
+    if (P.lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)P.lds));
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / P.t2w, (160 * 1024) / (P.lds + 64)));
+    const int nwg = std::max(1, std::min<int>(H.nusers, num_cus * per_cu));
+    hipLaunchKernelGGL(kfn, dim3(nwg), dim3(64 * P.t2w), P.lds, stream, T);
+    HIP_TRY(hipGetLastError());
+  } else {
+    size_t lds = 0;
+    const int nwaves = wave_kernel_waves(H.nusers, nrcmds, num_cus, &lds);
+    TopNArgs T;
+    T.nusers = H.nusers;
+    T.nitems_rows = W.nrows;
+    T.ncols = ncols;
+    T.nrcmds = nrcmds;
+    T.wptr = W.d_ptr; T.wind = W.d_ind; T.wval = W.d_val;
+    T.hptr = H.ptr; T.hind = H.ind; T.hval = H.val;
+    T.score = ws.score.get(); T.disc = ws.disc.get();
+    T.out_ids = ws.oid.get(); T.out_scores = ws.osc.get(); T.out_cnt = ws.ocnt.get(); T.queue = ws.queue.get();
+    if (lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(topn_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(topn_kernel, dim3(nwaves), dim3(64), lds, stream, T);
+    HIP_TRY(hipGetLastError());
+    if (ev)
+      launch_user_terms(stream, num_cus, H.nusers, nrcmds, ws.oid.get(), ws.ocnt.get(), ev->tptr, ev->tind,
+                        ev->fmarker, ev->fm_ncols, ev->terms);
+  }
+  return path;
+}
+
+double ms_since(const std::chrono::steady_clock::time_point& t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+int32_t hip_failure(const char* who, const HipFail& e) {
+  set_error(std::string(who) + ": HIP error '" + hipGetErrorString(e.code) + "' in " + e.where);
+  return status_of(e);
+}
+
+// the matrix and the model of one call: one device, one width, rows that are the caller's
+int32_t check_pair(const char* who, const DeviceCsrView& R, const DeviceRowView& W) {
+  if (R.merged) {
+    set_error(std::string(who) + ": the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were "
+              "merged: its rows are not the caller's, score through the host handle");
+    return SLIM_ERROR_INPUT;
+  }
+  if (W.device != R.device) {
+    set_error(std::string(who) + ": the model and the matrix live on different devices");
+    return SLIM_ERROR_INPUT;
+  }
+  if (W.nrows != R.ncols) {
+    set_error(std::string(who) + ": the model has " + std::to_string(W.nrows) + " items, the matrix " +
+              std::to_string(R.ncols));
+    return SLIM_ERROR_INPUT;
+  }
+  return SLIM_OK;
+}
+
+}  // namespace
+
+slimgpu_eval_stats_t& last_eval_stats() { return g_eval_stats; }
+
+void queue_row_facts(void* stream, int num_cus, int32_t nrows, const int64_t* d_ptr, const int32_t* d_ind,
+                     int32_t* d_facts) {
+  hipLaunchKernelGGL(k_row_facts, dim3(std::max(1, std::min((nrows + 255) / 256, num_cus * 8))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), nrows, d_ptr, d_ind, d_facts);
+  HIP_TRY(hipGetLastError());
+}
+
+slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                  int32_t fm_ncols, int32_t nrcmds, int32_t* status) {
+  auto fail = [&](int32_t st) {
+    if (status) *status = st;
+    return static_cast<slimgpu_evalset_t*>(nullptr);
+  };
+  DeviceCsrView R;
+  if (!mat || !tst || !tst->rowptr || !fmarker || fm_ncols < 0 || nrcmds < 1 || nrcmds > 128 ||
+      matrix_csr_view(mat, &R) != SLIM_OK) {
+    set_error("SLIMGPU_EvalSetCreate: bad arguments (a staged matrix, a test handle, a marker, 1 <= nrcmds <= 128)");
+    return fail(SLIM_ERROR_INPUT);
+  }
+  if (R.merged) {
+    set_error("SLIMGPU_EvalSetCreate: the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were "
+              "merged: its rows are not the caller's, evaluate through the host handle");
+    return fail(SLIM_ERROR_INPUT);
+  }
+  slimgpu_evalset* es = nullptr;
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    es = new slimgpu_evalset();
+    es->mat = mat;
+    es->device = R.device;
+    es->nusers = std::min(R.nrows, tst->nrows);  // pyapi.c:309
+    es->nrcmds = nrcmds;
+    es->fm_ncols = fm_ncols;
+    const int32_t nu = es->nusers;
+    const int64_t tnnz = tst->rowptr[nu];
+    es->d_tptr = DeviceBuffer<int64_t>((size_t)nu + 1);
+    es->d_tind = DeviceBuffer<int32_t>((size_t)tnnz);
+    es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
+    es->d_terms = DeviceBuffer<UserTerms>((size_t)nu);
+    es->d_out = DeviceBuffer<unsigned long long>(sizeof(EvalOut) / sizeof(unsigned long long));
+    static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
+    HIP_TRY(hipMemcpyAsync(es->d_tptr.get(), tst->rowptr, sizeof(int64_t) * ((size_t)nu + 1), hipMemcpyHostToDevice, stream));
+    if (tnnz > 0)
+      HIP_TRY(hipMemcpyAsync(es->d_tind.get(), tst->rowind, sizeof(int32_t) * (size_t)tnnz, hipMemcpyHostToDevice, stream));
+    if (fm_ncols > 0)
+      HIP_TRY(hipMemcpyAsync(es->d_fm.get(), fmarker, sizeof(int32_t) * (size_t)fm_ncols, hipMemcpyHostToDevice, stream));
+    // the longest history and the number of history entries, once (the scorer's key width needs the first)
+    int32_t* d_max = reinterpret_cast<int32_t*>(es->d_out.get());
+    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), stream));
+    if (nu > 0) {
+      hipLaunchKernelGGL(k_longest_row, dim3(std::max(1, std::min((nu + 255) / 256, R.num_cus * 8))), dim3(256), 0,
+                         stream, nu, R.d_ptr, d_max);
+      HIP_TRY(hipGetLastError());
+    }
+    int32_t h_max = 0;
+    int64_t h_ends[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&h_max, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_ends[0], R.d_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_ends[1], R.d_ptr + nu, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    es->max_hist = h_max;
+    es->hist_begin = h_ends[0];
+    es->hist_entries = h_ends[1] - h_ends[0];
+    // workspaces for the worst model: 64-bit keys, hence the smallest chunks and the largest split table
+    DeviceRowView worst;
+    worst.nrows = worst.ncols = R.ncols;
+    worst.rows_sorted = true;
+    const ChunkPlan P = plan_chunks(std::max(R.ncols, 1), 0, es->max_hist, /*force_key64=*/true);
+    reserve_scorer(es->ws, scorer_path(worst, nrcmds, P), R.ncols, std::max(R.ncols, 1), P, nu, nrcmds, R.num_cus,
+                   /*lists=*/false);
+    HIP_TRY(hipEventCreate(&es->ev0));
+    HIP_TRY(hipEventCreate(&es->ev1));
+    if (status) *status = SLIM_OK;
+    return es;
+  } catch (const HipFail& e) {
+    delete es;
+    return fail(hip_failure("SLIMGPU_EvalSetCreate", e));
+  } catch (const std::bad_alloc&) {
+    delete es;
+    set_error("SLIMGPU_EvalSetCreate: out of host memory");
+    return fail(SLIM_ERROR_MEMORY);
+  }
+}
+
+void evalset_free(slimgpu_evalset_t* es) { delete es; }
+
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, EvalResult* out) {
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (!es || !model || !out || model_row_view(model, &W) != SLIM_OK || matrix_csr_view(es->mat, &R) != SLIM_OK) {
+    set_error("SLIMGPU_ModelEvaluate: needs an eval set and a resident model with a row view");
+    return SLIM_ERROR_INPUT;
+  }
+  if (const int32_t rc = check_pair("SLIMGPU_ModelEvaluate", R, W); rc != SLIM_OK) return rc;
+  if (es->device != R.device) {
+    set_error("SLIMGPU_ModelEvaluate: the eval set and the matrix live on different devices");
+    return SLIM_ERROR_INPUT;
+  }
+  *out = EvalResult();
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    es->ws.allocs = 0;
+    EvalOut h = {};
+    if (es->nusers > 0) {
+      HistoryView H;
+      H.nusers = es->nusers;
+      H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
+      H.max_hist = es->max_hist;
+      const EvalTargets ev = {es->d_tptr.get(), es->d_tind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get()};
+      EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
+      HIP_TRY(hipEventRecord(es->ev0, stream));
+      st.path = queue_scorer(W, H, es->nrcmds, R.num_cus, stream, es->ws, &ev, /*lists=*/false);
+      launch_sum_in_user_order(stream, es->nusers, es->d_terms.get(), d_out->f, d_out->n);
+      HIP_TRY(hipEventRecord(es->ev1, stream));
+      HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
+      if (es->hist_entries > 0 && W.nnz > 0) {
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((es->hist_entries + 255) / 256, R.num_cus * 8));
+        hipLaunchKernelGGL(k_streamed_entries, dim3(blocks), dim3(256), 0, stream, es->hist_begin, es->hist_begin + es->hist_entries,
+                           R.d_ind, W.nrows, W.d_ptr, &d_out->streamed);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(&h, d_out, sizeof(EvalOut), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      st.d2h_bytes = sizeof(EvalOut);
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, es->ev0, es->ev1));
+      st.kernel_ms = ms;
+    }
+    out->nvalid = h.n[0];
+    out->nvalid_head = h.n[1];
+    out->nvalid_tail = h.n[2];
+    out->hr = h.n[0] > 0 ? h.f[0] / h.n[0] : 0;
+    out->hr_head = h.n[1] > 0 ? h.f[1] / h.n[1] : 0;
+    out->hr_tail = h.n[2] > 0 ? h.f[2] / h.n[2] : 0;
+    out->arhr = h.n[0] > 0 ? h.f[3] / h.n[0] : 0;
+    st.device_allocs = es->ws.allocs;
+    st.w_rows_read = es->hist_entries;
+    st.w_bytes = 8.0 * (double)h.streamed;
+    st.total_ms = ms_since(t_begin);
+    g_eval_stats = st;
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_ModelEvaluate", e);
+  }
+}
+
+int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
+                       float* scores) {
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (!model || !mat || !output || !scores || nrcmds < 1 || nrcmds > 128 || model_row_view(model, &W) != SLIM_OK ||
+      matrix_csr_view(mat, &R) != SLIM_OK) {
+    set_error("SLIMGPU_MatrixPredict: bad arguments (a resident model, a staged matrix, 1 <= nrcmds <= 128)");
+    return SLIM_ERROR_INPUT;
+  }
+  if (const int32_t rc = check_pair("SLIMGPU_MatrixPredict", R, W); rc != SLIM_OK) return rc;
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int32_t rc = SLIM_OK;
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    const int32_t nu = R.nrows;
+    if (nu > 0) {
+      ScorerWorkspace ws;
+      DeviceBuffer<int32_t> d_max(1);
+      ++ws.allocs;
+      HIP_TRY(hipMemsetAsync(d_max.get(), 0, sizeof(int32_t), stream));
+      hipLaunchKernelGGL(k_longest_row, dim3(std::max(1, std::min((nu + 255) / 256, R.num_cus * 8))), dim3(256), 0,
+                         stream, nu, R.d_ptr, d_max.get());
+      HIP_TRY(hipGetLastError());
+      int32_t h_max = 0;
+      HIP_TRY(hipMemcpyAsync(&h_max, d_max.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      HistoryView H;
+      H.nusers = nu;
+      H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
+      H.max_hist = h_max;
+      HIP_TRY(hipEventCreate(&ev0));
+      HIP_TRY(hipEventCreate(&ev1));
+      HIP_TRY(hipEventRecord(ev0, stream));
+      st.path = queue_scorer(W, H, nrcmds, R.num_cus, stream, ws, nullptr, /*lists=*/true);
+      HIP_TRY(hipEventRecord(ev1, stream));
+      // only the lists come down; slots beyond a list's length stay as the caller filled them
+      std::vector<int32_t> h_id((size_t)nu * nrcmds), h_cnt((size_t)nu);
+      std::vector<float> h_sc((size_t)nu * nrcmds);
+      HIP_TRY(hipMemcpyAsync(h_id.data(), ws.oid.get(), sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(h_sc.data(), ws.osc.get(), sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(h_cnt.data(), ws.ocnt.get(), sizeof(int32_t) * h_cnt.size(), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      for (int32_t u = 0; u < nu; ++u)
+        for (int32_t r = 0; r < h_cnt[u]; ++r) {
+          output[(int64_t)u * nrcmds + r] = h_id[(size_t)u * nrcmds + r];
+          scores[(int64_t)u * nrcmds + r] = h_sc[(size_t)u * nrcmds + r];
+        }
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+      st.kernel_ms = ms;
+      st.device_allocs = ws.allocs;
+      st.d2h_bytes = (int64_t)(sizeof(int32_t) * (h_id.size() + h_cnt.size()) + sizeof(float) * h_sc.size() + sizeof(int32_t));
+      st.w_rows_read = R.nnz;
+    }
+    st.total_ms = ms_since(t_begin);
+    g_eval_stats = st;
+  } catch (const HipFail& e) {
+    rc = hip_failure("SLIMGPU_MatrixPredict", e);
+  } catch (const std::bad_alloc&) {
+    set_error("SLIMGPU_MatrixPredict: out of host memory");
+    rc = SLIM_ERROR_MEMORY;
+  }
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  return rc;
 }
 
 }  // namespace slimamd

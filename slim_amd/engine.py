@@ -108,6 +108,18 @@ class ResidentModel(object):
             raise RuntimeError("SLIMGPU_ModelFetch failed (%d): %s" % (st.value, _lib.last_error()))
         return h if return_handle else model_to_scipy(self._lib, h)
 
+    def predict(self, device_matrix, nrcmds=10):
+        """SLIMGPU_MatrixPredict: top-N of every row of the staged matrix, scored in HBM (only the
+        lists come down).  Returns (ids, scores) of shape [nusers, nrcmds]; ids are -1 and scores 0
+        beyond a user's list."""
+        n = device_matrix.nrows
+        ids = np.full(n * nrcmds, -1, np.int32)
+        scores = np.zeros(n * nrcmds, np.float32)
+        st = self._lib.SLIMGPU_MatrixPredict(int(nrcmds), self.handle, device_matrix.handle, ids, scores)
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_MatrixPredict failed (%d): %s" % (st, _lib.last_error()))
+        return ids.reshape(n, nrcmds), scores.reshape(n, nrcmds)
+
     def free(self):
         if self.handle:
             self._lib.SLIMGPU_ModelFree(C.byref(self.handle))
@@ -120,6 +132,60 @@ class ResidentModel(object):
             pass
 
 
+def eval_stats(lib=None):
+    """Counters of the most recent ModelEvaluate / MatrixPredict on this thread, as a dict."""
+    st = _lib.EvalStats()
+    (lib or _lib.load()).SLIMGPU_LastEvalStats(C.byref(st))
+    return st.as_dict()
+
+
+def _wrap_rows(lib, M):
+    """Host handle (Py_csr_wrapper) of a scipy matrix's rows; release with Py_csr_free."""
+    M = sp.csr_matrix(M)
+    ptr = np.ascontiguousarray(M.indptr, dtype=np.intp)
+    ind = np.ascontiguousarray(M.indices, dtype=np.int32)
+    val = np.ascontiguousarray(M.data, dtype=np.float32)
+    h = C.c_void_p()
+    st = lib.Py_csr_wrapper(M.shape[0], ptr, ind, val.ctypes.data_as(C.c_void_p), C.byref(h))
+    if st != SLIM_OK:
+        raise RuntimeError("Py_csr_wrapper failed (%d)" % st)
+    return h
+
+
+class Evaluator(object):
+    """The test set of a grid staged in HBM (SLIMGPU_EvalSetCreate): `evaluate(resident_model)` scores
+    the model against the staged training matrix and brings down HR / ARHR only."""
+
+    def __init__(self, lib, handle, matrix):
+        self._lib = lib
+        self.handle = C.c_void_p(handle)
+        self._matrix = matrix      # borrowed by the eval set: keep it alive
+
+    def evaluate(self, model):
+        met = np.zeros(4, np.float64)
+        nv = np.zeros(3, np.int32)
+        st = self._lib.SLIMGPU_ModelEvaluate(self.handle, model.handle, met, nv)
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_ModelEvaluate failed (%d): %s" % (st, _lib.last_error()))
+        return {"hr": met[0], "hr_head": met[1], "hr_tail": met[2], "arhr": met[3],
+                "nvalid": int(nv[0]), "nvalid_head": int(nv[1]), "nvalid_tail": int(nv[2])}
+
+    def stats(self):
+        return eval_stats(self._lib)
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            self._lib.SLIMGPU_EvalSetFree(C.byref(self.handle))
+        self.handle = None
+        self._matrix = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
 class DeviceMatrix(object):
     """Training matrix resident in HBM (CSR + column view + norms)."""
 
@@ -127,6 +193,7 @@ class DeviceMatrix(object):
         self._lib = _lib.load()
         self.handle = C.c_void_p(handle)
         self._keep = keepalive
+        self._host_rows = None
         nr, nc, nz = C.c_int32(), C.c_int32(), C.c_int64()
         self._lib.SLIMGPU_MatrixInfo(self.handle, C.byref(nr), C.byref(nc), C.byref(nz))
         self.nrows, self.ncols, self.nnz = nr.value, nc.value, nz.value
@@ -146,7 +213,9 @@ class DeviceMatrix(object):
                                        iopt.ctypes.data_as(C.c_void_p), C.byref(st))
         if not h:
             raise RuntimeError("SLIMGPU_MatrixFromHost failed (%d): %s" % (st.value, _lib.last_error()))
-        return cls(h)
+        m = cls(h)
+        m._host_rows = (R.shape[0], ptr, ind)   # evaluator(): the head / tail split is over these rows
+        return m
 
     @classmethod
     def from_device_ptrs(cls, nrows, ncols, rowptr_ptr, rowind_ptr, rowval_ptr, keepalive=None,
@@ -168,6 +237,7 @@ class DeviceMatrix(object):
             self._lib.SLIMGPU_MatrixFree(C.byref(self.handle))
         self.handle = None
         self._keep = None
+        self._host_rows = None
 
     __del__ = close
 
@@ -233,6 +303,38 @@ class DeviceMatrix(object):
         stats = _lib.Stats()
         self._lib.SLIMGPU_LastStats(C.byref(stats))
         return ResidentModel(self._lib, h), stats.as_dict()
+
+    def evaluator(self, T, nrcmds=10, fmarker=None, R=None):
+        """SLIMGPU_EvalSetCreate: stage the test matrix T (scipy, one row per user) for evaluations
+        of resident models against this matrix.  fmarker=None: SLIM_DetermineHeadAndTail over the
+        training rows with ncols = the larger of the two matrices' widths, as Py_SLIM_Mselect does
+        (the rows from_scipy staged; R, a scipy matrix, for a matrix adopted from device pointers)."""
+        T = sp.csr_matrix(T)
+        if fmarker is None:
+            if R is not None:
+                R = sp.csr_matrix(R)
+                rows = (R.shape[0], np.ascontiguousarray(R.indptr, dtype=np.intp),
+                        np.ascontiguousarray(R.indices, dtype=np.int32))
+            else:
+                rows = self._host_rows
+            if rows is None:
+                raise ValueError("evaluator: give fmarker, or the training rows R to derive it from")
+            tmax = int(T.indices.max()) + 1 if T.nnz else 0
+            ncols = max(self.ncols, tmax, 1)
+            p = self._lib.SLIM_DetermineHeadAndTail(rows[0], ncols, rows[1], rows[2])
+            fmarker = np.ctypeslib.as_array(p, shape=(ncols,)).copy()
+            C.CDLL(None).free(p)
+        fmarker = np.ascontiguousarray(fmarker, dtype=np.int32)
+        ht = _wrap_rows(self._lib, T)
+        st = C.c_int32(0)
+        try:
+            h = self._lib.SLIMGPU_EvalSetCreate(self.handle, ht, fmarker, fmarker.size, int(nrcmds),
+                                                C.byref(st))
+        finally:
+            self._lib.Py_csr_free(ht)
+        if not h:
+            raise RuntimeError("SLIMGPU_EvalSetCreate failed (%d): %s" % (st.value, _lib.last_error()))
+        return Evaluator(self._lib, h, self)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)
