@@ -1931,6 +1931,12 @@ Entries run_launches(slimgpu_matrix* m, const LearnOptions& opt, const std::vect
     if (attempt > 0) L.t.nheavy = 0;  // a retry regroups what is left: plain clusters
     SolveArgs S = solve_args(m, opt, L, pending, attempt, d_ai, d_av);
     const int clusterK = L.t.clusterK;
+    if (opt.build_G && p.trace_level >= 1) {  // which form of the G builder this launch is (cd_tile.hpp, gram_mode 3)
+      const bool in_passes = S.gram_bits != 0 && p.gram_passes > 1;
+      std::fprintf(stderr, "[trace] G builder: form %s, clusters of %d, pass %d of %d, %d users at most per member\n",
+                   S.gram_bits == 2 ? "bits2" : (S.gram_bits == 1 ? "bits1" : "lines"), clusterK, L.gram_pass + 1,
+                   p.gram_passes, in_passes ? m->gsplit.max_rows : m->split[L.t.cluster_lg].max_rows);
+    }
 
     // clustered tiles: always launch whole clusters (every member must be resident)
     const int launch_waves = p.use_tile ? std::max(1, std::min((npend + p.tileP - 1) / p.tileP, L.t.nclusters)) * clusterK
