@@ -321,6 +321,8 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
       const int gst = S.gram_split_stride;  // (K + 1, or the row length of the user passes' table)
       const int nus = uend - ubase;
       for (int k = tid; k < nus; k += NT) s_bits[k] = 0u;
+      // (the word the padding of the id view points at: behind every member's users)
+      if (S.gview != nullptr && tid == 0) s_bits[S.gview_sentinel] = 0u;
       __syncthreads();
 #pragma unroll
       for (int pp = 0; pp < PPW; ++pp) {
@@ -347,16 +349,17 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
         constexpr int NPL = 16;  // planes: counts below 2^16 per (column slice, item) -- a member's
                                  // user range holds at most 37 888 users (148 KB of LDS)
         const int32_t* __restrict__ ord = S.order;
-        for (int p0 = base + wave * 64; p0 < S.nwork; p0 += NW * 64) {
+        // The ids come from the builder's view of them (SolveArgs::gview) when the engine has built it:
+        // 2 bytes per id instead of 4, a wavefront load of a row is contiguous (1 KB while every lane's
+        // slice lasts) instead of 16 bytes of 64 lines, and no lane tests its slice's end per id -- the
+        // padding of its last piece reads a word that holds 0.  Its groups are aligned to 64 positions: a
+        // tile whose base is an odd multiple of 32 starts in the middle of one, counts the 32 positions
+        // in front of its base with the rest and drops them.
+        const uint4* __restrict__ const gv = S.gview;
+        for (int p0 = (gv != nullptr ? (base & ~63) : base) + wave * 64; p0 < S.nwork; p0 += NW * 64) {
           const int pl = p0 + lane;
-          const bool have = pl < S.nwork;
+          const bool have = pl >= base && pl < S.nwork;
           const int i = have ? ord[pl] : 0;
-          int64_t cs = 0, ce = 0;
-          if (have) {
-            cs = csplit[(int64_t)i * gst + mk];
-            ce = csplit[(int64_t)i * gst + mk + 1];
-          }
-          const int len = (int)(ce - cs);
           uint32_t ones = 0u, twos = 0u, fours = 0u, hi[NPL - 3];
 #pragma unroll
           for (int pp = 0; pp < NPL - 3; ++pp) hi[pp] = 0u;
@@ -367,6 +370,86 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
     h = ((a) & (b)) | (u_ & (c));    \
     l = u_ ^ (c);                    \
   }
+          // eight words of every lane into its counter planes
+          auto add8 = [&](const uint32_t (&w)[8]) {
+            uint32_t ta, tb, fa, fb, e8;
+            SLIM_CSA(ta, ones, ones, w[0], w[1]);
+            SLIM_CSA(tb, ones, ones, w[2], w[3]);
+            SLIM_CSA(fa, twos, twos, ta, tb);
+            SLIM_CSA(ta, ones, ones, w[4], w[5]);
+            SLIM_CSA(tb, ones, ones, w[6], w[7]);
+            SLIM_CSA(fb, twos, twos, ta, tb);
+            SLIM_CSA(e8, fours, fours, fa, fb);
+            uint32_t carry = e8;  // into plane 3 and upward, while any lane carries
+#pragma unroll
+            for (int pp = 0; pp < NPL - 3; ++pp) {
+              if (__ballot(carry != 0u) == 0ull) break;
+              const uint32_t nc = hi[pp] & carry;
+              hi[pp] ^= carry;
+              carry = nc;
+              nhi = nhi > pp + 1 ? nhi : pp + 1;
+            }
+          };
+          if (gv != nullptr) {
+            // a step = four rows of the group's block (32 ids of every lane); the rows of the next
+            // step are requested before the words of this one are read.  The trip count is the
+            // longest slice's pieces: the same for every lane.  The rows that all 64 lanes are in lie
+            // 1 KB apart; behind them, rows are requested in order, so the start of the next one is a
+            // running count of the pieces requested (uniform), and a lane whose slice has ended
+            // requests nothing and adds the spare word.
+            constexpr int RS = 4;
+            const int64_t vblk = (int64_t)(S.gview_range0 + mk) * S.gview_ngroups + (p0 >> 6);
+            // pieces of this lane's slice (the positions in front of the base included)
+            const int mine = S.gview_cnt[vblk * 64 + lane];
+            const uint4* const vp = gv + uni(S.gview_base[vblk]);
+            int nch = mine, nall = mine;  // rows in all, rows that every lane is in
+            for (int off = 32; off > 0; off >>= 1) {
+              const int o = __shfl_xor(nch, off), u = __shfl_xor(nall, off);
+              nch = nch > o ? nch : o;
+              nall = nall < u ? nall : u;
+            }
+            nch = uni(nch);
+            nall = uni(nall);
+            const uint32_t pad2 = (uint32_t)S.gview_sentinel * 0x10001u;
+            int at = nall * 64;
+            auto row = [&](int c) {
+              if (c < nall) return vp[c * 64 + lane];
+              const bool in = c < mine;
+              const uint64_t who = __ballot(in);
+              uint4 v = make_uint4(pad2, pad2, pad2, pad2);
+              if (in) v = vp[at + __popcll(who & ((1ull << lane) - 1ull))];
+              at += __popcll(who);
+              return v;
+            };
+            uint4 cur[RS], nxt[RS];
+#pragma unroll
+            for (int j = 0; j < RS; ++j) cur[j] = row(j);
+            for (int c = 0; c < nch; c += RS) {
+#pragma unroll
+              for (int j = 0; j < RS; ++j) nxt[j] = row(c + RS + j);
+#pragma unroll
+              for (int j = 0; j < RS; ++j) {
+                if (c + j < nch) {
+                  const uint32_t pr[4] = {cur[j].x, cur[j].y, cur[j].z, cur[j].w};
+                  uint32_t w[8];
+#pragma unroll
+                  for (int h = 0; h < 4; ++h) {
+                    w[2 * h] = s_bits[pr[h] & 0xFFFFu];
+                    w[2 * h + 1] = s_bits[pr[h] >> 16];
+                  }
+                  add8(w);
+                }
+              }
+#pragma unroll
+              for (int j = 0; j < RS; ++j) cur[j] = nxt[j];
+            }
+          } else {
+          int64_t cs = 0, ce = 0;
+          if (have) {
+            cs = csplit[(int64_t)i * gst + mk];
+            ce = csplit[(int64_t)i * gst + mk + 1];
+          }
+          const int len = (int)(ce - cs);
           // a step = 32 ids of every lane's slice, i.e. one whole 128-byte line per lane (eight
           // 16-byte loads, dword-aligned): a lane that took 8 ids per step came back to its line
           // four times, and with 1024 lanes per CU walking different lines the caches did not
@@ -392,27 +475,40 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
                 w[j] = s_bits[ok ? uu[j] - ubase : 0];
                 w[j] = ok ? w[j] : 0u;
               }
-              uint32_t ta, tb, fa, fb, e8;
-              SLIM_CSA(ta, ones, ones, w[0], w[1]);
-              SLIM_CSA(tb, ones, ones, w[2], w[3]);
-              SLIM_CSA(fa, twos, twos, ta, tb);
-              SLIM_CSA(ta, ones, ones, w[4], w[5]);
-              SLIM_CSA(tb, ones, ones, w[6], w[7]);
-              SLIM_CSA(fb, twos, twos, ta, tb);
-              SLIM_CSA(e8, fours, fours, fa, fb);
-              uint32_t carry = e8;  // into plane 3 and upward, while any lane carries
-#pragma unroll
-              for (int pp = 0; pp < NPL - 3; ++pp) {
-                if (__ballot(carry != 0u) == 0ull) break;
-                const uint32_t nc = hi[pp] & carry;
-                hi[pp] ^= carry;
-                carry = nc;
-                nhi = nhi > pp + 1 ? nhi : pp + 1;
-              }
+              add8(w);
             }
+          }
           }
 #undef SLIM_CSA
           // planes -> the P counts of this lane's column
+          if (S.gram_part16) {
+            // as 16-bit numbers, two to a word (a member's count is at most its users, < 2^16): half a
+            // line per column to write here and to read back when the members' sums are added
+            uint32_t c2[P / 2];
+#pragma unroll
+            for (int h = 0; h < P / 2; ++h) {
+              const uint32_t o = ones >> (2 * h), t = twos >> (2 * h), f = fours >> (2 * h);
+              c2[h] = ((o & 1u) + ((t & 1u) << 1) + ((f & 1u) << 2)) |
+                      ((((o >> 1) & 1u) + (((t >> 1) & 1u) << 1) + (((f >> 1) & 1u) << 2)) << 16);
+            }
+#pragma unroll
+            for (int pp = 0; pp < NPL - 3; ++pp) {
+              if (pp < nhi) {
+#pragma unroll
+                for (int h = 0; h < P / 2; ++h) {
+                  const uint32_t v = hi[pp] >> (2 * h);
+                  c2[h] += ((v & 1u) << (pp + 3)) | (((v >> 1) & 1u) << (pp + 19));
+                }
+              }
+            }
+            if (have) {
+              uint4* const out = reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(part) + (int64_t)i * P);
+#pragma unroll
+              for (int j = 0; j < P / 8; ++j)
+                out[j] = make_uint4(c2[4 * j], c2[4 * j + 1], c2[4 * j + 2], c2[4 * j + 3]);
+            }
+            continue;
+          }
           float cnt[P];
 #pragma unroll
           for (int qq = 0; qq < P; ++qq)
@@ -693,7 +789,14 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
         const int pi = S.gram_pos[i];
         if (pi >= base && it >= 0) {
           float a = 0.0f;  // members in rank order
-          for (int k = 0; k < K; ++k) a += S.atypart[(int64_t)(cid * K + k) * S.x_stride + idx];
+          if (S.gram_part16) {  // (the bit-sliced form left 16-bit counts: their sum is below 2^24)
+            uint32_t n = 0u;
+            for (int k = 0; k < K; ++k)
+              n += reinterpret_cast<const uint16_t*>(S.atypart + (int64_t)(cid * K + k) * S.x_stride)[idx];
+            a = (float)n;
+          } else {
+            for (int k = 0; k < K; ++k) a += S.atypart[(int64_t)(cid * K + k) * S.x_stride + idx];
+          }
           // (user passes: every pass holds the sums over ITS users; counts are integers below 2^24,
           // so the float additions are exact in any order)
           if (S.gram_accum) a += S.G[(int64_t)it * S.G_ld + i];

@@ -120,6 +120,23 @@ struct SolveArgs {
                                  // user passes, the passes' common table: the launch's ubounds / csplit point at
                                  // the pass's first range)
   int32_t gram_accum;            // gram_bits, user passes after the first: the sums are ADDED to G
+  // gram_bits 2: the builder's own view of the column ids (engine.hip, k_gview_fill), nullptr: the ids come
+  // from the column view.  16-bit ids relative to the start of the user range, interleaved by GROUP of 64
+  // consecutive work-list positions (aligned to 64).  A slice is cut into pieces of 8 ids = 16 bytes, its
+  // last one filled up with gview_sentinel, the index of a spare word of the LDS words that is kept 0.
+  // The block of (range, group) is its rows one behind the other: row c holds piece c of every position
+  // whose slice has one, in lane order, so a short slice costs no bytes in the rows behind its end (a
+  // row of a group of equal slices is 64 x 16 bytes).  A lane finds its piece of row c at the row's
+  // start + the number of lower lanes that have one; the rows that every lane is in come first and need
+  // no such count
+  const uint4* gview;
+  const int64_t* gview_base;     // [ranges x gview_ngroups + 1]: first piece of every block (blocks lie in that
+                                 // order, so the next entry ends the block)
+  const uint16_t* gview_cnt;     // [ranges x gview_ngroups][64]: pieces of every position's slice
+  int32_t gview_ngroups;         // groups of 64 positions in the work list
+  int32_t gview_range0;          // the launch's first range (user passes: 32 x pass)
+  int32_t gview_sentinel;
+  int32_t gram_part16;           // gram_bits 2: the members' partial counts in atypart are 16-bit, [ncols][P]
   // packed item-space kernel (cd_gramr.hpp): g of every problem as the solve leaves it (g_save) / as an
   // earlier solve of the same problems left it (g_load: starts from it instead of set-up row + fold);
   // [item][g_stride] floats in the kernel's own thread layout; both may point at the same buffer

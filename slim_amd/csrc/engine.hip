@@ -110,6 +110,11 @@ struct slimgpu_matrix {
   DeviceBuffer<int64_t> ws_off, ws_stat_l, ws_icolptr;
   DeviceBuffer<float> ws_stat_f, ws_arena_v, ws_slab, ws_xslab, ws_part, ws_icolval;
   DeviceBuffer<uint64_t> ws_trace;
+  // the G builder's view of the column ids (build_gview): lives for one build
+  DeviceBuffer<uint4> ws_gview;
+  DeviceBuffer<int64_t> ws_gvbase;
+  DeviceBuffer<int32_t> ws_gvrows;
+  DeviceBuffer<uint16_t> ws_gvcnt;
   DeviceBuffer<unsigned long long> ws_mailbox;
   DeviceBuffer<int32_t> ws_icolind;
   // the row view of a resident model (transpose_on_device)
@@ -194,6 +199,67 @@ auto evict_cache(slimgpu_matrix* m) {
     drop_screen_cache(m);
     return true;
   };
+}
+
+// ---- the G builder's view of the column ids (SolveArgs::gview) ------------------
+// One wavefront per (user range, group of 64 work-list positions), lane = position.
+
+// 16-byte pieces (8 ids) the block of (range, group) takes: every slice of the group / 8, rounded up (cnt,
+// per position), summed
+__global__ void k_gview_rows(const int32_t* __restrict__ order, int32_t nwork, const int64_t* __restrict__ csplit,
+                             int32_t stride, int32_t ngroups, int32_t nblocks, int32_t* __restrict__ rows,
+                             uint16_t* __restrict__ cnt) {
+  const int b = (int)blockIdx.x * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6);
+  if (b >= nblocks) return;
+  const int r = b / ngroups, pl = (b % ngroups) * 64 + ((int)threadIdx.x & 63);
+  int len = 0;
+  if (pl < nwork) {
+    const int64_t* const c = csplit + (int64_t)order[pl] * stride + r;
+    len = (int)(c[1] - c[0]);
+  }
+  int n = (len + 7) >> 3;
+  cnt[(int64_t)b * 64 + (threadIdx.x & 63)] = (uint16_t)n;  // (a range holds fewer than 2^16 users)
+  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+  if ((threadIdx.x & 63) == 0) rows[b] = n;
+}
+
+// the blocks themselves: every lane walks its slice and stores its ids, relative to the range's first
+// user, eight to a piece; the last piece of a slice is filled up with the sentinel.  Row c of a block
+// holds piece c of every lane that has one, in lane order, and the rows follow each other without a
+// gap (a wavefront store is up to 1 KB contiguous) -- cd_tile.hpp finds a piece the same way
+__global__ void k_gview_fill(const int32_t* __restrict__ order, int32_t nwork, const int64_t* __restrict__ csplit,
+                             int32_t stride, const int32_t* __restrict__ ubounds, const int32_t* __restrict__ ci,
+                             int32_t ngroups, int32_t nblocks, const int64_t* __restrict__ base, uint32_t sentinel,
+                             uint4* __restrict__ view) {
+  const int b = (int)blockIdx.x * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6);
+  if (b >= nblocks) return;
+  const int lane = (int)threadIdx.x & 63;
+  const int r = b / ngroups, pl = (b % ngroups) * 64 + lane;
+  const int64_t end = base[b + 1];
+  const int32_t u0 = ubounds[r];
+  int64_t cs = 0;
+  int len = 0;
+  if (pl < nwork) {
+    const int64_t* const c = csplit + (int64_t)order[pl] * stride + r;
+    cs = c[0];
+    len = (int)(c[1] - cs);
+  }
+  int64_t at = base[b];  // the row's first piece
+  for (int c = 0;; ++c) {
+    const bool mine = 8 * c < len;
+    const uint64_t who = __ballot(mine);
+    if (who == 0ull) break;
+    if (mine) {
+      const int64_t slot = at + __popcll(who & ((1ull << lane) - 1ull));
+      uint32_t id[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) id[j] = 8 * c + j < len ? (uint32_t)(ci[cs + 8 * c + j] - u0) : sentinel;
+      if (slot < end)  // (always: base was summed from the same lengths)
+        view[slot] = make_uint4(id[0] | (id[1] << 16), id[2] | (id[3] << 16), id[4] | (id[5] << 16),
+                                id[6] | (id[7] << 16));
+    }
+    at += __popcll(who);
+  }
 }
 
 // ---- staging kernels -----------------------------------------------------------
@@ -1554,6 +1620,15 @@ struct Launch {
   bool cluster_fallback = false;
   int64_t arena_cap = 0;
   int32_t G_block = 0;
+  // the G builder's view of the column ids (build_gview), tried once per build
+  bool gview_tried = false;
+  const uint4* gview = nullptr;
+  const int64_t* gview_base = nullptr;
+  const uint16_t* gview_cnt = nullptr;
+  int32_t gview_ngroups = 0, gview_sentinel = 0;
+  size_t gview_bytes = 0;
+  double gview_ms = 0;
+  const char* gview_why = "";  // why the ids come from the column view instead
 };
 
 // The launches' buffers, the warm start, the screen-sum cache and the carried g.
@@ -1728,6 +1803,15 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
   if (const char* e = std::getenv("SLIM_GPU_GBITS"); e && S.gram_bits) S.gram_bits = std::atoi(e) == 1 ? 1 : 2;
   S.gram_split_stride = t.clusterK + 1;
   S.gram_accum = 0;
+  S.gview = nullptr;  // (run_launches: build_gview)
+  S.gview_base = nullptr;
+  S.gview_cnt = nullptr;
+  S.gview_ngroups = 0;
+  S.gview_range0 = 0;
+  S.gview_sentinel = 0;
+  // (SLIM_GPU_GPART16=0: float partial sums, as the other forms write them)
+  S.gram_part16 = S.gram_bits == 2 ? 1 : 0;
+  if (const char* e = std::getenv("SLIM_GPU_GPART16"); e && std::atoi(e) == 0) S.gram_part16 = 0;
   S.g_save = nullptr;
   S.g_load = nullptr;
   S.g_stride = 0;
@@ -1792,6 +1876,63 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
   S.st_err = L.stf;
   S.st_obj = L.stf + ncols;
   return S;
+}
+
+// The bit-sliced G builder's view of the column ids (SolveArgs::gview, cd_tile.hpp), over every user
+// range of the split in use (all passes) and the work list of this build, which S holds as its first
+// launch sees them.  Built before that launch, dropped when the build ends (run_launches).  Without it
+// -- SLIM_GPU_GVIEW=0, a range too long for 16-bit ids, no room in HBM -- the builder reads the
+// column view as it always did: the same G.
+void build_gview(slimgpu_matrix* m, Launch& L, const SolveArgs& S, const int32_t* d_colind) {
+  L.gview_tried = true;
+  if (const char* e = std::getenv("SLIM_GPU_GVIEW"); e && std::atoi(e) == 0) {
+    L.gview_why = " (SLIM_GPU_GVIEW=0)";
+    return;
+  }
+  hipStream_t stream = m->stream;
+  const double t0 = now_ms();
+  const int nranges = 32 * L.p.gram_passes;
+  const int ngroups = (S.nwork + 63) / 64;
+  // the spare word: behind every range's users, inside the LDS words (round_up(max_rows, 64) + 64 of them)
+  const int sentinel = S.bm_words - 64;
+  if ((int64_t)nranges * ngroups >= (int64_t(1) << 31) || sentinel >= 65536 || sentinel < 0) {
+    L.gview_why = " (ranges beyond 16-bit ids)";
+    return;
+  }
+  const int nblocks = nranges * ngroups;
+  try {
+    int32_t* d_rows = m->ws_gvrows.reserve((size_t)nblocks);
+    int64_t* d_base = m->ws_gvbase.reserve((size_t)nblocks + 1);
+    uint16_t* d_cnt = m->ws_gvcnt.reserve((size_t)nblocks * 64);
+    const dim3 grid((unsigned)((nblocks + 3) / 4)), block(256);
+    hipLaunchKernelGGL(k_gview_rows, grid, block, 0, stream, S.order, S.nwork, S.csplit, S.gram_split_stride, ngroups,
+                       nblocks, d_rows, d_cnt);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> rows((size_t)nblocks);
+    HIP_TRY(hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * rows.size(), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    std::vector<int64_t> base((size_t)nblocks + 1, 0);
+    for (int b = 0; b < nblocks; ++b) base[(size_t)b + 1] = base[(size_t)b] + rows[(size_t)b];
+    const int64_t total = base[(size_t)nblocks];
+    uint4* d_view = m->ws_gview.reserve((size_t)std::max<int64_t>(total, 1), evict_cache(m));
+    HIP_TRY(hipMemcpyAsync(d_base, base.data(), sizeof(int64_t) * base.size(), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_gview_fill, grid, block, 0, stream, S.order, S.nwork, S.csplit, S.gram_split_stride, S.ubounds,
+                       d_colind, ngroups, nblocks, d_base, (uint32_t)sentinel, d_view);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));  // (base is a local)
+    L.gview = d_view;
+    L.gview_base = d_base;
+    L.gview_cnt = d_cnt;
+    L.gview_ngroups = ngroups;
+    L.gview_sentinel = sentinel;
+    L.gview_bytes = (size_t)total * 16;
+    L.gview_ms = now_ms() - t0;
+  } catch (const HipFail& e) {
+    if (e.code != hipErrorOutOfMemory) throw;
+    (void)hipGetLastError();
+    m->ws_gview.reset();
+    L.gview_why = " (no room for the 16-bit view)";
+  }
 }
 
 // SLIM_GPU_TRACE: the per-tile timeline of a launch -- where does it spend its time?
@@ -1910,6 +2051,16 @@ Entries run_launches(slimgpu_matrix* m, const LearnOptions& opt, const std::vect
     P.nchunks = m->Gp_nchunks;
   }
 
+  struct DropView {  // the id view of a G build ends with the build, on every exit path
+    slimgpu_matrix* m;
+    ~DropView() {
+      m->ws_gview.reset();
+      m->ws_gvbase.reset();
+      m->ws_gvrows.reset();
+      m->ws_gvcnt.reset();
+    }
+  } drop_view{m};
+
   Entries E;
   E.cnt.assign((size_t)ncols, 0);
   E.off.assign((size_t)ncols, 0);
@@ -1931,11 +2082,25 @@ Entries run_launches(slimgpu_matrix* m, const LearnOptions& opt, const std::vect
     if (attempt > 0) L.t.nheavy = 0;  // a retry regroups what is left: plain clusters
     SolveArgs S = solve_args(m, opt, L, pending, attempt, d_ai, d_av);
     const int clusterK = L.t.clusterK;
+    if (opt.build_G && S.gram_bits == 2 && !L.gview_tried) build_gview(m, L, S, A.colind);
+    if (opt.build_G && S.gram_bits == 2 && L.gview) {
+      S.gview = L.gview;
+      S.gview_base = L.gview_base;
+      S.gview_cnt = L.gview_cnt;
+      S.gview_ngroups = L.gview_ngroups;
+      S.gview_range0 = 32 * L.gram_pass;
+      S.gview_sentinel = L.gview_sentinel;
+    }
     if (opt.build_G && p.trace_level >= 1) {  // which form of the G builder this launch is (cd_tile.hpp, gram_mode 3)
       const bool in_passes = S.gram_bits != 0 && p.gram_passes > 1;
       std::fprintf(stderr, "[trace] G builder: form %s, clusters of %d, pass %d of %d, %d users at most per member\n",
                    S.gram_bits == 2 ? "bits2" : (S.gram_bits == 1 ? "bits1" : "lines"), clusterK, L.gram_pass + 1,
                    p.gram_passes, in_passes ? m->gsplit.max_rows : m->split[L.t.cluster_lg].max_rows);
+      if (S.gview)
+        std::fprintf(stderr, "[trace] G builder: ids from view, %zu bytes = %.3f x 2 bytes per nnz, built in %.1f ms\n",
+                     L.gview_bytes, (double)L.gview_bytes / (2.0 * (double)std::max<int64_t>(m->nnz, 1)), L.gview_ms);
+      else
+        std::fprintf(stderr, "[trace] G builder: ids from csc%s\n", S.gram_bits == 2 ? L.gview_why : "");
     }
 
     // clustered tiles: always launch whole clusters (every member must be resident)
