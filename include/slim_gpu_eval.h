@@ -12,6 +12,8 @@
 extern "C" {
 #endif
 
+#define SLIMGPU_MAX_CUTOFFS 8 /* list lengths one eval set serves (SLIMGPU_EvalSetCreateAt) */
+
 /* Evaluation without leaving HBM.  Every cell of a model-selection grid is learn + evaluate
  * (src/programs/slim_mselect.c:99-196, src/libslim/pyapi.c:283-375); with the model resident and R
  * staged, the evaluation needs nothing from the host but the test set, which is staged once per
@@ -29,9 +31,41 @@ slimgpu_evalset_t *SLIMGPU_EvalSetCreate(slimgpu_matrix_t *mat, slim_t *tsthandl
                                          int32_t nrcmds, int32_t *r_status);
 void SLIMGPU_EvalSetFree(slimgpu_evalset_t **es);
 /* metrics = {HR, HR_head, HR_tail, ARHR}, nvalid[3]: exactly the outputs SLIMGPU_Evaluate gives for
- * the lists of SLIMGPU_ModelPredict, bit for bit.  28 bytes cross PCIe. */
+ * the lists of SLIMGPU_ModelPredict, bit for bit.  40 bytes cross PCIe.  The last row of
+ * SLIMGPU_ModelEvaluateAt: on an eval set made by SLIMGPU_EvalSetCreateAt, the figures of its largest
+ * cutoff over its users. */
 int32_t SLIMGPU_ModelEvaluate(slimgpu_evalset_t *es, const slimgpu_model_t *model,
                               double *metrics, int32_t *nvalid);
+
+/* Several list lengths and a subset of the users from ONE scoring pass.  The scorer's order is total
+ * (score descending, then discovery order), so the list of length c is the first c ranks of a longer
+ * list, and a user's hits are walked once in rank order: the float additions behind cutoff k are a
+ * prefix of those behind cutoff k + 1.  Users are scored independently of each other.  Hence the
+ * contract: row k of SLIMGPU_ModelEvaluateAt equals, bit for bit, SLIMGPU_ModelEvaluate on an eval set
+ * created with nrcmds = cutoffs[k] over a matrix and a test set that hold exactly the selected users'
+ * rows, in list order.  SLIMGPU_EvalSetCreate(.., nrcmds, ..) is SLIMGPU_EvalSetCreateAt(.., 1, &nrcmds,
+ * 0, NULL, ..).  A malformed list -- unsorted, repeated, out of range, more than SLIMGPU_MAX_CUTOFFS
+ * cutoffs, a cutoff of 0 or 129 -- is SLIM_ERROR_INPUT with a SLIMGPU_LastError text.  From the second
+ * evaluation on: no device allocation, nothing host to device, at most 8 + 32 * ncutoffs bytes device to
+ * host.  In slimgpu_eval_stats_t, w_rows_read and w_bytes count the selected users only; path follows
+ * the largest cutoff (1 up to 64, 2 above). */
+/* Like SLIMGPU_EvalSetCreate, for `ncutoffs` list lengths (strictly ascending, 1 <= c <= 128,
+ * 1 <= ncutoffs <= SLIMGPU_MAX_CUTOFFS) and, when users != NULL, for the `nusers` listed users only
+ * (strictly ascending ids in [0, min(mat rows, test rows)), nusers >= 1; users == NULL needs
+ * nusers == 0 and means every user).  Lists are copied; staged once, like the test rows. */
+slimgpu_evalset_t *SLIMGPU_EvalSetCreateAt(slimgpu_matrix_t *mat, slim_t *tsthandle,
+                                           const int32_t *fmarker, int32_t fm_ncols,
+                                           int32_t ncutoffs, const int32_t *cutoffs,
+                                           int32_t nusers, const int32_t *users, int32_t *r_status);
+/* metrics[k*4 .. +4) = {HR, HR_head, HR_tail, ARHR}, nvalid[k*3 .. +3) for cutoff k, from ONE scoring
+ * pass.  ncutoffs must equal the eval set's (SLIM_ERROR_INPUT otherwise). */
+int32_t SLIMGPU_ModelEvaluateAt(slimgpu_evalset_t *es, const slimgpu_model_t *model,
+                                int32_t ncutoffs, double *metrics, int32_t *nvalid);
+/* Option slot of Py_SLIM_Mselect (and slim_mselect -evalstride=K): with K > 1 the grid evaluates users
+ * 0, K, 2K, ... only; -1 or 1: every user.  Needs the evaluation in HBM: with ADMM, several GPUs, nrcmds above 128,
+ * SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0 or a matrix whose duplicates were merged the call fails
+ * with SLIM_ERROR_INPUT before the first solve. */
+enum { SLIM_OPTION_GPU_EVALSTRIDE = 22 };
 /* Top-N of every row of the resident matrix through a resident model: only the lists come down.
  * Bit-identical to SLIMGPU_ModelPredict on the host handle of the same rows. */
 int32_t SLIMGPU_MatrixPredict(int32_t nrcmds, const slimgpu_model_t *model,

@@ -13,6 +13,13 @@ and checks that both give the same figures.  Writes the per-pair table, the tota
 w_bytes / kernel_ms against the 8 TB/s HBM peak to --out.
 
   python scripts/grid_eval.py [--workload c5] [--scale 1.0] [--pairs 0] [--budget-s 900] [--out FILE]
+                              [--stride 1,10,100] [--cutoffs 5,10,20]
+
+--stride: after the grid, the last model evaluated on every K-th user for each K given (an eval set with a
+user list, SLIMGPU_EvalSetCreateAt): seconds, kernel time and w_bytes per K.  --cutoffs: the last model
+evaluated at these list lengths in ONE pass (SLIMGPU_ModelEvaluateAt), against one pass per length; the
+rows of the one pass must equal the single passes.  With SLIM_AMD_LIB pointing at a build from before these
+entry points (an A / B run against it) the grid part still runs; --stride and --cutoffs need the new build.
 
 --pairs 0 (default): the short grid -- the cold pair, three l2 steps and one l1 change; N > 0: the first
 N pairs of the file; -1: all of them (each warm-started from the one before it in the list).  The run stops adding pairs when --budget-s is used up and says so.
@@ -39,6 +46,25 @@ def head_tail(pop, nnz):
     return fm
 
 
+def make_evaluator(mat, T, fm, nrcmds=10, cutoffs=None, users=None):
+    """mat.evaluator(); on a build without SLIMGPU_EvalSetCreateAt (SLIM_AMD_LIB, A / B runs): the
+    one-length, every-user eval set through SLIMGPU_EvalSetCreate."""
+    import numpy as np
+    from slim_amd import _lib as _l
+    from slim_amd.engine import Evaluator, _wrap_rows
+    lib = mat._lib
+    if hasattr(lib, "SLIMGPU_EvalSetCreateAt"):
+        return mat.evaluator(T, nrcmds=nrcmds, fmarker=fm, cutoffs=cutoffs, users=users)
+    assert cutoffs is None and users is None, "this build of the library has no SLIMGPU_EvalSetCreateAt"
+    fm = np.ascontiguousarray(fm, dtype=np.int32)
+    ht = _wrap_rows(lib, T)
+    st = C.c_int32(0)
+    h = lib.SLIMGPU_EvalSetCreate(mat.handle, ht, fm, fm.size, int(nrcmds), C.byref(st))
+    lib.Py_csr_free(ht)
+    assert h, _l.last_error()
+    return Evaluator(lib, h, mat, (int(nrcmds),))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c5")
@@ -48,6 +74,8 @@ def main():
     ap.add_argument("--nrcmds", type=int, default=10)
     ap.add_argument("--budget-s", type=float, default=900.0)
     ap.add_argument("--no-a", action="store_true", help="skip path A (no host copy of the training rows)")
+    ap.add_argument("--stride", default="", help="comma-separated strides K: the last model on every K-th user")
+    ap.add_argument("--cutoffs", default="", help="comma-separated list lengths: one pass against one pass each")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_eval_c5.txt"))
     args = ap.parse_args()
     import numpy as np
@@ -98,7 +126,7 @@ def main():
                                         keepalive=(trn_ptr, trn_ind), device=0)
     lib = mat._lib
     t0 = time.time()
-    ev = mat.evaluator(T, nrcmds=args.nrcmds, fmarker=fm)
+    ev = make_evaluator(mat, T, fm, nrcmds=args.nrcmds)
     say("# eval set staged once: %.2f s" % (time.time() - t0))
     hr = ht = None
     if not args.no_a:
@@ -177,6 +205,40 @@ def main():
         say("# scorer: %.1f GB of model rows streamed in %.1f ms of kernel = %.3f TB/s, %.1f %% of the %.0f TB/s HBM peak"
             % (wb / 1e9, km, wb / km / 1e9, 100.0 * wb / km / 1e6 / HBM_PEAK_GBS, HBM_PEAK_GBS / 1e3))
         say("# evaluation is %.0f %% of learn + evaluate (B)" % (100.0 * B / (L + B)))
+    def timed(e, many):
+        t0 = time.time()
+        got = e.evaluate_at(prev) if many else [e.evaluate(prev)]
+        return time.time() - t0, got, e.stats()
+
+    strides = [int(v) for v in args.stride.split(",") if v]
+    if strides and prev is not None:
+        say("# the last model on every K-th user, nrcmds %d (time should follow w_GB)" % args.nrcmds)
+        say("# %-6s %10s | %8s %9s %9s %7s | %s" % ("K", "users", "eval_s", "kernel_ms", "w_GB", "TB/s", "hr arhr nvalid"))
+        for K in strides:
+            users = None if K == 1 else np.arange(0, nrows, K, dtype=np.int32)
+            e = make_evaluator(mat, T, fm, nrcmds=args.nrcmds, users=users)
+            s, got, es = timed(e, False)
+            e.close()
+            say("  %-6d %10d | %8.3f %9.1f %9.1f %7.3f | %.4f %.4f %d"
+                % (K, nrows if users is None else users.size, s, es["kernel_ms"], es["w_bytes"] / 1e9,
+                   es["w_bytes"] / max(es["kernel_ms"], 1e-9) / 1e9, got[0]["hr"], got[0]["arhr"], got[0]["nvalid"]))
+    cutoffs = [int(v) for v in args.cutoffs.split(",") if v]
+    if cutoffs and prev is not None:
+        e = make_evaluator(mat, T, fm, cutoffs=cutoffs)
+        s_one, rows_one, es = timed(e, True)
+        e.close()
+        say("# cutoffs %s in one pass: %.3f s (kernel %.1f ms, d2h %d bytes)" % (cutoffs, s_one, es["kernel_ms"], es["d2h_bytes"]))
+        s_sum = 0.0
+        for c, row in zip(cutoffs, rows_one):
+            e = make_evaluator(mat, T, fm, nrcmds=c)
+            s, got, es = timed(e, False)
+            e.close()
+            s_sum += s
+            same = all(got[0][k] == row[k] for k in got[0])
+            say("#   nrcmds %3d alone: %.3f s (kernel %.1f ms)  hr %.4f arhr %.4f  %s" %
+                (c, s, es["kernel_ms"], row["hr"], row["arhr"], "equal to its row of the one pass" if same else "DIFFERS"))
+            assert same, (got[0], row)
+        say("# one pass %.3f s against %.3f s for %d single passes: %.2fx" % (s_one, s_sum, len(cutoffs), s_sum / s_one))
     say("# whole run: %.1f s" % (time.time() - t_start))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

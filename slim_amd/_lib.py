@@ -139,6 +139,16 @@ _EVAL_SIGNATURES = {
 
 EVAL_SYMBOLS = tuple(_EVAL_SIGNATURES)
 
+# ... at several list lengths and on a subset of the users, from one scoring pass
+_EVAL_AT_SIGNATURES = {
+    "SLIMGPU_EvalSetCreateAt": (C.c_void_p, [C.c_void_p, C.c_void_p, i32_1d, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "SLIMGPU_ModelEvaluateAt": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, f64_1d, i32_1d]),
+}
+
+EVAL_AT_SYMBOLS = tuple(_EVAL_AT_SIGNATURES)
+MAX_CUTOFFS = 8     # SLIMGPU_MAX_CUTOFFS
+
 _lib = None
 
 
@@ -152,7 +162,8 @@ def load():
             "slim_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for SLIM training." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()):
+    for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
+                              list(_EVAL_AT_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

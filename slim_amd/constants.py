@@ -49,6 +49,7 @@ class Opt(enum.IntEnum):
     GPU_NGPUS = 19         # SLIM_Learn & co: shard the item columns over this many GPUs (default 1)
     GPU_SHARDCOUNT = 20    # SLIMGPU_Learn*: solve one shard of the requested columns ...
     GPU_SHARDINDEX = 21    # ... granules INDEX, INDEX + COUNT, ... of the cost-ordered work list
+    GPU_EVALSTRIDE = 22    # Py_SLIM_Mselect: evaluate users 0, K, 2K, ... only (slim_gpu_eval.h; default: all)
 
 
 for _o in Opt:

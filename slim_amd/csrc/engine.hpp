@@ -144,11 +144,15 @@ struct DeviceCsrView {
 int32_t matrix_csr_view(const slimgpu_matrix_t* m, DeviceCsrView* out);
 
 // topn.hip: a resident model scored and evaluated against the resident matrix (slim_gpu_eval.h:
-// SLIMGPU_EvalSetCreate & co).  Per evaluation only the four sums and three counts come down.
+// SLIMGPU_EvalSetCreateAt & co).  Per evaluation only the four sums and three counts of every list length
+// come down.  cutoffs[ncutoffs]: list lengths, ascending; users[nusers]: the evaluated users, ascending
+// (nullptr and 0: every user).  model_evaluate fills out[0 .. ncutoffs), which must be the eval set's count.
 slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
-                                  int32_t fm_ncols, int32_t nrcmds, int32_t* status);
+                                  int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
+                                  const int32_t* users, int32_t* status);
 void evalset_free(slimgpu_evalset_t* es);
-int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, EvalResult* out);
+int32_t evalset_cutoffs(const slimgpu_evalset_t* es);
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out);
 int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
                        float* scores);
 slimgpu_eval_stats_t& last_eval_stats();

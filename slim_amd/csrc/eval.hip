@@ -2,7 +2,8 @@
 // as HIP kernels:
 //   * hit counting, HR / ARHR and the head / tail split of the leave-k-out protocol
 //     (/root/reference/src/programs/slim_predict.c:181-236, slim_mselect.c:122-187,
-//     src/libslim/pyapi.c:309-366), one user per lane, then ONE wavefront adding the users'
+//     src/libslim/pyapi.c:309-366), one user per lane (every list length of an evaluation from one
+//     walk over the list, eval_terms.hpp), then ONE wavefront per list length adding the users'
 //     terms in user order with the reference's own arithmetic (float accumulators fed with
 //     double terms, pyapi.c:223-230) -- so the four figures are the host loop's, bit for bit;
 //   * the 1-vs-k protocol (src/libslim/predict.c:77-133, pyapi.c:483-528): every user ranks
@@ -29,59 +30,60 @@ namespace {
 
 // ---- HR / ARHR -------------------------------------------------------------------------
 
-__global__ void k_user_terms(int32_t nusers, int32_t nrcmds, const int32_t* __restrict__ lists,
-                             const int32_t* __restrict__ counts,
+// One lane per position: the test row once (what does not depend on the cutoff), then ONE walk over the
+// list in rank order; the record of a cutoff is formed when the walk reaches its rank (or the end of the
+// list), from the sums so far -- the prefix argument of eval_terms.hpp.
+__global__ void k_user_terms(int32_t nsel, const int32_t* __restrict__ users, int32_t nrcmds, const Cutoffs cut,
+                             const int32_t* __restrict__ lists, const int32_t* __restrict__ counts,
                              const int64_t* __restrict__ tptr, const int32_t* __restrict__ tind,
                              const int32_t* __restrict__ fmarker, int32_t fm_ncols,
                              UserTerms* __restrict__ out) {
-  for (int32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < nusers; u += gridDim.x * blockDim.x) {
-    UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
+  for (int32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nsel; q += gridDim.x * blockDim.x) {
+    const int32_t u = users ? users[q] : q;
     const int64_t t0 = tptr[u], t1 = tptr[u + 1];
+    int ntrue0 = 0, ntrue1 = 0, flags = 0;
+    float ideal = 0.0f;
     if (t1 - t0 >= 1) {
-      int ntrue[2] = {0, 0}, nhits[3] = {0, 0, 0};
-      float gain = 0.0f, ideal = 0.0f;
-      t.flags = 1;
+      flags = 1;
       for (int64_t z = t0; z < t1; ++z) {
         const int32_t it = tind[z];
         const int cls = (it >= 0 && it < fm_ncols) ? fmarker[it] : 1;
-        ++ntrue[cls];
-        t.flags |= cls ? 4 : 2;
+        if (cls) ++ntrue1; else ++ntrue0;
+        flags |= cls ? 4 : 2;
         ideal = (float)((double)ideal + 1.0 / (1.0 + double(z - t0)));
       }
-      const int n = counts[u];
-      for (int r = 0; r < n; ++r) {
-        const int32_t id = lists[(int64_t)u * nrcmds + r];
+    }
+    HitWalk w;
+    const int n = flags ? counts[q] : 0;
+    int r = 0;
+    const unsigned long long cuts = cut.packed();
+    for (int k = 0; k < cut.n; ++k) {
+      // the last record takes the whole list, whatever its row length nrcmds (SLIMGPU_Evaluate sets no upper
+      // bound on it); the lengths before it come from an eval set and are at most 128
+      const int end = min(n, k == cut.n - 1 ? nrcmds : Cutoffs::at(cuts, k));
+      for (; r < end; ++r) {
+        const int32_t id = lists[(int64_t)q * nrcmds + r];
         bool hit = false;
         for (int64_t z = t0; z < t1 && !hit; ++z) hit = tind[z] == id;
-        if (hit) {
-          const int cls = (id >= 0 && id < fm_ncols) ? fmarker[id] : 1;
-          ++nhits[cls];
-          ++nhits[2];
-          gain = (float)((double)gain + 1.0 / (1.0 + r));
-        }
+        if (hit) w.hit(r, (id >= 0 && id < fm_ncols) ? fmarker[id] : 1);
       }
-      t.hr_head = nhits[0] > 0 ? 1.0 * nhits[0] / ntrue[0] : 0.0;
-      t.hr_tail = nhits[1] > 0 ? 1.0 * nhits[1] / ntrue[1] : 0.0;
-      t.hr_all = 1.0 * nhits[2] / double(t1 - t0);
-      t.arhr = gain / ideal;
+      out[(int64_t)k * nsel + q] = w.terms(ntrue0, ntrue1, t1 - t0, ideal, flags);
     }
-    out[u] = t;
   }
 }
 
-// one wavefront: 64 users' terms per coalesced load, added by lane order = user order
-__global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nusers,
-                                                          const UserTerms* __restrict__ terms,
-                                                          float* __restrict__ out_f,
-                                                          int32_t* __restrict__ out_n) {
+// one wavefront per cutoff: 64 positions' terms per coalesced load, added by lane order = position order
+__global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nsel, const UserTerms* __restrict__ terms,
+                                                          EvalSums* __restrict__ out) {
   const int lane = threadIdx.x;
+  terms += (int64_t)blockIdx.x * nsel;
   float hr_all = 0, hr_head = 0, hr_tail = 0, arhr = 0;
   int nvalid = 0, nhead = 0, ntail = 0;
-  for (int32_t b = 0; b < nusers; b += 64) {
+  for (int32_t b = 0; b < nsel; b += 64) {
     const int32_t u = b + lane;
     UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
-    if (u < nusers) t = terms[u];
-    const int cnt = nusers - b < 64 ? nusers - b : 64;
+    if (u < nsel) t = terms[u];
+    const int cnt = nsel - b < 64 ? nsel - b : 64;
     for (int k = 0; k < cnt; ++k) {
       const int fl = __shfl(t.flags, k);
       if (!(fl & 1)) continue;
@@ -97,8 +99,10 @@ __global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nusers,
     }
   }
   if (lane == 0) {
-    out_f[0] = hr_all; out_f[1] = hr_head; out_f[2] = hr_tail; out_f[3] = arhr;
-    out_n[0] = nvalid; out_n[1] = nhead; out_n[2] = ntail;
+    EvalSums& o = out[blockIdx.x];
+    o.f[0] = hr_all; o.f[1] = hr_head; o.f[2] = hr_tail; o.f[3] = arhr;
+    o.n[0] = nvalid; o.n[1] = nhead; o.n[2] = ntail;
+    o.pad = 0;
   }
 }
 
@@ -224,18 +228,18 @@ int32_t fail(const char* who, const HipFail& e) {
 
 }  // namespace
 
-void launch_user_terms(hipStream_t stream, int num_cus, int32_t nusers, int32_t nrcmds, const int32_t* lists,
-                       const int32_t* counts, const int64_t* tptr, const int32_t* tind, const int32_t* fmarker,
-                       int32_t fm_ncols, UserTerms* terms) {
-  const int blocks = std::max(1, std::min((nusers + 255) / 256, num_cus * 8));
-  hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, stream, nusers, nrcmds, lists, counts, tptr,
-                     tind, fmarker, fm_ncols, terms);
+void launch_user_terms(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* users, int32_t nrcmds,
+                       const Cutoffs& cut, const int32_t* lists, const int32_t* counts, const int64_t* tptr,
+                       const int32_t* tind, const int32_t* fmarker, int32_t fm_ncols, UserTerms* terms) {
+  const int blocks = std::max(1, std::min((nsel + 255) / 256, num_cus * 8));
+  hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, stream, nsel, users, nrcmds, cut, lists, counts,
+                     tptr, tind, fmarker, fm_ncols, terms);
   HIP_TRY(hipGetLastError());
 }
 
-void launch_sum_in_user_order(hipStream_t stream, int32_t nusers, const UserTerms* terms, float* out_f,
-                              int32_t* out_n) {
-  hipLaunchKernelGGL(k_sum_in_user_order, dim3(1), dim3(64), 0, stream, nusers, terms, out_f, out_n);
+void launch_sum_in_user_order(hipStream_t stream, int32_t nsel, int32_t ncut, const UserTerms* terms,
+                              EvalSums* out) {
+  hipLaunchKernelGGL(k_sum_in_user_order, dim3(ncut), dim3(64), 0, stream, nsel, terms, out);
   HIP_TRY(hipGetLastError());
 }
 
@@ -253,23 +257,24 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
     (void)hipGetLastError();
     const int64_t tnnz = tst->rowptr[nusers];
     DeviceBuffer<int32_t> d_lists((size_t)nusers * nrcmds), d_counts((size_t)nusers), d_tind((size_t)tnnz),
-        d_fm((size_t)std::max(fm_ncols, 1)), d_n(3);
+        d_fm((size_t)std::max(fm_ncols, 1));
     DeviceBuffer<int64_t> d_tptr((size_t)nusers + 1);
     DeviceBuffer<UserTerms> d_terms((size_t)nusers);
-    DeviceBuffer<float> d_f(4);
+    DeviceBuffer<EvalSums> d_sums(1);
     upload(d_lists, lists, (size_t)nusers * nrcmds);
     upload(d_counts, counts, (size_t)nusers);
     static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
     upload(d_tptr, reinterpret_cast<const int64_t*>(tst->rowptr), (size_t)nusers + 1);
     upload(d_tind, tst->rowind, (size_t)tnnz);
     upload(d_fm, fmarker, (size_t)fm_ncols);
-    launch_user_terms(nullptr, cu_count(), nusers, nrcmds, d_lists.get(), d_counts.get(), d_tptr.get(),
-                      d_tind.get(), d_fm.get(), fm_ncols, d_terms.get());
-    launch_sum_in_user_order(nullptr, nusers, d_terms.get(), d_f.get(), d_n.get());
-    float f[4];
-    int32_t n[3];
-    HIP_TRY(hipMemcpy(f, d_f.get(), sizeof(f), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(n, d_n.get(), sizeof(n), hipMemcpyDeviceToHost));
+    // every user, one cutoff: the lists are as long as the caller made them
+    launch_user_terms(nullptr, cu_count(), nusers, nullptr, nrcmds, one_cutoff(nrcmds), d_lists.get(),
+                      d_counts.get(), d_tptr.get(), d_tind.get(), d_fm.get(), fm_ncols, d_terms.get());
+    launch_sum_in_user_order(nullptr, nusers, 1, d_terms.get(), d_sums.get());
+    EvalSums h;
+    HIP_TRY(hipMemcpy(&h, d_sums.get(), sizeof(h), hipMemcpyDeviceToHost));
+    const float* f = h.f;
+    const int32_t* n = h.n;
     out->nvalid = n[0];
     out->nvalid_head = n[1];
     out->nvalid_tail = n[2];

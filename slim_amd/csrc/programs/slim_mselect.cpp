@@ -10,26 +10,29 @@ int main(int argc, char** argv) {
       {"ifmt", true},    {"binarize", false}, {"optTol", true},  {"niters", true},
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
-      {"help", false}};
+      {"evalstride", true}, {"help", false}};
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() != 3) {
     std::printf("\n Usage: slim_mselect [options] train-file test-file l12-file\n"
                 "   -ifmt=csr|csrnv|cluto|ijv  -binarize  -optTol=f  -niters=i  -nnbrs=i  -simtype=s\n"
                 "   -nrcmds=i  -nthreads=i  -dbglvl=i  -nomodels (do not write '<l1 l2>.model' files)\n"
-                "   -ngpus=i   (engine extension: R replicated on i GPUs, every model sharded over them)\n\n");
+                "   -ngpus=i   (engine extension: R replicated on i GPUs, every model sharded over them)\n"
+                "   -evalstride=i  (engine extension: evaluate users 0, i, 2i, ... only; needs the evaluation in HBM)\n\n");
     return 0;
   }
   const Fmt fmt = parse_fmt(a.str("ifmt", "csr"));
   for (const auto& p : a.pos)
     if (!file_exists(p)) die("Input file " + p + " does not exist.");
   const int nrcmds = a.integer("nrcmds", 10);
+  const int stride = a.integer("evalstride", 1);
+  if (stride < 1) die("Invalid -evalstride of " + a.str("evalstride", "") + ".");
   Csr trn = read_matrix(a.pos[0], fmt), tst = read_matrix(a.pos[1], fmt);
   if (a.has("binarize")) trn.has_val = false;
   const std::string sim = a.str("simtype", "cos");
   banner();
   std::printf("  trnfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[0].c_str(), trn.nrows, trn.ncols, trn.nnz());
   std::printf("  tstfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[1].c_str(), tst.nrows, tst.ncols, tst.nnz());
-  std::printf("  l12file: %s\n\nEstimating & evaluating models...\n\n", a.pos[2].c_str());
+  std::printf("  l12file: %s\n", a.pos[2].c_str());
 
   int32_t io[SLIM_NOPTIONS];
   double dopt[SLIM_NOPTIONS];
@@ -72,11 +75,24 @@ int main(int argc, char** argv) {
   // brings down its figures only (SLIM_GPU_EVAL_RESIDENT=0, or a refusal: lists through the host)
   const char* evr_env = std::getenv("SLIM_GPU_EVAL_RESIDENT");
   slimgpu_evalset_t* evalset = nullptr;
+  const int32_t nall = std::min(trn.nrows, tst.nrows);
+  std::vector<int32_t> sel;  // -evalstride: the evaluated users
+  if (stride > 1)
+    for (int64_t u = 0; u < nall; u += stride) sel.push_back((int32_t)u);
   if (resident && nrcmds >= 1 && nrcmds <= 128 && !(evr_env && std::atoi(evr_env) == 0)) {
     slim_t* th = to_handle(tst);
-    evalset = SLIMGPU_EvalSetCreate(R, th, fmarker, ncols, nrcmds, &status);
+    const int32_t cutoff = nrcmds;
+    evalset = SLIMGPU_EvalSetCreateAt(R, th, fmarker, ncols, 1, &cutoff, (int32_t)sel.size(),
+                                      sel.empty() ? nullptr : sel.data(), &status);
     Py_csr_free(th);
   }
+  // the host loop has no subset form: a stride without the evaluation in HBM fails before the first solve
+  if (stride > 1 && !evalset)
+    die(std::string("-evalstride needs the evaluation in HBM (one GPU, 1 <= nrcmds <= 128, SLIM_GPU_RESIDENT and "
+                    "SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ") +
+        (nrcmds < 1 || nrcmds > 128 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
+  if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
+  std::printf("\nEstimating & evaluating models...\n\n");
   double best_hr = 0, best_ar = 0, bh_l1 = 0, bh_l2 = 0, ba_l1 = 0, ba_l2 = 0;
   while (std::fgets(line, sizeof line, lf)) {
     double l1, l2;
@@ -118,6 +134,7 @@ int main(int argc, char** argv) {
     double em[4];
     int32_t env[3];
     const bool evaluated = evalset && SLIMGPU_ModelEvaluate(evalset, dmodel, em, env) == SLIM_OK;
+    if (!evaluated && stride > 1) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
     if (evaluated) {
       e.hr = em[0]; e.hr_head = em[1]; e.hr_tail = em[2]; e.arhr = em[3];
       e.nvalid = env[0]; e.nvalid_head = env[1]; e.nvalid_tail = env[2];

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "engine.hpp"
@@ -190,6 +191,12 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
     return SLIM_ERROR_INPUT;
   }
   const bool admm = base.algo == SLIM_ALGO_ADMM;
+  // evaluate every stride-th user only (slot 22; -1 or 1: every user)
+  const int32_t stride = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALSTRIDE] == -1) ? 1 : ioptions[SLIM_OPTION_GPU_EVALSTRIDE];
+  if (stride < 1) {
+    set_error("Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALSTRIDE must be at least 1");
+    return SLIM_ERROR_INPUT;
+  }
 
   // R goes to HBM once for the whole grid (the reference re-runs
   // CreateTrainingMatrix inside every SLIM_Learn call, pyapi.c:295-297)
@@ -207,6 +214,39 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   const int32_t ncols = trn_ncols > tst_ncols ? trn_ncols : tst_ncols;  // pyapi.c:255-257
   int32_t* fmarker = head_tail_split(trn->nrows, ncols, trn->rowptr, trn->rowind);
 
+  // One GPU, CD: the models of the grid stay in HBM (engine.hpp: learn_resident) -- each pair is
+  // warm-started from the previous one without an upload and scored where it lies; only its nnz is
+  // printed, so nothing of it ever crosses PCIe.  SLIM_GPU_RESIDENT=0: host models as before.
+  const char* res_env = std::getenv("SLIM_GPU_RESIDENT");
+  const bool resident = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 && nrcmds <= 128 &&
+                        !(res_env && std::atoi(res_env) == 0);
+  // ... and evaluated where they lie: the test rows and the marker go to HBM once (evalset_create), a
+  // pair brings down its four sums and three counts.  SLIM_GPU_EVAL_RESIDENT=0, or a refusal (a matrix
+  // whose repeated pairs were merged), keeps the lists-through-the-host path below -- which has no
+  // subset form: a stride needs the eval set, and the call fails here, before the first solve, without it.
+  const char* evr_env = std::getenv("SLIM_GPU_EVAL_RESIDENT");
+  slimgpu_evalset_t* evalset = nullptr;
+  const int32_t nall = std::min(trn->nrows, tst->nrows);
+  std::vector<int32_t> sel;
+  if (stride > 1)
+    for (int64_t u = 0; u < nall; u += stride) sel.push_back((int32_t)u);
+  if (resident && !(evr_env && std::atoi(evr_env) == 0)) {
+    evalset = evalset_create(mat, tst, fmarker, ncols, 1, &nrcmds, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
+                             &status);
+    if (!evalset && stride == 1) set_error("");
+  }
+  if (stride > 1 && !evalset) {
+    const std::string why = SLIMGPU_LastError();
+    set_error("Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALSTRIDE needs the evaluation in HBM (cd on one GPU, "
+              "1 <= nrcmds <= 128, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without "
+              "merged pairs)" +
+              (nrcmds < 1 || nrcmds > 128 ? ": nrcmds is " + std::to_string(nrcmds) : std::string()) +
+              (why.empty() ? std::string() : ": " + why));
+    std::free(fmarker);
+    matrix_free(mat);
+    return SLIM_ERROR_INPUT;
+  }
+
   std::printf("------------------------------------------------------------------\n");
   std::printf("SLIM, version %s (MI355X engine)\n", SLIM_VERSION);
   std::printf("------------------------------------------------------------------\n");
@@ -215,26 +255,12 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   std::printf("  tst matrix, nrows: %d, ncols: %d, nnz: %zd\n", tst->nrows, tst_ncols,
               tst->rowptr[tst->nrows]);
   std::printf("  optTol: %.2le, niters: %d\n", base.optTol, base.maxniters);
+  if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
   std::printf("\nEstimating & evaluating models...\n\n");
 
   *bestHRHR = *bestARHR = *bestHRAR = *bestARAR = 0.0;
   slim_csr_t* model = nullptr;
-  // One GPU, CD: the models of the grid stay in HBM (engine.hpp: learn_resident) -- each pair is
-  // warm-started from the previous one without an upload and scored where it lies; only its nnz is
-  // printed, so nothing of it ever crosses PCIe.  SLIM_GPU_RESIDENT=0: host models as before.
-  const char* res_env = std::getenv("SLIM_GPU_RESIDENT");
-  const bool resident = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 && nrcmds <= 128 &&
-                        !(res_env && std::atoi(res_env) == 0);
   slimgpu_model* dmodel = nullptr;
-  // ... and evaluated where they lie: the test rows and the marker go to HBM once (evalset_create), a
-  // pair brings down its four sums and three counts.  SLIM_GPU_EVAL_RESIDENT=0, or a refusal (a matrix
-  // whose repeated pairs were merged), keeps the lists-through-the-host path below.
-  const char* evr_env = std::getenv("SLIM_GPU_EVAL_RESIDENT");
-  slimgpu_evalset_t* evalset = nullptr;
-  if (resident && !(evr_env && std::atoi(evr_env) == 0)) {
-    evalset = evalset_create(mat, tst, fmarker, ncols, nrcmds, &status);
-    if (!evalset) set_error("");
-  }
   int32_t rc = SLIM_OK;
   for (int32_t a = 0; a < nl1 && rc == SLIM_OK; ++a) {
     for (int32_t b = 0; b < nl2; ++b) {
@@ -264,7 +290,11 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
           break;
         }
         model_nnz_now = (ssize_t)model_nnz(dmodel);
-        evaluated = evalset && model_evaluate(evalset, dmodel, &ev) == SLIM_OK;
+        evaluated = evalset && model_evaluate(evalset, dmodel, 1, &ev) == SLIM_OK;
+        if (!evaluated && stride > 1) {  // (no silent evaluation of everybody)
+          rc = SLIM_ERROR;
+          break;
+        }
         DeviceRowView wv;
         if (!evaluated) {
           host_lists();
@@ -548,13 +578,20 @@ int32_t SLIMGPU_ModelPredict(int32_t nrcmds, const slimgpu_model_t* model, slim_
   return predict_device_view(v, as_csr(trnhandle), nrcmds, output, scores, nullptr);
 }
 
-slimgpu_evalset_t* SLIMGPU_EvalSetCreate(slimgpu_matrix_t* mat, slim_t* tsthandle, const int32_t* fmarker,
-                                         int32_t fm_ncols, int32_t nrcmds, int32_t* r_status) {
+slimgpu_evalset_t* SLIMGPU_EvalSetCreateAt(slimgpu_matrix_t* mat, slim_t* tsthandle, const int32_t* fmarker,
+                                           int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs,
+                                           int32_t nusers, const int32_t* users, int32_t* r_status) {
   set_error("");
   int32_t status = SLIM_ERROR;
-  slimgpu_evalset_t* es = evalset_create(mat, as_csr(tsthandle), fmarker, fm_ncols, nrcmds, &status);
+  slimgpu_evalset_t* es =
+      evalset_create(mat, as_csr(tsthandle), fmarker, fm_ncols, ncutoffs, cutoffs, nusers, users, &status);
   if (r_status) *r_status = status;
   return es;
+}
+
+slimgpu_evalset_t* SLIMGPU_EvalSetCreate(slimgpu_matrix_t* mat, slim_t* tsthandle, const int32_t* fmarker,
+                                         int32_t fm_ncols, int32_t nrcmds, int32_t* r_status) {
+  return SLIMGPU_EvalSetCreateAt(mat, tsthandle, fmarker, fm_ncols, 1, &nrcmds, 0, nullptr, r_status);
 }
 
 void SLIMGPU_EvalSetFree(slimgpu_evalset_t** es) {
@@ -563,15 +600,38 @@ void SLIMGPU_EvalSetFree(slimgpu_evalset_t** es) {
   *es = nullptr;
 }
 
+int32_t SLIMGPU_ModelEvaluateAt(slimgpu_evalset_t* es, const slimgpu_model_t* model, int32_t ncutoffs,
+                                double* metrics, int32_t* nvalid) {
+  set_error("");
+  if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
+  EvalResult ev[SLIMGPU_MAX_CUTOFFS];
+  if (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS) {
+    set_error("SLIMGPU_ModelEvaluateAt: ncutoffs must be the eval set's number of list lengths");
+    return SLIM_ERROR_INPUT;
+  }
+  const int32_t rc = model_evaluate(es, model, ncutoffs, ev);
+  if (rc != SLIM_OK) return rc;
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    double* m = metrics + 4 * k;
+    int32_t* n = nvalid + 3 * k;
+    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
+    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
+  }
+  return SLIM_OK;
+}
+
+// the last row of SLIMGPU_ModelEvaluateAt: the longest lists of the eval set
 int32_t SLIMGPU_ModelEvaluate(slimgpu_evalset_t* es, const slimgpu_model_t* model, double* metrics,
                               int32_t* nvalid) {
   set_error("");
   if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
-  EvalResult ev;
-  const int32_t rc = model_evaluate(es, model, &ev);
+  EvalResult ev[SLIMGPU_MAX_CUTOFFS];
+  const int32_t ncut = std::max(1, evalset_cutoffs(es));
+  const int32_t rc = model_evaluate(es, model, ncut, ev);
   if (rc != SLIM_OK) return rc;
-  metrics[0] = ev.hr; metrics[1] = ev.hr_head; metrics[2] = ev.hr_tail; metrics[3] = ev.arhr;
-  nvalid[0] = ev.nvalid; nvalid[1] = ev.nvalid_head; nvalid[2] = ev.nvalid_tail;
+  const EvalResult& e = ev[ncut - 1];
+  metrics[0] = e.hr; metrics[1] = e.hr_head; metrics[2] = e.hr_tail; metrics[3] = e.arhr;
+  nvalid[0] = e.nvalid; nvalid[1] = e.nvalid_head; nvalid[2] = e.nvalid_tail;
   return SLIM_OK;
 }
 

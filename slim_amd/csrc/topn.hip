@@ -57,14 +57,15 @@ struct ScorerWorkspace {
 struct slimgpu_evalset {
   slimgpu_matrix_t* mat = nullptr;
   int device = 0;
-  int32_t nusers = 0, nrcmds = 0, fm_ncols = 0;
-  int64_t hist_begin = 0;    // offset of user 0's history in the matrix's CSR
-  int64_t hist_entries = 0;  // history entries of users [0, nusers): the model rows one evaluation streams
+  int32_t nsel = 0, fm_ncols = 0;  // positions evaluated: the listed users, or every user
+  bool listed = false;             // d_users holds the user of every position (else position q is user q)
+  slimamd::Cutoffs cut = {};       // list lengths; the lists scored have the last one's
+  int64_t hist_entries = 0;  // history entries of the evaluated users: the model rows one evaluation streams
   int64_t max_hist = 0;      // the longest of those histories
   slimamd::DeviceBuffer<int64_t> d_tptr;
-  slimamd::DeviceBuffer<int32_t> d_tind, d_fm;
-  slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;
-  slimamd::DeviceBuffer<unsigned long long> d_out;  // EvalOut
+  slimamd::DeviceBuffer<int32_t> d_tind, d_fm, d_users;
+  slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;  // [cut.n][nsel]
+  slimamd::DeviceBuffer<unsigned long long> d_out;    // EvalOut
   slimamd::ScorerWorkspace ws;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   ~slimgpu_evalset() {
@@ -82,7 +83,8 @@ constexpr unsigned long long kUntouched = ~0ull;
 constexpr unsigned long long kExcluded = ~0ull - 1ull;
 
 struct TopNArgs {
-  int32_t nusers, nitems_rows, ncols, nrcmds;
+  int32_t nusers, nitems_rows, ncols, nrcmds;  // nusers: positions
+  const int32_t* users = nullptr;  // the user of every position; nullptr: position q is user q
   const int64_t* wptr;
   const int32_t* wind;
   const float* wval;
@@ -109,8 +111,8 @@ __device__ __forceinline__ int64_t uni64(int64_t v) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
-// Control flow is wave-uniform wherever the data allows it: users are strided statically
-// over the wavefronts, loop bounds over history rows and output ranks are scalars, and the
+// Control flow is wave-uniform wherever the data allows it: positions are strided statically
+// over the wavefronts (outputs are indexed by the position, history by its user), loop bounds over history rows and output ranks are scalars, and the
 // only divergent loops are the lane-strided walks and the per-lane list insertion.
 __global__ __launch_bounds__(64) void topn_kernel(const TopNArgs T) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -124,7 +126,8 @@ __global__ __launch_bounds__(64) void topn_kernel(const TopNArgs T) {
   float* score = T.score + (int64_t)blockIdx.x * T.ncols;
   unsigned long long* disc = T.disc + (int64_t)blockIdx.x * T.ncols;
 
-  for (int u = (int)blockIdx.x; u < T.nusers; u += (int)gridDim.x) {
+  for (int q = (int)blockIdx.x; q < T.nusers; q += (int)gridDim.x) {
+    const int u = T.users ? __builtin_amdgcn_readfirstlane(T.users[q]) : q;
     const int64_t h0 = uni64(T.hptr[u]), h1 = uni64(T.hptr[u + 1]);
 
     for (int k = lane; k < T.ncols; k += 64) disc[k] = kUntouched;
@@ -213,14 +216,14 @@ __global__ __launch_bounds__(64) void topn_kernel(const TopNArgs T) {
       const int id = __shfl(my_id, winner);
       if (any) {
         if (lane == 0) {
-          T.out_ids[(int64_t)u * N + r] = id;
-          T.out_scores[(int64_t)u * N + r] = bs;
+          T.out_ids[(int64_t)q * N + r] = id;
+          T.out_scores[(int64_t)q * N + r] = bs;
         }
         if (lane == winner) ++head;
         ++nout;
       }
     }
-    if (lane == 0) T.out_cnt[u] = nout;
+    if (lane == 0) T.out_cnt[q] = nout;
   }
 }
 
@@ -252,7 +255,8 @@ constexpr int kT2MaxN = 64;       // lists live one rank per lane: up to a wavef
 constexpr int kT2MaxCW = 1536;
 
 struct TopN2Args {
-  int32_t nusers, nitems_rows, ncols, nrcmds;
+  int32_t nusers, nitems_rows, ncols, nrcmds;  // nusers: positions pulled from the queue
+  const int32_t* users = nullptr;  // the user of every position; nullptr: position q is user q
   int32_t cw, nchunks;
   uint32_t wlast;    // nnz(W) - 1 (0 for an empty model): clamp for the unconditional loads
   int32_t pos_bits;  // discovery key = history index << pos_bits | position in the row
@@ -267,12 +271,14 @@ struct TopN2Args {
   float* out_scores;
   int32_t* out_cnt;
   int32_t* queue;
-  // fused evaluation (EVAL instantiations only): the test rows, the head / tail marker, one record per user
+  // fused evaluation (EVAL instantiations only): the test rows, the head / tail marker, one record per
+  // cutoff and position (terms[k * nusers + q]); cut.c[cut.n - 1] == nrcmds
   const int64_t* tptr = nullptr;
   const int32_t* tind = nullptr;
   const int32_t* fmarker = nullptr;
   int32_t fm_ncols = 0;
   UserTerms* terms = nullptr;
+  Cutoffs cut = {};
 };
 
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
@@ -336,9 +342,12 @@ __global__ void k_row_split(int32_t nrows, int32_t nchunks, int32_t cw,
 // EVAL: the fused epilogue of the resident evaluation.  Once wavefront 0 has merged the lists, lane t
 // holds rank t; the user's test row sits in LDS (loaded by the whole workgroup into wavefront 0's score
 // chunk, which is free by then; what does not fit is walked from HBM), every lane tests its id against
-// it, one ballot gives the hit mask, and the user's UserTerms record is formed exactly as k_user_terms
-// (eval.hip) forms it -- gain added in rank order, ideal in test-row order, float accumulators fed with
-// double terms.  Lists are written only when an output pointer is given.
+// it, one ballot gives the hit mask, and the user's UserTerms records are formed exactly as k_user_terms
+// (eval.hip) forms them -- gain added in rank order, ideal in test-row order, float accumulators fed with
+// double terms; the set bits are walked once and the record of cutoff k leaves when the walk passes rank
+// cut.c[k] (eval_terms.hpp: the additions behind a cutoff are a prefix of those behind the next one, so
+// every record is the one a separate evaluation with lists of that length forms).  Lists are written only
+// when an output pointer is given.
 template <int NW, typename KeyT, bool EVAL>
 __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
   constexpr KeyT kUnt = ~KeyT(0), kExc = ~KeyT(0) - 1;
@@ -359,8 +368,11 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
   for (;;) {
     if (tid == 0) s_user = atomicAdd(T.queue, 1);
     __syncthreads();
-    const int u = __builtin_amdgcn_readfirstlane(s_user);
+    // a position; the user is looked up once, outputs are indexed by the position (re-read from LDS after
+    // the chunks, so that it does not occupy a scalar register through them)
+    int u = __builtin_amdgcn_readfirstlane(s_user);
     if (u >= T.nusers) break;
+    if (T.users) u = __builtin_amdgcn_readfirstlane(T.users[u]);
     const int64_t h0 = uni64(T.hptr[u]), h1 = uni64(T.hptr[u + 1]);
 
     // this wavefront's N best so far: lane t holds rank t
@@ -522,6 +534,7 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
       tl = (t1 - t0) < (int64_t)CW ? (int)(t1 - t0) : CW;
       for (int z = tid; z < tl; z += 64 * NW) s_test[z] = T.tind[t0 + z];
     }
+    const int q = __builtin_amdgcn_readfirstlane(s_user);  // (unchanged until the barrier that ends this user)
     if (wave == 0) {
       for (int w = 1; w < NW; ++w) {
         const int cw_ = __builtin_amdgcn_readfirstlane(m_cnt[w]);
@@ -534,20 +547,22 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
       }
       if (!EVAL || T.out_ids != nullptr) {
         if (lane < count) {
-          T.out_ids[(int64_t)u * N + lane] = lid;
-          T.out_scores[(int64_t)u * N + lane] = ls;
+          T.out_ids[(int64_t)q * N + lane] = lid;
+          T.out_scores[(int64_t)q * N + lane] = ls;
         }
-        if (lane == 0) T.out_cnt[u] = count;
+        if (lane == 0) T.out_cnt[q] = count;
       }
     }
     if constexpr (EVAL) {
       __syncthreads();  // the test row is in LDS
       if (wave == 0) {
-        UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
+        // what does not depend on the cutoff, once: the test row's classes, ideal, the hit mask
         const int64_t tlen = t1 - t0;
+        int ntrue0 = 0, ntrue1 = 0, flags = 0;
+        float ideal = 0.0f;
+        unsigned long long mask = 0;
         if (tlen >= 1) {
-          int ntrue0 = 0, ntrue1 = 0, flags = 1;
-          float ideal = 0.0f;
+          flags = 1;
           bool hit = false;
           for (int64_t z = 0; z < tlen; ++z) {
             const int it = z < tl ? s_test[z] : T.tind[t0 + z];
@@ -557,25 +572,22 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
             ideal = (float)((double)ideal + 1.0 / (1.0 + double(z)));
             hit = hit || it == lid;
           }
-          unsigned long long mask = __ballot(hit && lane < count);
-          int nh0 = 0, nh1 = 0, nh2 = 0;
-          float gain = 0.0f;
-          while (mask) {  // set bits = ranks that hit, walked in rank order
+          mask = __ballot(hit && lane < count);  // set bits = ranks that hit
+        }
+        // one walk in rank order; cutoff k's record is the sums of the ranks below cut.c[k]
+        HitWalk w;
+        const unsigned long long cuts = T.cut.packed();
+        for (int k = 0; k < T.cut.n; ++k) {
+          const int c = Cutoffs::at(cuts, k);
+          while (mask && __builtin_ctzll(mask) < c) {
             const int r = __builtin_ctzll(mask);
             mask &= mask - 1;
             const int id = __builtin_amdgcn_readlane(lid, r);
-            const int cls = (id >= 0 && id < T.fm_ncols) ? T.fmarker[id] : 1;
-            if (cls) ++nh1; else ++nh0;
-            ++nh2;
-            gain = (float)((double)gain + 1.0 / (1.0 + r));
+            w.hit(r, (id >= 0 && id < T.fm_ncols) ? T.fmarker[id] : 1);
           }
-          t.hr_head = nh0 > 0 ? 1.0 * nh0 / ntrue0 : 0.0;
-          t.hr_tail = nh1 > 0 ? 1.0 * nh1 / ntrue1 : 0.0;
-          t.hr_all = 1.0 * nh2 / double(tlen);
-          t.arhr = gain / ideal;
-          t.flags = flags;
+          const UserTerms t = w.terms(ntrue0, ntrue1, tlen, ideal, flags);
+          if (lane == 0) T.terms[(int64_t)k * T.nusers + q] = t;
         }
-        if (lane == 0) T.terms[u] = t;
       }
     }
     __syncthreads();
@@ -607,29 +619,49 @@ __global__ void k_row_facts(int32_t nrows, const int64_t* __restrict__ ptr, cons
   if (bad) atomicExch(facts + 1, 1);
 }
 
-// entries of the longest row of a CSR (out preset to 0)
-__global__ void k_longest_row(int32_t nrows, const int64_t* __restrict__ ptr, int32_t* __restrict__ out) {
+// entries of the longest row among the rows at `nsel` positions of a CSR (users == nullptr: rows
+// [0, nsel)), and, when `total` is given, the entries of all of them (both preset to 0)
+__global__ void k_longest_row(int32_t nsel, const int32_t* __restrict__ users, const int64_t* __restrict__ ptr,
+                              int32_t* __restrict__ out, unsigned long long* __restrict__ total) {
   int32_t mx = 0;
-  for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x)
-    mx = max(mx, (int32_t)(ptr[r + 1] - ptr[r]));
-  for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
+  unsigned long long sum = 0;
+  for (int32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nsel; q += gridDim.x * blockDim.x) {
+    const int32_t r = users ? users[q] : q;
+    const int64_t len = ptr[r + 1] - ptr[r];
+    mx = max(mx, (int32_t)len);
+    sum += (unsigned long long)len;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = max(mx, __shfl_xor(mx, off));
+    const uint32_t lo = __shfl_xor((uint32_t)sum, off), hi = __shfl_xor((uint32_t)(sum >> 32), off);
+    sum += ((unsigned long long)hi << 32) | lo;
+  }
   if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(out, mx);
+  if (total && (threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
 }
 
-// the scorer's byte model: entries of the model rows that the histories of users [0, nusers) stream
-// (out preset to 0)
-__global__ void k_streamed_entries(int64_t h0, int64_t h1, const int32_t* __restrict__ hind, int32_t wrows,
+// the scorer's byte model: entries of the model rows that the histories of the users at `nsel` positions
+// stream (out preset to 0).  One wavefront per position, its lanes over the history.
+__global__ void k_streamed_entries(int32_t nsel, const int32_t* __restrict__ users, const int64_t* __restrict__ hptr,
+                                   const int32_t* __restrict__ hind, int32_t wrows,
                                    const int64_t* __restrict__ wptr, unsigned long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   unsigned long long sum = 0;
-  for (int64_t h = h0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < h1; h += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t i = hind[h];
-    if (i >= 0 && i < wrows) sum += (unsigned long long)(wptr[i + 1] - wptr[i]);
+  for (int64_t q = wave; q < nsel; q += nwaves) {
+    const int32_t u = users ? users[q] : (int32_t)q;
+    const int64_t h1 = hptr[u + 1];
+    for (int64_t h = hptr[u] + lane; h < h1; h += 64) {
+      const int32_t i = hind[h];
+      if (i >= 0 && i < wrows) sum += (unsigned long long)(wptr[i + 1] - wptr[i]);
+    }
   }
   for (int off = 32; off > 0; off >>= 1) {
     const uint32_t lo = __shfl_xor((uint32_t)sum, off), hi = __shfl_xor((uint32_t)(sum >> 32), off);
     sum += ((unsigned long long)hi << 32) | lo;
   }
-  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(out, sum);
+  if (lane == 0 && sum) atomicAdd(out, sum);
 }
 
 // Geometry of the chunk kernel for a model / history pair: key width, chunk width, LDS.
@@ -862,20 +894,21 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
 // The evaluate half of a model-selection cell without the host: the history is the staged matrix's CSR
 // where it lies, the model is a resident model's row view, the test rows and the head / tail marker
 // were staged once (slimgpu_evalset).  One fused kernel scores, selects and forms every user's terms;
-// k_sum_in_user_order adds them; 40 bytes come down.
+// k_sum_in_user_order adds them; 8 + 32 bytes per cutoff come down.  The evaluated users are the matrix's
+// first rows or a sorted list of them (positions, eval_terms.hpp); several list lengths are served by the
+// one scoring pass of the longest.
 namespace {
 
 thread_local slimgpu_eval_stats_t g_eval_stats;
 
-struct EvalOut {  // what one evaluation brings down
-  float f[4];
-  int32_t n[3];
-  int32_t pad;
+struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoffs bytes
   unsigned long long streamed;  // entries of the model rows streamed
+  EvalSums sums[SLIMGPU_MAX_CUTOFFS];
 };
 
 struct HistoryView {
-  int32_t nusers = 0;
+  int32_t nusers = 0;               // positions
+  const int32_t* users = nullptr;   // the user of every position; nullptr: position q is user q
   const int64_t* ptr = nullptr;
   const int32_t* ind = nullptr;
   const float* val = nullptr;
@@ -886,7 +919,8 @@ struct EvalTargets {  // the fused epilogue's inputs and output
   const int32_t* tind;
   const int32_t* fmarker;
   int32_t fm_ncols;
-  UserTerms* terms;
+  UserTerms* terms;  // [cut.n][positions]
+  Cutoffs cut;       // cut.c[cut.n - 1] == the nrcmds the scorer is queued with
 };
 
 int wave_kernel_waves(int32_t nusers, int32_t nrcmds, int num_cus, size_t* lds_out) {
@@ -942,6 +976,7 @@ int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, i
     }
     TopN2Args T{};
     T.nusers = H.nusers;
+    T.users = H.users;
     T.nitems_rows = W.nrows;
     T.ncols = ncols;
     T.nrcmds = nrcmds;
@@ -957,6 +992,7 @@ int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, i
     T.queue = ws.queue.get();
     if (ev) {
       T.tptr = ev->tptr; T.tind = ev->tind; T.fmarker = ev->fmarker; T.fm_ncols = ev->fm_ncols; T.terms = ev->terms;
+      T.cut = ev->cut;
     }
     const bool w16 = P.t2w == 16;
     auto kfn = ev ? (P.key32 ? (w16 ? topn_chunk_eval_kernel<16, uint32_t> : topn_chunk_eval_kernel<8, uint32_t>)
@@ -977,6 +1013,7 @@ int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, i
     const int nwaves = wave_kernel_waves(H.nusers, nrcmds, num_cus, &lds);
     TopNArgs T;
     T.nusers = H.nusers;
+    T.users = H.users;
     T.nitems_rows = W.nrows;
     T.ncols = ncols;
     T.nrcmds = nrcmds;
@@ -990,8 +1027,8 @@ int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, i
     hipLaunchKernelGGL(topn_kernel, dim3(nwaves), dim3(64), lds, stream, T);
     HIP_TRY(hipGetLastError());
     if (ev)
-      launch_user_terms(stream, num_cus, H.nusers, nrcmds, ws.oid.get(), ws.ocnt.get(), ev->tptr, ev->tind,
-                        ev->fmarker, ev->fm_ncols, ev->terms);
+      launch_user_terms(stream, num_cus, H.nusers, H.users, nrcmds, ev->cut, ws.oid.get(), ws.ocnt.get(), ev->tptr,
+                        ev->tind, ev->fmarker, ev->fm_ncols, ev->terms);
   }
   return path;
 }
@@ -1036,22 +1073,42 @@ void queue_row_facts(void* stream, int num_cus, int32_t nrows, const int64_t* d_
 }
 
 slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
-                                  int32_t fm_ncols, int32_t nrcmds, int32_t* status) {
+                                  int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
+                                  const int32_t* users, int32_t* status) {
   auto fail = [&](int32_t st) {
     if (status) *status = st;
     return static_cast<slimgpu_evalset_t*>(nullptr);
   };
+  auto refuse = [&](const std::string& what) {
+    set_error("SLIMGPU_EvalSetCreate: " + what);
+    return fail(SLIM_ERROR_INPUT);
+  };
   DeviceCsrView R;
-  if (!mat || !tst || !tst->rowptr || !fmarker || fm_ncols < 0 || nrcmds < 1 || nrcmds > 128 ||
-      matrix_csr_view(mat, &R) != SLIM_OK) {
-    set_error("SLIMGPU_EvalSetCreate: bad arguments (a staged matrix, a test handle, a marker, 1 <= nrcmds <= 128)");
-    return fail(SLIM_ERROR_INPUT);
+  if (!mat || !tst || !tst->rowptr || !fmarker || fm_ncols < 0 || !cutoffs)
+    return refuse("bad arguments (a staged matrix, a test handle, a marker, the list lengths)");
+  if (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS)
+    return refuse("between 1 and " + std::to_string(SLIMGPU_MAX_CUTOFFS) + " list lengths, not " + std::to_string(ncutoffs));
+  Cutoffs cut = {};
+  cut.n = ncutoffs;
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    if (cutoffs[k] < 1 || cutoffs[k] > 128)
+      return refuse("bad arguments (1 <= nrcmds <= 128, not " + std::to_string(cutoffs[k]) + ")");
+    if (k > 0 && cutoffs[k] <= cutoffs[k - 1]) return refuse("the list lengths must ascend strictly");
+    cut.c[k] = cutoffs[k];
   }
-  if (R.merged) {
-    set_error("SLIMGPU_EvalSetCreate: the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were "
-              "merged: its rows are not the caller's, evaluate through the host handle");
-    return fail(SLIM_ERROR_INPUT);
+  if (users ? nusers < 1 : nusers != 0)
+    return refuse(users ? "a user list needs at least one user" : "nusers must be 0 without a user list");
+  if (matrix_csr_view(mat, &R) != SLIM_OK) return refuse("bad arguments (a staged matrix)");
+  if (R.merged)
+    return refuse("the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were "
+                  "merged: its rows are not the caller's, evaluate through the host handle");
+  const int32_t nall = std::min(R.nrows, tst->nrows);  // pyapi.c:309
+  for (int32_t q = 0; q < nusers; ++q) {
+    if (users[q] < 0 || users[q] >= nall)
+      return refuse("user " + std::to_string(users[q]) + " is outside [0, " + std::to_string(nall) + ")");
+    if (q > 0 && users[q] <= users[q - 1]) return refuse("the user ids must ascend strictly");
   }
+  const int32_t nrcmds = cut.c[cut.n - 1];
   slimgpu_evalset* es = nullptr;
   try {
     (void)hipGetLastError();
@@ -1060,45 +1117,51 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
     es = new slimgpu_evalset();
     es->mat = mat;
     es->device = R.device;
-    es->nusers = std::min(R.nrows, tst->nrows);  // pyapi.c:309
-    es->nrcmds = nrcmds;
+    es->listed = users != nullptr;
+    es->nsel = users ? nusers : nall;
+    es->cut = cut;
     es->fm_ncols = fm_ncols;
-    const int32_t nu = es->nusers;
-    const int64_t tnnz = tst->rowptr[nu];
-    es->d_tptr = DeviceBuffer<int64_t>((size_t)nu + 1);
+    const int32_t nsel = es->nsel;
+    const int64_t tnnz = tst->rowptr[nall];
+    es->d_tptr = DeviceBuffer<int64_t>((size_t)nall + 1);
     es->d_tind = DeviceBuffer<int32_t>((size_t)tnnz);
     es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
-    es->d_terms = DeviceBuffer<UserTerms>((size_t)nu);
+    es->d_terms = DeviceBuffer<UserTerms>((size_t)cut.n * (size_t)nsel);
     es->d_out = DeviceBuffer<unsigned long long>(sizeof(EvalOut) / sizeof(unsigned long long));
     static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
-    HIP_TRY(hipMemcpyAsync(es->d_tptr.get(), tst->rowptr, sizeof(int64_t) * ((size_t)nu + 1), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(es->d_tptr.get(), tst->rowptr, sizeof(int64_t) * ((size_t)nall + 1), hipMemcpyHostToDevice, stream));
     if (tnnz > 0)
       HIP_TRY(hipMemcpyAsync(es->d_tind.get(), tst->rowind, sizeof(int32_t) * (size_t)tnnz, hipMemcpyHostToDevice, stream));
     if (fm_ncols > 0)
       HIP_TRY(hipMemcpyAsync(es->d_fm.get(), fmarker, sizeof(int32_t) * (size_t)fm_ncols, hipMemcpyHostToDevice, stream));
-    // the longest history and the number of history entries, once (the scorer's key width needs the first)
-    int32_t* d_max = reinterpret_cast<int32_t*>(es->d_out.get());
-    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), stream));
-    if (nu > 0) {
-      hipLaunchKernelGGL(k_longest_row, dim3(std::max(1, std::min((nu + 255) / 256, R.num_cus * 8))), dim3(256), 0,
-                         stream, nu, R.d_ptr, d_max);
+    if (users) {  // (pageable source: the copy has left the caller's array when the call returns)
+      es->d_users = DeviceBuffer<int32_t>((size_t)nsel);
+      HIP_TRY(hipMemcpyAsync(es->d_users.get(), users, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
+    }
+    // the longest history of the evaluated users and the number of their history entries, once (the
+    // scorer's key width needs the first)
+    EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
+    int32_t* d_max = &d_out->sums[0].n[0];
+    HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(EvalOut), stream));
+    if (nsel > 0) {
+      hipLaunchKernelGGL(k_longest_row, dim3(std::max(1, std::min((nsel + 255) / 256, R.num_cus * 8))), dim3(256), 0,
+                         stream, nsel, static_cast<const int32_t*>(users ? es->d_users.get() : nullptr), R.d_ptr, d_max,
+                         &d_out->streamed);
       HIP_TRY(hipGetLastError());
     }
     int32_t h_max = 0;
-    int64_t h_ends[2] = {0, 0};
+    unsigned long long h_total = 0;
     HIP_TRY(hipMemcpyAsync(&h_max, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&h_ends[0], R.d_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&h_ends[1], R.d_ptr + nu, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_total, &d_out->streamed, sizeof(h_total), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     es->max_hist = h_max;
-    es->hist_begin = h_ends[0];
-    es->hist_entries = h_ends[1] - h_ends[0];
+    es->hist_entries = (int64_t)h_total;
     // workspaces for the worst model: 64-bit keys, hence the smallest chunks and the largest split table
     DeviceRowView worst;
     worst.nrows = worst.ncols = R.ncols;
     worst.rows_sorted = true;
     const ChunkPlan P = plan_chunks(std::max(R.ncols, 1), 0, es->max_hist, /*force_key64=*/true);
-    reserve_scorer(es->ws, scorer_path(worst, nrcmds, P), R.ncols, std::max(R.ncols, 1), P, nu, nrcmds, R.num_cus,
+    reserve_scorer(es->ws, scorer_path(worst, nrcmds, P), R.ncols, std::max(R.ncols, 1), P, nsel, nrcmds, R.num_cus,
                    /*lists=*/false);
     HIP_TRY(hipEventCreate(&es->ev0));
     HIP_TRY(hipEventCreate(&es->ev1));
@@ -1116,11 +1179,18 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
 
 void evalset_free(slimgpu_evalset_t* es) { delete es; }
 
-int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, EvalResult* out) {
+int32_t evalset_cutoffs(const slimgpu_evalset_t* es) { return es ? es->cut.n : 0; }
+
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out) {
   DeviceRowView W;
   DeviceCsrView R;
   if (!es || !model || !out || model_row_view(model, &W) != SLIM_OK || matrix_csr_view(es->mat, &R) != SLIM_OK) {
     set_error("SLIMGPU_ModelEvaluate: needs an eval set and a resident model with a row view");
+    return SLIM_ERROR_INPUT;
+  }
+  if (ncutoffs != es->cut.n) {
+    set_error("SLIMGPU_ModelEvaluate: the eval set holds " + std::to_string(es->cut.n) + " list lengths, the call asks for " +
+              std::to_string(ncutoffs));
     return SLIM_ERROR_INPUT;
   }
   if (const int32_t rc = check_pair("SLIMGPU_ModelEvaluate", R, W); rc != SLIM_OK) return rc;
@@ -1128,7 +1198,8 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, EvalRe
     set_error("SLIMGPU_ModelEvaluate: the eval set and the matrix live on different devices");
     return SLIM_ERROR_INPUT;
   }
-  *out = EvalResult();
+  const int32_t ncut = es->cut.n;
+  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
   try {
@@ -1137,38 +1208,43 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, EvalRe
     hipStream_t stream = static_cast<hipStream_t>(R.stream);
     es->ws.allocs = 0;
     EvalOut h = {};
-    if (es->nusers > 0) {
+    if (es->nsel > 0) {
       HistoryView H;
-      H.nusers = es->nusers;
+      H.nusers = es->nsel;
+      H.users = es->listed ? es->d_users.get() : nullptr;
       H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
       H.max_hist = es->max_hist;
-      const EvalTargets ev = {es->d_tptr.get(), es->d_tind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get()};
+      const EvalTargets ev = {es->d_tptr.get(), es->d_tind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get(), es->cut};
       EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
       HIP_TRY(hipEventRecord(es->ev0, stream));
-      st.path = queue_scorer(W, H, es->nrcmds, R.num_cus, stream, es->ws, &ev, /*lists=*/false);
-      launch_sum_in_user_order(stream, es->nusers, es->d_terms.get(), d_out->f, d_out->n);
+      st.path = queue_scorer(W, H, es->cut.c[ncut - 1], R.num_cus, stream, es->ws, &ev, /*lists=*/false);
+      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), d_out->sums);
       HIP_TRY(hipEventRecord(es->ev1, stream));
       HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
       if (es->hist_entries > 0 && W.nnz > 0) {
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((es->hist_entries + 255) / 256, R.num_cus * 8));
-        hipLaunchKernelGGL(k_streamed_entries, dim3(blocks), dim3(256), 0, stream, es->hist_begin, es->hist_begin + es->hist_entries,
-                           R.d_ind, W.nrows, W.d_ptr, &d_out->streamed);
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)es->nsel + 3) / 4, R.num_cus * 8));
+        hipLaunchKernelGGL(k_streamed_entries, dim3(blocks), dim3(256), 0, stream, es->nsel, H.users, R.d_ptr, R.d_ind,
+                           W.nrows, W.d_ptr, &d_out->streamed);
         HIP_TRY(hipGetLastError());
       }
-      HIP_TRY(hipMemcpyAsync(&h, d_out, sizeof(EvalOut), hipMemcpyDeviceToHost, stream));
+      const size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncut;
+      HIP_TRY(hipMemcpyAsync(&h, d_out, down, hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
-      st.d2h_bytes = sizeof(EvalOut);
+      st.d2h_bytes = (int64_t)down;
       float ms = 0;
       HIP_TRY(hipEventElapsedTime(&ms, es->ev0, es->ev1));
       st.kernel_ms = ms;
     }
-    out->nvalid = h.n[0];
-    out->nvalid_head = h.n[1];
-    out->nvalid_tail = h.n[2];
-    out->hr = h.n[0] > 0 ? h.f[0] / h.n[0] : 0;
-    out->hr_head = h.n[1] > 0 ? h.f[1] / h.n[1] : 0;
-    out->hr_tail = h.n[2] > 0 ? h.f[2] / h.n[2] : 0;
-    out->arhr = h.n[0] > 0 ? h.f[3] / h.n[0] : 0;
+    for (int32_t k = 0; k < ncut; ++k) {
+      const EvalSums& s = h.sums[k];
+      out[k].nvalid = s.n[0];
+      out[k].nvalid_head = s.n[1];
+      out[k].nvalid_tail = s.n[2];
+      out[k].hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0;
+      out[k].hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0;
+      out[k].hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
+      out[k].arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
+    }
     st.device_allocs = es->ws.allocs;
     st.w_rows_read = es->hist_entries;
     st.w_bytes = 8.0 * (double)h.streamed;
@@ -1205,7 +1281,8 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
       ++ws.allocs;
       HIP_TRY(hipMemsetAsync(d_max.get(), 0, sizeof(int32_t), stream));
       hipLaunchKernelGGL(k_longest_row, dim3(std::max(1, std::min((nu + 255) / 256, R.num_cus * 8))), dim3(256), 0,
-                         stream, nu, R.d_ptr, d_max.get());
+                         stream, nu, static_cast<const int32_t*>(nullptr), R.d_ptr, d_max.get(),
+                         static_cast<unsigned long long*>(nullptr));
       HIP_TRY(hipGetLastError());
       int32_t h_max = 0;
       HIP_TRY(hipMemcpyAsync(&h_max, d_max.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream));

@@ -153,13 +153,15 @@ def _wrap_rows(lib, M):
 
 
 class Evaluator(object):
-    """The test set of a grid staged in HBM (SLIMGPU_EvalSetCreate): `evaluate(resident_model)` scores
-    the model against the staged training matrix and brings down HR / ARHR only."""
+    """The test set of a grid staged in HBM (SLIMGPU_EvalSetCreateAt): `evaluate(resident_model)` scores
+    the model against the staged training matrix and brings down HR / ARHR only -- of the longest
+    lists; `evaluate_at(resident_model)` gives the figures of every list length, from the same pass."""
 
-    def __init__(self, lib, handle, matrix):
+    def __init__(self, lib, handle, matrix, cutoffs=(10,)):
         self._lib = lib
         self.handle = C.c_void_p(handle)
         self._matrix = matrix      # borrowed by the eval set: keep it alive
+        self.cutoffs = tuple(int(c) for c in cutoffs)
 
     def evaluate(self, model):
         met = np.zeros(4, np.float64)
@@ -169,6 +171,18 @@ class Evaluator(object):
             raise RuntimeError("SLIMGPU_ModelEvaluate failed (%d): %s" % (st, _lib.last_error()))
         return {"hr": met[0], "hr_head": met[1], "hr_tail": met[2], "arhr": met[3],
                 "nvalid": int(nv[0]), "nvalid_head": int(nv[1]), "nvalid_tail": int(nv[2])}
+
+    def evaluate_at(self, model):
+        """SLIMGPU_ModelEvaluateAt: one dict per list length (evaluate()'s keys and "nrcmds")."""
+        n = len(self.cutoffs)
+        met = np.zeros(4 * n, np.float64)
+        nv = np.zeros(3 * n, np.int32)
+        st = self._lib.SLIMGPU_ModelEvaluateAt(self.handle, model.handle, n, met, nv)
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_ModelEvaluateAt failed (%d): %s" % (st, _lib.last_error()))
+        return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
+                 "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
+                 "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
 
     def stats(self):
         return eval_stats(self._lib)
@@ -304,9 +318,11 @@ class DeviceMatrix(object):
         self._lib.SLIMGPU_LastStats(C.byref(stats))
         return ResidentModel(self._lib, h), stats.as_dict()
 
-    def evaluator(self, T, nrcmds=10, fmarker=None, R=None):
-        """SLIMGPU_EvalSetCreate: stage the test matrix T (scipy, one row per user) for evaluations
-        of resident models against this matrix.  fmarker=None: SLIM_DetermineHeadAndTail over the
+    def evaluator(self, T, nrcmds=10, fmarker=None, R=None, cutoffs=None, users=None):
+        """SLIMGPU_EvalSetCreateAt: stage the test matrix T (scipy, one row per user) for evaluations
+        of resident models against this matrix.  cutoffs: the list lengths (ascending, at most 8 of
+        1..128; None: [nrcmds]), all served by one scoring pass.  users: ascending user ids to evaluate
+        (None: every user).  fmarker=None: SLIM_DetermineHeadAndTail over the
         training rows with ncols = the larger of the two matrices' widths, as Py_SLIM_Mselect does
         (the rows from_scipy staged; R, a scipy matrix, for a matrix adopted from device pointers)."""
         T = sp.csr_matrix(T)
@@ -325,16 +341,21 @@ class DeviceMatrix(object):
             fmarker = np.ctypeslib.as_array(p, shape=(ncols,)).copy()
             C.CDLL(None).free(p)
         fmarker = np.ascontiguousarray(fmarker, dtype=np.int32)
+        cut = np.ascontiguousarray([nrcmds] if cutoffs is None else cutoffs, dtype=np.int32).ravel()
+        sel = None if users is None else np.ascontiguousarray(users, dtype=np.int32).ravel()
         ht = _wrap_rows(self._lib, T)
         st = C.c_int32(0)
         try:
-            h = self._lib.SLIMGPU_EvalSetCreate(self.handle, ht, fmarker, fmarker.size, int(nrcmds),
-                                                C.byref(st))
+            h = self._lib.SLIMGPU_EvalSetCreateAt(self.handle, ht, fmarker, fmarker.size, cut.size,
+                                                  cut.ctypes.data_as(C.c_void_p),
+                                                  0 if sel is None else sel.size,
+                                                  None if sel is None else sel.ctypes.data_as(C.c_void_p),
+                                                  C.byref(st))
         finally:
             self._lib.Py_csr_free(ht)
         if not h:
-            raise RuntimeError("SLIMGPU_EvalSetCreate failed (%d): %s" % (st.value, _lib.last_error()))
-        return Evaluator(self._lib, h, self)
+            raise RuntimeError("SLIMGPU_EvalSetCreateAt failed (%d): %s" % (st.value, _lib.last_error()))
+        return Evaluator(self._lib, h, self, cut.tolist())
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)

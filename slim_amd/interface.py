@@ -117,7 +117,8 @@ def build_options(params):
     dopt[Opt.L2R] = view.get("l2r")
     dopt[Opt.OPTTOL] = view.get("optTol")
     # engine extensions ride along when present (include/slim_gpu.h)
-    for key, slot in (("gpu_seed", Opt.GPU_SEED), ("gpu_device", Opt.GPU_DEVICE),
+    for key, slot in (("gpu_seed", Opt.GPU_SEED), ("gpu_evalstride", Opt.GPU_EVALSTRIDE),
+                      ("gpu_device", Opt.GPU_DEVICE),
                       ("gpu_kernel", Opt.GPU_KERNEL), ("gpu_colbegin", Opt.GPU_COLBEGIN),
                       ("gpu_colend", Opt.GPU_COLEND)):
         if view.has(key):
