@@ -1384,16 +1384,28 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
     const bool prof = p.trace_level >= 2;
     const bool val = !m->binary;
     const bool nw16 = p.tileNW == 16;
-    if (p.tileP == 32 && opt.nnbrs > 0)
+    // (form / profiled: what the branch that assigns p.fn instantiates, for the trace line below)
+    const char* form = "colfold";
+    bool profiled = false;
+    if (p.tileP == 32 && opt.nnbrs > 0) {
       p.fn = tile_kernel_p32_fslim(val, nw16);
-    else if (p.tileP == 32 && !prof && !p.has_imodel)
+      form = "fslim";
+    } else if (p.tileP == 32 && !prof && !p.has_imodel) {
       p.fn = tile_kernel_p32_cold(val, nw16);
-    else if (p.tileP == 32 && !prof && row_fold)
+      form = "cold";
+    } else if (p.tileP == 32 && !prof && row_fold) {
       p.fn = tile_kernel_p32_rowfold(val, nw16);
-    else if (p.tileP == 32)
+      form = "rowfold";
+    } else if (p.tileP == 32) {
       p.fn = nw16 ? tile_kernel_p32_nw16(val, prof) : tile_kernel_p32_nw8(val, prof);
-    else
+      profiled = prof;
+    } else {
       p.fn = nw16 ? tile_kernel_p16_nw16(val, prof) : tile_kernel_p16_nw8(val, prof);
+      profiled = prof;
+    }
+    if (p.trace_level >= 1)  // which instantiation of cd_tile_kernel this solve runs (tile_inst.hpp)
+      std::fprintf(stderr, "[trace] tile kernel: P %d, %d wavefronts, form %s, %s%s\n", p.tileP, nw16 ? 16 : 8,
+                   form, val ? "valued" : "binary", profiled ? ", profiled" : "");
   }
   int waves_per_cu;
   if (p.use_gram) {  // one workgroup per problem, as many per CU as g (LDS) and registers allow
