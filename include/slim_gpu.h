@@ -172,7 +172,8 @@ int32_t SLIMGPU_MatrixDevice(const slimgpu_matrix_t *mat);
  * their blocks into each other's buffers (View: device floats, `ld` per row -- e.g. one RCCL
  * broadcast per block), and Commit declares every row present (and forms the byte planes where G is
  * integer-valued).  Without these every rank builds all of G itself (what SLIMGPU_Learn does when
- * it needs G).  No counterpart in the reference (its CD keeps the residual, src/libslim/cd.c:86-153);
+ * it needs G).  The committed G must be symmetric -- it is R^T R --: the byte planes are formed from
+ * the rows of the items in popularity order, read for the columns they mirror.  No counterpart in the reference (its CD keeps the residual, src/libslim/cd.c:86-153);
  * the sums are the a_i . a_j of estimate.c:412-421 for every pair of items.  SLIM_OK or an error
  * code (SLIMGPU_LastError). */
 int32_t SLIMGPU_MatrixGramBuildRows(slimgpu_matrix_t *mat, int32_t row_begin, int32_t row_end);
@@ -301,5 +302,7 @@ const char *SLIMGPU_LastError(void);
 
 /* Evaluation of resident models without leaving HBM (eval sets, top-N of the staged rows). */
 #include "slim_gpu_eval.h"
+/* A look at the byte planes of G = R^T R (SLIMGPU_MatrixGramPlanes). */
+#include "slim_gpu_planes.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

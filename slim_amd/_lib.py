@@ -147,6 +147,21 @@ _EVAL_AT_SIGNATURES = {
 }
 
 EVAL_AT_SYMBOLS = tuple(_EVAL_AT_SIGNATURES)
+
+
+class GramPlanes(C.Structure):
+    """slimgpu_gram_planes_t (include/slim_gpu_planes.h): device pointers and sizes."""
+    _fields_ = ([("ncols", C.c_int32), ("nchunks", C.c_int32), ("ldb", C.c_int64), ("hi_bytes", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("lo", "base", "hi", "hi_off", "hi_k", "hi2_k", "diag", "meta",
+                                           "rank_of", "item_of")])
+
+
+# a look at the byte planes of G (include/slim_gpu_planes.h)
+_PLANES_SIGNATURES = {
+    "SLIMGPU_MatrixGramPlanes": (C.c_int32, [C.c_void_p, C.POINTER(GramPlanes)]),
+}
+
+PLANES_SYMBOLS = tuple(_PLANES_SIGNATURES)
 MAX_CUTOFFS = 8     # SLIMGPU_MAX_CUTOFFS
 
 _lib = None
@@ -163,7 +178,7 @@ def load():
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for SLIM training." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
-                              list(_EVAL_AT_SIGNATURES.items())):
+                              list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

@@ -99,7 +99,7 @@ struct slimgpu_matrix {
   DeviceBuffer<uint4> ws_Gmeta;
   DeviceBuffer<int64_t> ws_hioff, ws_hi2off;
   DeviceBuffer<int32_t> ws_hik, ws_hi2k, ws_rankof, ws_itemof;
-  int64_t Gp_ldb = 0;
+  int64_t Gp_ldb = 0, Gp_pool_bytes = 0;
   int32_t Gp_nchunks = 0;
   bool Gp_ready = false, Gp_tried = false;
   bool Gf_dropped = false;          // the floats of G were freed once the planes stood (drop_float_gram)
@@ -997,9 +997,25 @@ bool pack_gram(slimgpu_matrix* m) {
   // (SLIM_GPU_PACK_BASE=0: no per-chunk base bytes -- the first form of the planes, A/B runs)
   int use_base = 1;
   if (const char* e = std::getenv("SLIM_GPU_PACK_BASE")) use_base = std::atoi(e) != 0;
-  hipLaunchKernelGGL(gram_pack_scan_fn(), dim3(ncols), dim3(256), 0, st, dG, m->G_ld, ncols, d_item_of, nchunks,
-                     use_base, d_hik, d_hi2k, d_flag);
-  HIP_TRY(hipGetLastError());
+  // (SLIM_GPU_PACK_GATHER=1: the per-row kernels that gather g[item_of[.]] -- A/B runs and the tests
+  // that hold the streamed form against them; the streamed form reads G[item_of[r]][j] for
+  // G[j][item_of[r]], equal wherever planes are built at all: an integer-valued G is exactly symmetric)
+  bool gather = false;
+  if (const char* e = std::getenv("SLIM_GPU_PACK_GATHER")) gather = std::atoi(e) != 0;
+  const dim3 tgrid(kGramrNT / kPackTS, (ncols + kPackJT - 1) / kPackJT);
+  if (gather) {
+    hipLaunchKernelGGL(gram_pack_scan_fn(), dim3(ncols), dim3(256), 0, st, dG, m->G_ld, ncols, d_item_of, nchunks,
+                       use_base, d_hik, d_hi2k, d_flag);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemsetAsync(d_hik, 0xff, sizeof(int32_t) * (size_t)ncols, st));  // last chunk: -1
+    HIP_TRY(hipMemsetAsync(d_hi2k, 0xff, sizeof(int32_t) * (size_t)ncols, st));
+    hipLaunchKernelGGL(gram_pack_scan_t_fn(), tgrid, dim3(256), 0, st, dG, m->G_ld, ncols, d_item_of, d_rank_of,
+                       nchunks, use_base, d_hik, d_hi2k, d_flag);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gram_pack_groups_fn(), dim3((ncols + 255) / 256), dim3(256), 0, st, ncols, d_hik, d_hi2k);
+    HIP_TRY(hipGetLastError());
+  }
   std::vector<int32_t> hk((size_t)ncols + 1), h2k((size_t)ncols);
   HIP_TRY(hipMemcpyAsync(hk.data(), d_hik, sizeof(int32_t) * hk.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(h2k.data(), d_hi2k, sizeof(int32_t) * h2k.size(), hipMemcpyDeviceToHost, st));
@@ -1026,7 +1042,9 @@ bool pack_gram(slimgpu_matrix* m) {
   uint8_t* d_hi = m->ws_Ghi.reserve((size_t)npool + kPackGroup);
   uint8_t* d_hi2 = d_hi;
   uint8_t* d_base = m->ws_Gbase.reserve((size_t)ncols * kPackGroup);
-  HIP_TRY(hipMemsetAsync(d_base, 0, (size_t)ncols * kPackGroup, st));
+  if (gather) {  // (streamed: every record is written)
+    HIP_TRY(hipMemsetAsync(d_base, 0, (size_t)ncols * kPackGroup, st));
+  }
   float* d_diag = m->ws_Gdiag.reserve((size_t)ncols);
   HIP_TRY(hipMemsetAsync(d_diag, 0, sizeof(float) * (size_t)ncols, st));
   int64_t* d_off1 = m->ws_hioff.reserve((size_t)ncols);
@@ -1034,8 +1052,13 @@ bool pack_gram(slimgpu_matrix* m) {
   HIP_TRY(hipMemcpyAsync(d_off1, off1.data(), sizeof(int64_t) * off1.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(d_off2, off2.data(), sizeof(int64_t) * off2.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(d_hi + npool, 0, kPackGroup, st));
-  hipLaunchKernelGGL(gram_pack_write_fn(), dim3(ncols), dim3(256), 0, st, dG, m->G_ld, ncols, d_item_of, nchunks,
-                     d_lo, ldb, d_hi, d_off1, d_hik, d_hi2, d_off2, d_hi2k, d_base, d_diag);
+  if (gather) {
+    hipLaunchKernelGGL(gram_pack_write_fn(), dim3(ncols), dim3(256), 0, st, dG, m->G_ld, ncols, d_item_of, nchunks,
+                       d_lo, ldb, d_hi, d_off1, d_hik, d_hi2, d_off2, d_hi2k, d_base, d_diag);
+  } else {
+    hipLaunchKernelGGL(gram_pack_write_t_fn(), tgrid, dim3(256), 0, st, dG, m->G_ld, ncols, d_item_of, d_rank_of,
+                       nchunks, d_lo, ldb, d_hi, d_off1, d_hik, d_hi2, d_off2, d_hi2k, d_base, d_diag);
+  }
   HIP_TRY(hipGetLastError());
   uint4* d_meta = m->ws_Gmeta.reserve((size_t)ncols);
   hipLaunchKernelGGL(gram_pack_meta_fn(), dim3((ncols + 255) / 256), dim3(256), 0, st, ncols, d_rank_of, d_hik,
@@ -1046,12 +1069,13 @@ bool pack_gram(slimgpu_matrix* m) {
   HIP_TRY(hipStreamSynchronize(st));  // (off1 / off2 are locals)
   if (meta_flag & 2) return false;    // |a_i|^2 of the planes is not the column view's: float kernels
   m->Gp_ldb = ldb;
+  m->Gp_pool_bytes = npool + kPackGroup;
   m->Gp_nchunks = nchunks;
   m->Gp_bytes_per_row = (double)ldb + 16.0 * std::min(nchunks, kGramrNT) + (double)(n1 + n2) / std::max(1, ncols);
   m->Gp_ready = true;
   if (const char* te = std::getenv("SLIM_GPU_TRACE"); te && std::atoi(te) >= 1)
-    std::fprintf(stderr, "[trace] G packed: lo %.2f GB + base %.2f GB + hi %.2f GB + hi2 %.3f GB = %.3f bytes per entry, %.1f ms\n",
-                 (double)ncols * ldb * 1e-9, (double)ncols * kPackGroup * 1e-9, n1 * 1e-9, n2 * 1e-9,
+    std::fprintf(stderr, "[trace] G packed (%s): lo %.2f GB + base %.2f GB + hi %.2f GB + hi2 %.3f GB = %.3f bytes per entry, %.1f ms\n",
+                 gather ? "gathers" : "streamed tiles", (double)ncols * ldb * 1e-9, (double)ncols * kPackGroup * 1e-9, n1 * 1e-9, n2 * 1e-9,
                  m->Gp_bytes_per_row / std::max(1, ncols), now_ms() - t0);
   return true;
 }
@@ -2769,6 +2793,28 @@ int32_t gram_commit(slimgpu_matrix_t* m) {
     report(e, "SLIMGPU_MatrixGramCommit");
     return status_of(e);
   }
+}
+
+int32_t gram_planes(slimgpu_matrix_t* m, slimgpu_gram_planes_t* out) {
+  if (!m || !out || !m->Gp_ready) {
+    set_error("SLIMGPU_MatrixGramPlanes: no byte planes on this handle (no G committed, or a G that could not be packed)");
+    return SLIM_ERROR_INPUT;
+  }
+  out->ncols = m->ncols;
+  out->nchunks = m->Gp_nchunks;
+  out->ldb = m->Gp_ldb;
+  out->hi_bytes = m->Gp_pool_bytes;
+  out->lo = m->ws_Glo.get();
+  out->base = m->ws_Gbase.get();
+  out->hi = m->ws_Ghi.get();
+  out->hi_off = m->ws_hioff.get();
+  out->hi_k = m->ws_hik.get();
+  out->hi2_k = m->ws_hi2k.get();
+  out->diag = m->ws_Gdiag.get();
+  out->meta = reinterpret_cast<const uint32_t*>(m->ws_Gmeta.get());
+  out->rank_of = m->ws_rankof.get();
+  out->item_of = m->ws_itemof.get();
+  return SLIM_OK;
 }
 
 }  // namespace slimamd

@@ -66,6 +66,8 @@ void matrix_expect_solves(slimgpu_matrix_t* m, int32_t n);
 int32_t gram_build_rows(slimgpu_matrix_t* m, int32_t row_begin, int32_t row_end);
 int32_t gram_view(slimgpu_matrix_t* m, void** dptr, int64_t* ld, int32_t* nrows);
 int32_t gram_commit(slimgpu_matrix_t* m);
+// the byte planes the handle holds (slim_gpu_planes.h); SLIM_ERROR_INPUT when it holds none
+int32_t gram_planes(slimgpu_matrix_t* m, slimgpu_gram_planes_t* out);
 
 // EstimateModelCD + SaveModel on the device matrix.  Returns a host model
 // (slim_csr_t with both views) or nullptr with *status set.

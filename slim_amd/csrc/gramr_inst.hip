@@ -35,4 +35,7 @@ int gramr_union_threads() { return kGramrUnionNT; }
 PackScanFn gram_pack_scan_fn() { return gram_pack_scan; }
 PackWriteFn gram_pack_write_fn() { return gram_pack_write; }
 PackMetaFn gram_pack_meta_fn() { return gram_pack_meta; }
+PackScanTFn gram_pack_scan_t_fn() { return gram_pack_scan_t; }
+PackGroupsFn gram_pack_groups_fn() { return gram_pack_groups; }
+PackWriteTFn gram_pack_write_t_fn() { return gram_pack_write_t; }
 }  // namespace slimamd

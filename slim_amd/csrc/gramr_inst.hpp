@@ -27,5 +27,16 @@ PackWriteFn gram_pack_write_fn();
 using PackMetaFn = void (*)(int, const int32_t*, const int32_t*, const int32_t*, const int64_t*, const float*,
                             const int64_t*, const float*, const float*, uint4*, int32_t*);
 PackMetaFn gram_pack_meta_fn();
+// the same passes by streaming transposed tiles (gram_pack.hpp): scan into last1 / last2, the rounding
+// to groups, write; grid (kGramrNT / kPackTS, ceil(ncols / kPackJT)) x 256 threads for scan and write
+using PackScanTFn = void (*)(const float*, int64_t, int, const int32_t*, const int32_t*, int, int, int32_t*, int32_t*,
+                             int32_t*);
+using PackGroupsFn = void (*)(int, int32_t*, int32_t*);
+using PackWriteTFn = void (*)(const float*, int64_t, int, const int32_t*, const int32_t*, int, uint8_t*, int64_t,
+                              uint8_t*, const int64_t*, const int32_t*, uint8_t*, const int64_t*, const int32_t*,
+                              uint8_t*, float*);
+PackScanTFn gram_pack_scan_t_fn();
+PackGroupsFn gram_pack_groups_fn();
+PackWriteTFn gram_pack_write_t_fn();
 
 }  // namespace slimamd

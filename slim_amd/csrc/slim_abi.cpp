@@ -519,6 +519,11 @@ int32_t SLIMGPU_MatrixGramCommit(slimgpu_matrix_t* mat) {
   return gram_commit(mat);
 }
 
+int32_t SLIMGPU_MatrixGramPlanes(slimgpu_matrix_t* mat, slimgpu_gram_planes_t* out) {
+  set_error("");
+  return gram_planes(mat, out);
+}
+
 slim_t* SLIMGPU_Learn(slimgpu_matrix_t* mat, int32_t* ioptions, double* doptions, slim_t* imodel,
                       int32_t* r_status) {
   set_error("");

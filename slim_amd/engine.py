@@ -407,6 +407,38 @@ class DeviceMatrix(object):
         if st != SLIM_OK:
             raise RuntimeError("SLIMGPU_MatrixGramCommit failed (%d): %s" % (st, _lib.last_error()))
 
+    def gram_planes(self):
+        """Host copies of the byte planes the handle holds (SLIMGPU_MatrixGramPlanes; the layout is
+        in include/slim_gpu_planes.h) as a dict of numpy arrays: lo (ncols, ldb), base (ncols, 8192),
+        hi (the pool, slack included), hi_off, hi_k, hi2_k, diag, meta (ncols, 4), rank_of, item_of,
+        and the ints ncols, nchunks, ldb.  RuntimeError when the handle holds none."""
+        import torch
+        p = _lib.GramPlanes()
+        st = self._lib.SLIMGPU_MatrixGramPlanes(self.handle, C.byref(p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_MatrixGramPlanes failed (%d): %s" % (st, _lib.last_error()))
+        n, ldb = int(p.ncols), int(p.ldb)
+        dev = torch.device("cuda", self.device)
+        torch.cuda.synchronize(dev)
+
+        def fetch(ptr, shape, dtype):
+            out = np.empty(shape, dtype)
+            if out.size:
+                class _Alias:
+                    pass
+                a = _Alias()
+                a.__cuda_array_interface__ = {"shape": (out.nbytes,), "typestr": "|u1", "data": (int(ptr), False),
+                                              "version": 2, "strides": None}
+                out.view(np.uint8).reshape(-1)[:] = torch.as_tensor(a, device=dev).cpu().numpy()
+            return out
+        return {"ncols": n, "nchunks": int(p.nchunks), "ldb": ldb,
+                "lo": fetch(p.lo, (n, ldb), np.uint8), "base": fetch(p.base, (n, 8192), np.uint8),
+                "hi": fetch(p.hi, (int(p.hi_bytes),), np.uint8), "hi_off": fetch(p.hi_off, (n,), np.int64),
+                "hi_k": fetch(p.hi_k, (n,), np.int32), "hi2_k": fetch(p.hi2_k, (n,), np.int32),
+                "diag": fetch(p.diag, (n,), np.float32), "meta": fetch(p.meta, (n, 4), np.uint32),
+                "rank_of": fetch(p.rank_of, (n,), np.int32),
+                "item_of": fetch(p.item_of, (16 * int(p.nchunks),), np.int32)}
+
 
 def _scipy_to_model_handle(lib, W):
     """Model handle (row + column views) from a scipy matrix, via the text-free
