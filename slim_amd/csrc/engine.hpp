@@ -163,6 +163,10 @@ slimgpu_eval_stats_t& last_eval_stats();
 // `stream` (a hipStream_t); throws HipFail when the launch fails.
 void queue_row_facts(void* stream, int num_cus, int32_t nrows, const int64_t* d_ptr, const int32_t* d_ind,
                      int32_t* d_facts);
+// the row-order check of a host model once it is staged (the scorers of topn.hip and the 1-vs-k scorer of
+// eval.hip): whether the ids of every row ascend strictly.  One kernel on the null stream and four bytes
+// down; throws HipFail.
+bool rows_ascend_strictly(int num_cus, int32_t nrows, const int64_t* d_ptr, const int32_t* d_ind);
 
 // admm.hip: SLIM_Learn(algo = admm), the reference's dense ADMM solver (estimate.c:38-304) with
 // rocBLAS for the panel solves, updates and products and HIP kernels for the rest.

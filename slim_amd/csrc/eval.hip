@@ -23,6 +23,7 @@
 #include "eval_terms.hpp"
 #include "hip_check.hpp"
 #include "host_csr.hpp"
+#include "host_stage.hpp"
 
 namespace slimamd {
 
@@ -108,16 +109,6 @@ __global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nsel, const Us
 
 // ---- 1-vs-k ----------------------------------------------------------------------------
 
-__global__ void k_rows_ascending(int32_t nrows, const int64_t* __restrict__ ptr,
-                                 const int32_t* __restrict__ ind, int32_t* __restrict__ bad) {
-  for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x)
-    for (int64_t k = ptr[r] + 1; k < ptr[r + 1]; ++k)
-      if (ind[k] <= ind[k - 1]) {
-        *bad = 1;
-        break;
-      }
-}
-
 constexpr int kMaxCandPerLane = 16;  // up to 1024 candidates per user
 
 __global__ __launch_bounds__(64) void k_topn_1vsk(int32_t nusers, int32_t wrows, int32_t ncols,
@@ -166,8 +157,14 @@ __global__ __launch_bounds__(64) void k_topn_1vsk(int32_t nusers, int32_t wrows,
           const int64_t mid = (lo + hi) >> 1;
           if (wind[mid] < cid[k]) lo = mid + 1; else hi = mid;
         }
-        // product and sum rounded separately, like the host's `key += rating * w`
-        if (lo < t && wind[lo] == cid[k]) key[k] = __fadd_rn(key[k], __fmul_rn(rating, wval[lo]));
+        if (lo < t && wind[lo] == cid[k]) {
+          // product and sum rounded separately, like the host's `key += rating * w` (__fmul_rn and
+          // __fadd_rn are plain operators to the compiler: it fused them into one FMA, and rated
+          // histories scored an ulp off the host)
+#pragma clang fp contract(off)
+          const float prod = rating * wval[lo];
+          key[k] = key[k] + prod;
+        }
       }
     }
     // emit_best: descending score, ties in candidate order; nrcmds rounds of a wave arg-max
@@ -209,21 +206,9 @@ __global__ __launch_bounds__(64) void k_topn_1vsk(int32_t nusers, int32_t wrows,
   }
 }
 
-int cu_count() {
-  int dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-  return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-}
-
 template <class T>
 void upload(DeviceBuffer<T>& b, const T* src, size_t n) {
   if (n) HIP_TRY(hipMemcpy(b.get(), src, sizeof(T) * n, hipMemcpyHostToDevice));
-}
-
-int32_t fail(const char* who, const HipFail& e) {
-  set_error(std::string(who) + ": HIP error '" + hipGetErrorString(e.code) + "' in " + e.where);
-  return status_of(e);
 }
 
 }  // namespace
@@ -255,21 +240,17 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
   if (nusers <= 0) return SLIM_OK;
   try {
     (void)hipGetLastError();
-    const int64_t tnnz = tst->rowptr[nusers];
-    DeviceBuffer<int32_t> d_lists((size_t)nusers * nrcmds), d_counts((size_t)nusers), d_tind((size_t)tnnz),
+    DeviceBuffer<int32_t> d_lists((size_t)nusers * nrcmds), d_counts((size_t)nusers),
         d_fm((size_t)std::max(fm_ncols, 1));
-    DeviceBuffer<int64_t> d_tptr((size_t)nusers + 1);
+    const StagedCsr t = stage_csr(tst, nusers, /*values=*/false, /*stream=*/nullptr);
     DeviceBuffer<UserTerms> d_terms((size_t)nusers);
     DeviceBuffer<EvalSums> d_sums(1);
     upload(d_lists, lists, (size_t)nusers * nrcmds);
     upload(d_counts, counts, (size_t)nusers);
-    static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
-    upload(d_tptr, reinterpret_cast<const int64_t*>(tst->rowptr), (size_t)nusers + 1);
-    upload(d_tind, tst->rowind, (size_t)tnnz);
     upload(d_fm, fmarker, (size_t)fm_ncols);
     // every user, one cutoff: the lists are as long as the caller made them
     launch_user_terms(nullptr, cu_count(), nusers, nullptr, nrcmds, one_cutoff(nrcmds), d_lists.get(),
-                      d_counts.get(), d_tptr.get(), d_tind.get(), d_fm.get(), fm_ncols, d_terms.get());
+                      d_counts.get(), t.ptr.get(), t.ind.get(), d_fm.get(), fm_ncols, d_terms.get());
     launch_sum_in_user_order(nullptr, nusers, 1, d_terms.get(), d_sums.get());
     EvalSums h;
     HIP_TRY(hipMemcpy(&h, d_sums.get(), sizeof(h), hipMemcpyDeviceToHost));
@@ -284,15 +265,15 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
     out->arhr = n[0] > 0 ? f[3] / n[0] : 0;
     return SLIM_OK;
   } catch (const HipFail& e) {
-    return fail("SLIMGPU_Evaluate", e);
+    return hip_failure("SLIMGPU_Evaluate", e);
   }
 }
 
 int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
                             int32_t nnegs, const int32_t* negitems, int32_t* output,
                             float* scores) {
-  if (!W || !hist || !W->rowptr || !hist->rowptr || nrcmds < 1 || nnegs < 1 || !negitems ||
-      nnegs > 64 * kMaxCandPerLane) {
+  if (!W || !hist || !W->rowptr || !hist->rowptr || (!W->rowval && W->rowptr[W->nrows] > 0) || nrcmds < 1 ||
+      nnegs < 1 || !negitems || nnegs > 64 * kMaxCandPerLane) {
     set_error("SLIMGPU_Predict1vsK: bad arguments (1 <= nnegs <= 1024)");
     return SLIM_ERROR_INPUT;
   }
@@ -300,34 +281,19 @@ int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t
   if (nusers <= 0) return SLIM_ERROR;
   try {
     (void)hipGetLastError();
-    const int64_t wnnz = W->rowptr[W->nrows], hnnz = hist->rowptr[nusers];
-    DeviceBuffer<int64_t> d_wptr((size_t)W->nrows + 1), d_hptr((size_t)nusers + 1);
-    DeviceBuffer<int32_t> d_wind((size_t)wnnz), d_hind((size_t)hnnz), d_neg((size_t)nusers * nnegs),
-        d_oid((size_t)nusers * nrcmds), d_bad(1);
-    DeviceBuffer<float> d_wval((size_t)wnnz), d_hval(hist->rowval ? (size_t)hnnz : 1),
-        d_osc((size_t)nusers * nrcmds);
-    upload(d_wptr, reinterpret_cast<const int64_t*>(W->rowptr), (size_t)W->nrows + 1);
-    upload(d_hptr, reinterpret_cast<const int64_t*>(hist->rowptr), (size_t)nusers + 1);
-    upload(d_wind, W->rowind, (size_t)wnnz);
-    upload(d_wval, W->rowval, (size_t)wnnz);
-    upload(d_hind, hist->rowind, (size_t)hnnz);
-    if (hist->rowval) upload(d_hval, hist->rowval, (size_t)hnnz);
+    const StagedCsr w = stage_csr(W, W->nrows, /*values=*/true, /*stream=*/nullptr);
+    const StagedCsr h = stage_csr(hist, nusers, /*values=*/true, /*stream=*/nullptr);
+    DeviceBuffer<int32_t> d_neg((size_t)nusers * nnegs), d_oid((size_t)nusers * nrcmds);
+    DeviceBuffer<float> d_osc((size_t)nusers * nrcmds);
     upload(d_neg, negitems, (size_t)nusers * nnegs);
-    HIP_TRY(hipMemset(d_bad.get(), 0, sizeof(int32_t)));
     const int cus = cu_count();
-    hipLaunchKernelGGL(k_rows_ascending, dim3(std::max(1, std::min(W->nrows / 256 + 1, cus * 8))),
-                       dim3(256), 0, 0, W->nrows, d_wptr.get(), d_wind.get(), d_bad.get());
-    HIP_TRY(hipGetLastError());
-    int32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, d_bad.get(), sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (bad) {
+    if (!rows_ascend_strictly(cus, W->nrows, w.ptr.get(), w.ind.get())) {
       set_error("SLIMGPU_Predict1vsK: model rows are not ascending by item id");
       return SLIM_ERROR_INPUT;
     }
     hipLaunchKernelGGL(k_topn_1vsk, dim3(std::max(1, std::min(nusers, cus * 16))), dim3(64), 0, 0,
-                       nusers, W->nrows, W->ncols, nrcmds, nnegs, d_wptr.get(), d_wind.get(), d_wval.get(),
-                       d_hptr.get(), d_hind.get(), hist->rowval ? d_hval.get() : nullptr, d_neg.get(), d_oid.get(),
-                       d_osc.get());
+                       nusers, W->nrows, W->ncols, nrcmds, nnegs, w.ptr.get(), w.ind.get(), w.val.get(), h.ptr.get(),
+                       h.ind.get(), h.val.get(), d_neg.get(), d_oid.get(), d_osc.get());
     HIP_TRY(hipGetLastError());
     const int32_t n = std::min(nnegs, nrcmds);
     std::vector<int32_t> h_id((size_t)nusers * nrcmds);
@@ -341,7 +307,7 @@ int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t
       }
     return SLIM_OK;
   } catch (const HipFail& e) {
-    return fail("SLIMGPU_Predict1vsK", e);
+    return hip_failure("SLIMGPU_Predict1vsK", e);
   }
 }
 

@@ -16,7 +16,13 @@
 //     in the W row), which sorts like the host's discovery counter;
 //   * selection: one pass over the score vector with a per-lane sorted list of the N best
 //     (LDS), then N rounds of a wave-wide arg-max over the 64 list heads.
-// The score/discovery vectors (12 bytes per item) live in a per-wavefront HBM slab.
+// The score/discovery vectors (12 bytes per item) live in a per-wavefront HBM slab.  A second kernel
+// (topn_chunk_kernel, below) keeps them in LDS and serves lists of up to 64 from models with sorted rows.
+//
+// Host side: every entry point -- predict_device / predict_device_view (a host history), matrix_predict
+// and model_evaluate (the resident matrix) -- stages what it lacks on the device (host_stage.hpp),
+// describes the model and the histories as views and goes through queue_scorer, the one place that
+// chooses the kernel, builds the split table, fills the kernel arguments and launches.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -33,6 +39,7 @@
 #include "eval_terms.hpp"
 #include "hip_check.hpp"
 #include "host_csr.hpp"
+#include "host_stage.hpp"
 
 namespace slimamd {
 
@@ -62,8 +69,8 @@ struct slimgpu_evalset {
   slimamd::Cutoffs cut = {};       // list lengths; the lists scored have the last one's
   int64_t hist_entries = 0;  // history entries of the evaluated users: the model rows one evaluation streams
   int64_t max_hist = 0;      // the longest of those histories
-  slimamd::DeviceBuffer<int64_t> d_tptr;
-  slimamd::DeviceBuffer<int32_t> d_tind, d_fm, d_users;
+  slimamd::StagedCsr tst;  // the test rows of the matrix's users (ids only)
+  slimamd::DeviceBuffer<int32_t> d_fm, d_users;
   slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;  // [cut.n][nsel]
   slimamd::DeviceBuffer<unsigned long long> d_out;    // EvalOut
   slimamd::ScorerWorkspace ws;
@@ -316,6 +323,21 @@ __global__ void k_rows_sorted(int32_t nrows, const int64_t* __restrict__ ptr,
     if (bad) atomicExch(unsorted, 1);
   }
 }
+
+}  // namespace
+
+bool rows_ascend_strictly(int num_cus, int32_t nrows, const int64_t* d_ptr, const int32_t* d_ind) {
+  DeviceBuffer<int32_t> d_unsorted(1);
+  HIP_TRY(hipMemset(d_unsorted.get(), 0, sizeof(int32_t)));
+  hipLaunchKernelGGL(k_rows_sorted, dim3(std::max(1, std::min(nrows / 4 + 1, num_cus * 8))), dim3(256), 0, 0, nrows,
+                     d_ptr, d_ind, d_unsorted.get());
+  HIP_TRY(hipGetLastError());
+  int32_t unsorted = 0;
+  HIP_TRY(hipMemcpy(&unsorted, d_unsorted.get(), sizeof(int32_t), hipMemcpyDeviceToHost));
+  return unsorted == 0;
+}
+
+namespace {
 
 // wsplit[r][c] = number of ids of row r below c * cw (binary search; rows are sorted)
 __global__ void k_row_split(int32_t nrows, int32_t nchunks, int32_t cw,
@@ -698,214 +720,11 @@ ChunkPlan plan_chunks(int32_t ncols, int64_t max_row, int64_t max_hist, bool for
 }
 constexpr size_t kSplitLimit = size_t(2) << 30;  // bytes of split table beyond which the wave kernel serves
 
-}  // namespace
-
-// Top-N lists of every history row.  output/scores are [nusers][nrcmds], slots beyond a
-// user's list length are left as the caller filled them; counts (optional) = list lengths.
-// W: its row view on the device -- uploaded by predict_device (host model), or where a resident model
-// already holds it (predict_device_view: nothing of W crosses PCIe).
-int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
-                            int32_t* output, float* scores, int32_t* counts) {
-  if (!hist || !hist->rowptr || !W.d_ptr || nrcmds < 1 || nrcmds > 128) {
-    set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
-    return SLIM_ERROR_INPUT;
-  }
-  const int32_t nusers = hist->nrows;
-  const int32_t ncols = std::max(W.ncols, 1);
-  const int64_t wnnz = W.nnz, hnnz = hist->rowptr[nusers];
-  const auto t_begin = std::chrono::steady_clock::now();
-  try {
-    (void)hipGetLastError();  // a failure of an earlier call must not be reported by this one
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
-    hipDeviceProp_t prop;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    const int64_t* d_wptr = W.d_ptr;
-    const int32_t* d_wind = W.d_ind;
-    const float* d_wval = W.d_val;
-    DeviceBuffer<int64_t> d_hptr((size_t)nusers + 1);
-    DeviceBuffer<int32_t> d_hind((size_t)hnnz);
-    DeviceBuffer<float> d_hval(hist->rowval ? (size_t)hnnz : 1);
-    DeviceBuffer<float> d_oscore((size_t)nusers * nrcmds);
-    DeviceBuffer<int32_t> d_oid((size_t)nusers * nrcmds), d_ocnt((size_t)nusers), d_queue(2);
-    HIP_TRY(hipMemcpy(d_hptr.get(), hist->rowptr, sizeof(int64_t) * ((size_t)nusers + 1), hipMemcpyHostToDevice));
-    if (hnnz) {
-      HIP_TRY(hipMemcpy(d_hind.get(), hist->rowind, sizeof(int32_t) * (size_t)hnnz, hipMemcpyHostToDevice));
-      if (hist->rowval)
-        HIP_TRY(hipMemcpy(d_hval.get(), hist->rowval, sizeof(float) * (size_t)hnnz, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemset(d_queue.get(), 0, 2 * sizeof(int32_t)));
-    HIP_TRY(hipMemset(d_ocnt.get(), 0, sizeof(int32_t) * (size_t)nusers));
-
-    // kernel choice: score chunks in LDS (lists of up to 64, rows of W sorted by id), else the
-    // one-wavefront-per-user kernel with its vectors in HBM.  SLIM_TOPN_KERNEL=wave|chunk and
-    // SLIM_TOPN_CW=<chunk width> override (tests).
-    const char* kenv = std::getenv("SLIM_TOPN_KERNEL");
-    bool chunked = nrcmds <= kT2MaxN && wnnz < (int64_t(1) << 31) &&
-                   !(kenv && std::strcmp(kenv, "wave") == 0);
-    if (chunked) {
-      int32_t unsorted = 0;
-      if (wnnz > 0 && !W.rows_sorted) {
-        hipLaunchKernelGGL(k_rows_sorted, dim3(std::max(1, std::min(W.nrows / 4 + 1, prop.multiProcessorCount * 8))),
-                           dim3(256), 0, 0, W.nrows, d_wptr, d_wind, d_queue.get() + 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(&unsorted, d_queue.get() + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-      }
-      if (unsorted) chunked = false;
-    }
-    int64_t max_hist = 0;
-    for (int32_t u = 0; u < nusers; ++u) max_hist = std::max<int64_t>(max_hist, hist->rowptr[u + 1] - hist->rowptr[u]);
-    const ChunkPlan P = plan_chunks(ncols, W.max_row, max_hist, false);
-    const int t2w = P.t2w, pos_bits = P.pos_bits, cw = P.cw, nchunks = P.nchunks;
-    const bool key32 = P.key32;
-    if (chunked && (size_t)W.nrows * ((size_t)nchunks + 1) * sizeof(uint32_t) > kSplitLimit)
-      chunked = false;
-    if (kenv && std::strcmp(kenv, "chunk") == 0 && !chunked) {
-      set_error("SLIMGPU_Predict: SLIM_TOPN_KERNEL=chunk needs nrcmds <= 64 and model rows sorted by id");
-      return SLIM_ERROR_INPUT;
-    }
-
-    if (chunked) {
-      DeviceBuffer<uint32_t> d_split((size_t)std::max(W.nrows, 1) * ((size_t)nchunks + 1));
-      if (W.nrows > 0) {
-        const int64_t total = (int64_t)W.nrows * (nchunks + 1);
-        hipLaunchKernelGGL(k_row_split, dim3((unsigned)std::min<int64_t>((total + 255) / 256, prop.multiProcessorCount * 16)),
-                           dim3(256), 0, 0, W.nrows, nchunks, cw, d_wptr, d_wind, d_split.get());
-        HIP_TRY(hipGetLastError());
-      }
-      TopN2Args T{};
-      T.nusers = nusers;
-      T.nitems_rows = W.nrows;
-      T.ncols = ncols;
-      T.nrcmds = nrcmds;
-      T.cw = cw;
-      T.nchunks = nchunks;
-      T.pos_bits = pos_bits;
-      T.wlast = wnnz > 0 ? (uint32_t)(wnnz - 1) : 0u;
-      T.wptr = d_wptr; T.wind = d_wind; T.wval = d_wval; T.wsplit = d_split.get();
-      T.hptr = d_hptr.get(); T.hind = d_hind.get(); T.hval = hist->rowval ? d_hval.get() : nullptr;
-      T.out_ids = d_oid.get(); T.out_scores = d_oscore.get(); T.out_cnt = d_ocnt.get(); T.queue = d_queue.get();
-      const size_t lds = P.lds;
-      auto kfn = key32 ? (t2w == 16 ? topn_chunk_kernel<16, uint32_t> : topn_chunk_kernel<8, uint32_t>)
-                       : (t2w == 16 ? topn_chunk_kernel<16, unsigned long long>
-                                    : topn_chunk_kernel<8, unsigned long long>);
-      if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / t2w, (160 * 1024) / (lds + 64)));
-      const int nwg = std::max(1, std::min<int>(nusers, prop.multiProcessorCount * per_cu));
-      const auto t_k0 = std::chrono::steady_clock::now();
-      hipLaunchKernelGGL(kfn, dim3(nwg), dim3(64 * t2w), lds, 0, T);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-      if (std::getenv("SLIM_GPU_TRACE"))
-        std::fprintf(stderr, "[trace] top-N chunk kernel: %d users, %d workgroups of %d wavefronts, chunks of %d ids, "
-                             "%d-bit keys: %.1f ms (upload + split table before it: %.1f ms)\n",
-                     nusers, nwg, t2w, cw, key32 ? 32 : 64,
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_k0).count(),
-                     std::chrono::duration<double, std::milli>(t_k0 - t_begin).count());
-    } else {
-      const size_t lds = (size_t)nrcmds * 64 * (sizeof(float) + sizeof(unsigned long long) + sizeof(int));
-      int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (128 * 1024) / lds));
-      const int nwaves = std::max(1, std::min<int>(nusers, prop.multiProcessorCount * per_cu));
-      DeviceBuffer<float> d_score((size_t)nwaves * ncols);
-      DeviceBuffer<unsigned long long> d_disc((size_t)nwaves * ncols);
-      TopNArgs T;
-      T.nusers = nusers;
-      T.nitems_rows = W.nrows;
-      T.ncols = ncols;
-      T.nrcmds = nrcmds;
-      T.wptr = d_wptr; T.wind = d_wind; T.wval = d_wval;
-      T.hptr = d_hptr.get(); T.hind = d_hind.get(); T.hval = hist->rowval ? d_hval.get() : nullptr;
-      T.score = d_score.get(); T.disc = d_disc.get();
-      T.out_ids = d_oid.get(); T.out_scores = d_oscore.get(); T.out_cnt = d_ocnt.get(); T.queue = d_queue.get();
-      if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(topn_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(topn_kernel, dim3(nwaves), dim3(64), lds, 0, T);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-
-    std::vector<int32_t> h_id((size_t)nusers * nrcmds), h_cnt((size_t)nusers);
-    std::vector<float> h_sc((size_t)nusers * nrcmds);
-    HIP_TRY(hipMemcpy(h_id.data(), d_oid.get(), sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_sc.data(), d_oscore.get(), sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_cnt.data(), d_ocnt.get(), sizeof(int32_t) * h_cnt.size(), hipMemcpyDeviceToHost));
-    for (int32_t u = 0; u < nusers; ++u) {
-      for (int32_t r = 0; r < h_cnt[u]; ++r) {
-        output[(int64_t)u * nrcmds + r] = h_id[(size_t)u * nrcmds + r];
-        scores[(int64_t)u * nrcmds + r] = h_sc[(size_t)u * nrcmds + r];
-      }
-      if (counts) counts[u] = h_cnt[u];
-    }
-    return SLIM_OK;
-  } catch (const HipFail& e) {
-    set_error(std::string("SLIMGPU_Predict: HIP error '") + hipGetErrorString(e.code) + "' in " +
-              e.where);
-    return status_of(e);
-  } catch (const std::bad_alloc&) {
-    set_error("SLIMGPU_Predict: out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
-}
-
-
-int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
-                       int32_t* output, float* scores, int32_t* counts) {
-  if (!W || !hist || !W->rowptr || !hist->rowptr || nrcmds < 1 || nrcmds > 128) {
-    set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
-    return SLIM_ERROR_INPUT;
-  }
-  try {
-    (void)hipGetLastError();
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
-    const int64_t wnnz = W->rowptr[W->nrows];
-    DeviceBuffer<int64_t> d_wptr((size_t)W->nrows + 1);
-    DeviceBuffer<int32_t> d_wind((size_t)wnnz);
-    DeviceBuffer<float> d_wval((size_t)wnnz);
-    HIP_TRY(hipMemcpy(d_wptr.get(), W->rowptr, sizeof(int64_t) * ((size_t)W->nrows + 1), hipMemcpyHostToDevice));
-    if (wnnz) {
-      HIP_TRY(hipMemcpy(d_wind.get(), W->rowind, sizeof(int32_t) * (size_t)wnnz, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(d_wval.get(), W->rowval, sizeof(float) * (size_t)wnnz, hipMemcpyHostToDevice));
-    }
-    DeviceRowView v;
-    v.nrows = W->nrows;
-    v.ncols = W->ncols;
-    v.nnz = wnnz;
-    v.d_ptr = d_wptr.get();
-    v.d_ind = d_wind.get();
-    v.d_val = d_wval.get();
-    for (int32_t r = 0; r < W->nrows; ++r) v.max_row = std::max<int64_t>(v.max_row, W->rowptr[r + 1] - W->rowptr[r]);
-    return predict_device_view(v, hist, nrcmds, output, scores, counts);
-  } catch (const HipFail& e) {
-    set_error(std::string("SLIMGPU_Predict: HIP error '") + hipGetErrorString(e.code) + "' in " + e.where);
-    return status_of(e);
-  }
-}
-
-// ---- a resident model against the resident matrix ----------------------------------------------
+// ---- the launch path -----------------------------------------------------------------------------
 //
-// The evaluate half of a model-selection cell without the host: the history is the staged matrix's CSR
-// where it lies, the model is a resident model's row view, the test rows and the head / tail marker
-// were staged once (slimgpu_evalset).  One fused kernel scores, selects and forms every user's terms;
-// k_sum_in_user_order adds them; 8 + 32 bytes per cutoff come down.  The evaluated users are the matrix's
-// first rows or a sorted list of them (positions, eval_terms.hpp); several list lengths are served by the
-// one scoring pass of the longest.
-namespace {
-
-thread_local slimgpu_eval_stats_t g_eval_stats;
-
-struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoffs bytes
-  unsigned long long streamed;  // entries of the model rows streamed
-  EvalSums sums[SLIMGPU_MAX_CUTOFFS];
-};
-
+// Every entry point describes its model (DeviceRowView) and its histories (HistoryView) and queues the
+// scorer through queue_scorer: the kernel choice, the split table, the kernel arguments, LDS and grid
+// exist here only.
 struct HistoryView {
   int32_t nusers = 0;               // positions
   const int32_t* users = nullptr;   // the user of every position; nullptr: position q is user q
@@ -957,13 +776,24 @@ void reserve_scorer(ScorerWorkspace& ws, int path, int32_t wrows, int32_t ncols,
   }
 }
 
+// How queue_scorer served a call.
+struct ScorerLaunch {
+  int path = 0;    // scorer_path
+  int groups = 0;  // workgroups of the chunk kernel, wavefronts of the wave kernel
+  ChunkPlan plan;  // the chunk kernel's geometry
+  std::chrono::steady_clock::time_point launched;  // host time at which the scorer kernel itself was queued
+};
+
 // Queues the scorer on `stream`: lists into ws.oid / osc / ocnt when `lists` (always on path 2), the
-// users' terms into ev->terms when ev is given.  Returns the path taken.
-int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, int num_cus, hipStream_t stream,
-                 ScorerWorkspace& ws, const EvalTargets* ev, bool lists) {
+// users' terms into ev->terms when ev is given.
+ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, int num_cus,
+                          hipStream_t stream, ScorerWorkspace& ws, const EvalTargets* ev, bool lists) {
   const int32_t ncols = std::max(W.ncols, 1);
   const ChunkPlan P = plan_chunks(ncols, W.max_row, H.max_hist, false);
   const int path = scorer_path(W, nrcmds, P);
+  ScorerLaunch L;
+  L.path = path;
+  L.plan = P;
   reserve_scorer(ws, path, W.nrows, ncols, P, H.nusers, nrcmds, num_cus, lists);
   HIP_TRY(hipMemsetAsync(ws.queue.get(), 0, 2 * sizeof(int32_t), stream));
   if (lists || path == 2) HIP_TRY(hipMemsetAsync(ws.ocnt.get(), 0, sizeof(int32_t) * (size_t)H.nusers, stream));
@@ -1006,6 +836,8 @@ int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, i
                                    (int)P.lds));
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / P.t2w, (160 * 1024) / (P.lds + 64)));
     const int nwg = std::max(1, std::min<int>(H.nusers, num_cus * per_cu));
+    L.groups = nwg;
+    L.launched = std::chrono::steady_clock::now();
     hipLaunchKernelGGL(kfn, dim3(nwg), dim3(64 * P.t2w), P.lds, stream, T);
     HIP_TRY(hipGetLastError());
   } else {
@@ -1024,23 +856,141 @@ int queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, i
     if (lds > 64 * 1024)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(topn_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    L.groups = nwaves;
+    L.launched = std::chrono::steady_clock::now();
     hipLaunchKernelGGL(topn_kernel, dim3(nwaves), dim3(64), lds, stream, T);
     HIP_TRY(hipGetLastError());
     if (ev)
       launch_user_terms(stream, num_cus, H.nusers, H.users, nrcmds, ev->cut, ws.oid.get(), ws.ocnt.get(), ev->tptr,
                         ev->tind, ev->fmarker, ev->fm_ncols, ev->terms);
   }
-  return path;
+  return L;
+}
+
+// Brings the lists of a scorer queued on `stream` down and copies the counts[u] entries of every user's
+// list; the slots beyond a list stay as the caller filled them.  counts is optional.  Returns the bytes
+// that came down.
+size_t fetch_lists(const ScorerWorkspace& ws, int32_t nusers, int32_t nrcmds, hipStream_t stream, int32_t* output,
+                   float* scores, int32_t* counts) {
+  if (nusers <= 0) return 0;
+  std::vector<int32_t> h_id((size_t)nusers * nrcmds), h_cnt((size_t)nusers);
+  std::vector<float> h_sc((size_t)nusers * nrcmds);
+  HIP_TRY(hipMemcpyAsync(h_id.data(), ws.oid.get(), sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(h_sc.data(), ws.osc.get(), sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(h_cnt.data(), ws.ocnt.get(), sizeof(int32_t) * h_cnt.size(), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int32_t u = 0; u < nusers; ++u) {
+    for (int32_t r = 0; r < h_cnt[u]; ++r) {
+      output[(int64_t)u * nrcmds + r] = h_id[(size_t)u * nrcmds + r];
+      scores[(int64_t)u * nrcmds + r] = h_sc[(size_t)u * nrcmds + r];
+    }
+    if (counts) counts[u] = h_cnt[u];
+  }
+  return sizeof(int32_t) * (h_id.size() + h_cnt.size()) + sizeof(float) * h_sc.size();
 }
 
 double ms_since(const std::chrono::steady_clock::time_point& t) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
-int32_t hip_failure(const char* who, const HipFail& e) {
-  set_error(std::string(who) + ": HIP error '" + hipGetErrorString(e.code) + "' in " + e.where);
-  return status_of(e);
+}  // namespace
+
+// Top-N lists of every history row.  output/scores are [nusers][nrcmds], slots beyond a
+// user's list length are left as the caller filled them; counts (optional) = list lengths.
+// W: its row view on the device -- uploaded by predict_device (host model), or where a resident model
+// already holds it (nothing of W crosses PCIe).  The history is staged, the scorer queued on the null
+// stream through queue_scorer, the lists brought down.  Only here, SLIM_TOPN_KERNEL=chunk is an error
+// when the chunk kernel cannot serve (the resident entry points fall back to the wave kernel).
+int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
+                            int32_t* output, float* scores, int32_t* counts) {
+  if (!hist || !hist->rowptr || !W.d_ptr || nrcmds < 1 || nrcmds > 128) {
+    set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
+    return SLIM_ERROR_INPUT;
+  }
+  const int32_t nusers = hist->nrows;
+  const auto t_begin = std::chrono::steady_clock::now();
+  try {
+    (void)hipGetLastError();  // a failure of an earlier call must not be reported by this one
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
+    if (W.device >= 0) HIP_TRY(hipSetDevice(W.device));
+    const int num_cus = cu_count();
+    const StagedCsr h = stage_csr(hist, nusers, /*values=*/true, /*stream=*/nullptr);
+    HistoryView H;
+    H.nusers = nusers;
+    H.ptr = h.ptr.get(); H.ind = h.ind.get(); H.val = h.val.get();
+    H.max_hist = h.max_row;
+    DeviceRowView V = W;
+    if (!V.rows_sorted && V.nnz > 0) V.rows_sorted = rows_ascend_strictly(num_cus, V.nrows, V.d_ptr, V.d_ind);
+    const char* kenv = std::getenv("SLIM_TOPN_KERNEL");
+    if (kenv && std::strcmp(kenv, "chunk") == 0 &&
+        scorer_path(V, nrcmds, plan_chunks(std::max(V.ncols, 1), V.max_row, H.max_hist, false)) != 1) {
+      set_error("SLIMGPU_Predict: SLIM_TOPN_KERNEL=chunk needs nrcmds <= 64 and model rows sorted by id");
+      return SLIM_ERROR_INPUT;
+    }
+    ScorerWorkspace ws;
+    const ScorerLaunch L =
+        queue_scorer(V, H, nrcmds, num_cus, /*stream=*/nullptr, ws, /*ev=*/nullptr, /*lists=*/true);
+    HIP_TRY(hipDeviceSynchronize());
+    if (L.path == 1 && std::getenv("SLIM_GPU_TRACE"))
+      std::fprintf(stderr, "[trace] top-N chunk kernel: %d users, %d workgroups of %d wavefronts, chunks of %d ids, "
+                           "%d-bit keys: %.1f ms (upload + split table before it: %.1f ms)\n",
+                   nusers, L.groups, L.plan.t2w, L.plan.cw, L.plan.key32 ? 32 : 64, ms_since(L.launched),
+                   std::chrono::duration<double, std::milli>(L.launched - t_begin).count());
+    fetch_lists(ws, nusers, nrcmds, nullptr, output, scores, counts);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_Predict", e);
+  } catch (const std::bad_alloc&) {
+    set_error("SLIMGPU_Predict: out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
 }
+
+int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
+                       int32_t* output, float* scores, int32_t* counts) {
+  if (!W || !hist || !W->rowptr || !hist->rowptr || (!W->rowval && W->rowptr[W->nrows] > 0) || nrcmds < 1 ||
+      nrcmds > 128) {
+    set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
+    return SLIM_ERROR_INPUT;
+  }
+  try {
+    (void)hipGetLastError();
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
+    const StagedCsr w = stage_csr(W, W->nrows, /*values=*/true, /*stream=*/nullptr);
+    DeviceRowView v;
+    v.nrows = W->nrows;
+    v.ncols = W->ncols;
+    v.nnz = w.nnz;
+    v.max_row = w.max_row;
+    v.d_ptr = w.ptr.get();
+    v.d_ind = w.ind.get();
+    v.d_val = w.val.get();
+    return predict_device_view(v, hist, nrcmds, output, scores, counts);
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_Predict", e);
+  }
+}
+
+// ---- a resident model against the resident matrix ----------------------------------------------
+//
+// The evaluate half of a model-selection cell without the host: the history is the staged matrix's CSR
+// where it lies, the model is a resident model's row view, the test rows and the head / tail marker
+// were staged once (slimgpu_evalset).  One fused kernel scores, selects and forms every user's terms;
+// k_sum_in_user_order adds them; 8 + 32 bytes per cutoff come down.  The evaluated users are the matrix's
+// first rows or a sorted list of them (positions, eval_terms.hpp); several list lengths are served by the
+// one scoring pass of the longest.
+namespace {
+
+thread_local slimgpu_eval_stats_t g_eval_stats;
+
+struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoffs bytes
+  unsigned long long streamed;  // entries of the model rows streamed
+  EvalSums sums[SLIMGPU_MAX_CUTOFFS];
+};
 
 // the matrix and the model of one call: one device, one width, rows that are the caller's
 int32_t check_pair(const char* who, const DeviceCsrView& R, const DeviceRowView& W) {
@@ -1122,16 +1072,10 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
     es->cut = cut;
     es->fm_ncols = fm_ncols;
     const int32_t nsel = es->nsel;
-    const int64_t tnnz = tst->rowptr[nall];
-    es->d_tptr = DeviceBuffer<int64_t>((size_t)nall + 1);
-    es->d_tind = DeviceBuffer<int32_t>((size_t)tnnz);
+    es->tst = stage_csr(tst, nall, /*values=*/false, stream);
     es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
     es->d_terms = DeviceBuffer<UserTerms>((size_t)cut.n * (size_t)nsel);
     es->d_out = DeviceBuffer<unsigned long long>(sizeof(EvalOut) / sizeof(unsigned long long));
-    static_assert(sizeof(ssize_t) == sizeof(int64_t), "LP64 expected");
-    HIP_TRY(hipMemcpyAsync(es->d_tptr.get(), tst->rowptr, sizeof(int64_t) * ((size_t)nall + 1), hipMemcpyHostToDevice, stream));
-    if (tnnz > 0)
-      HIP_TRY(hipMemcpyAsync(es->d_tind.get(), tst->rowind, sizeof(int32_t) * (size_t)tnnz, hipMemcpyHostToDevice, stream));
     if (fm_ncols > 0)
       HIP_TRY(hipMemcpyAsync(es->d_fm.get(), fmarker, sizeof(int32_t) * (size_t)fm_ncols, hipMemcpyHostToDevice, stream));
     if (users) {  // (pageable source: the copy has left the caller's array when the call returns)
@@ -1214,10 +1158,10 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
       H.users = es->listed ? es->d_users.get() : nullptr;
       H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
       H.max_hist = es->max_hist;
-      const EvalTargets ev = {es->d_tptr.get(), es->d_tind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get(), es->cut};
+      const EvalTargets ev = {es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get(), es->cut};
       EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
       HIP_TRY(hipEventRecord(es->ev0, stream));
-      st.path = queue_scorer(W, H, es->cut.c[ncut - 1], R.num_cus, stream, es->ws, &ev, /*lists=*/false);
+      st.path = queue_scorer(W, H, es->cut.c[ncut - 1], R.num_cus, stream, es->ws, &ev, /*lists=*/false).path;
       launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), d_out->sums);
       HIP_TRY(hipEventRecord(es->ev1, stream));
       HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
@@ -1294,25 +1238,14 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
       HIP_TRY(hipEventCreate(&ev0));
       HIP_TRY(hipEventCreate(&ev1));
       HIP_TRY(hipEventRecord(ev0, stream));
-      st.path = queue_scorer(W, H, nrcmds, R.num_cus, stream, ws, nullptr, /*lists=*/true);
+      st.path = queue_scorer(W, H, nrcmds, R.num_cus, stream, ws, nullptr, /*lists=*/true).path;
       HIP_TRY(hipEventRecord(ev1, stream));
-      // only the lists come down; slots beyond a list's length stay as the caller filled them
-      std::vector<int32_t> h_id((size_t)nu * nrcmds), h_cnt((size_t)nu);
-      std::vector<float> h_sc((size_t)nu * nrcmds);
-      HIP_TRY(hipMemcpyAsync(h_id.data(), ws.oid.get(), sizeof(int32_t) * h_id.size(), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipMemcpyAsync(h_sc.data(), ws.osc.get(), sizeof(float) * h_sc.size(), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipMemcpyAsync(h_cnt.data(), ws.ocnt.get(), sizeof(int32_t) * h_cnt.size(), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      for (int32_t u = 0; u < nu; ++u)
-        for (int32_t r = 0; r < h_cnt[u]; ++r) {
-          output[(int64_t)u * nrcmds + r] = h_id[(size_t)u * nrcmds + r];
-          scores[(int64_t)u * nrcmds + r] = h_sc[(size_t)u * nrcmds + r];
-        }
+      // only the lists come down (and the longest history's length before them)
+      st.d2h_bytes = (int64_t)(fetch_lists(ws, nu, nrcmds, stream, output, scores, nullptr) + sizeof(int32_t));
       float ms = 0;
       HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
       st.kernel_ms = ms;
       st.device_allocs = ws.allocs;
-      st.d2h_bytes = (int64_t)(sizeof(int32_t) * (h_id.size() + h_cnt.size()) + sizeof(float) * h_sc.size() + sizeof(int32_t));
       st.w_rows_read = R.nnz;
     }
     st.total_ms = ms_since(t_begin);
