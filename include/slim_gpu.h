@@ -122,13 +122,17 @@ typedef enum {
   SLIMGPU_KERNEL_TILE = 3,     /* one workgroup per 32 items, residuals
                                   interleaved r[user][32] in HBM (large matrices) */
   SLIMGPU_KERNEL_TILE16 = 4,   /* same with 16 items per workgroup             */
-  SLIMGPU_KERNEL_GRAM = 5      /* item-space CD: one workgroup per item, g = a_i.r over the
+  SLIMGPU_KERNEL_GRAM = 5,     /* item-space CD: one workgroup per item, g = a_i.r over the
                                   ITEMS kept on chip, an update reads one row of G = R^T R
                                   (built on the first such solve and kept with the handle: floats,
                                   and byte planes of ~1-2 bytes per entry when G is integer-valued).
                                   AUTO takes it when its byte model beats the residual kernel's
                                   (ncols^2 / nnz < 45) and the call's columns -- times the solves
-                                  announced -- pay for G; no FSLIM form                         */
+                                  announced -- pay for G; FSLIM: SLIMGPU_KERNEL_GRAM_FSLIM      */
+  SLIMGPU_KERNEL_GRAM_FSLIM = 6 /* FSLIM in item space: the neighbour lists are read off row iC of G,
+                                  the descent runs on the neighbourhood's block of G.  Needs
+                                  nnbrs > 0, ratings all > 0 and the float G on the handle (built on
+                                  first use).  Never chosen by AUTO                              */
 } slimgpu_kernel_et;
 
 /* A training matrix staged in HBM: CSR as given + the column view (CSC, rows

@@ -29,6 +29,7 @@
 #include "tile_inst.hpp"
 #include "gram_inst.hpp"
 #include "gramr_inst.hpp"
+#include "fslim_gram_inst.hpp"
 #include "cd_wave.hpp"
 #include "engine.hpp"
 #include "hip_check.hpp"
@@ -109,6 +110,9 @@ struct slimgpu_matrix {
   DeviceBuffer<int32_t> ws_order, ws_cnt, ws_stat_i, ws_misc, ws_arena_i, ws_ulist;
   DeviceBuffer<int64_t> ws_off, ws_stat_l, ws_icolptr;
   DeviceBuffer<float> ws_stat_f, ws_arena_v, ws_slab, ws_xslab, ws_part, ws_icolval;
+  // item-space FSLIM (cd_fslim_gram.hpp): the neighbour lists of a slice of the work list
+  DeviceBuffer<int32_t> ws_fn, ws_fid, ws_fslot;
+  DeviceBuffer<float> ws_faty;
   DeviceBuffer<uint64_t> ws_trace;
   // the G builder's view of the column ids (build_gview): lives for one build
   DeviceBuffer<uint4> ws_gview;
@@ -1197,6 +1201,11 @@ struct Path {
   int nwaves = 1;            // workgroups launched (tiles: re-planned by plan_tiles)
   int trace_level = 0;
   bool has_imodel = false;
+  // FSLIM in item space (cd_fslim_gram.hpp)
+  bool use_fgram = false, f_block = false;
+  int f_stride = 0, f_ustride = 0, f_tab_n = 0, f_waves = 1;
+  size_t f_wave_lds = 0, f_union_lds = 0;
+  FslimFn fn_f = nullptr;
 };
 
 // The kernel flavour, up to the item-space choice (which may need G built first).
@@ -1215,6 +1224,29 @@ Path choose_kernel(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork) {
   const bool gram_fits =
       gram_geometry(p.ncols_pad, &p.gram_nw, &p.gram_v) && opt.nnbrs == 0 && !opt.build_G && ncols > 0;
   const size_t G_bytes = sizeof(float) * (size_t)ncols * (size_t)gram_ld(ncols);
+  if (p.kernel == SLIMGPU_KERNEL_GRAM_FSLIM) {
+    // FSLIM in item space (cd_fslim_gram.hpp): only when asked for, and only where a row of the
+    // float G says who the co-rated columns are and a problem's state fits a wavefront's LDS
+    if (opt.nnbrs <= 0 || opt.build_G)
+      throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: the item-space FSLIM kernel needs nnbrs > 0"};
+    if (m->nonpositive)
+      throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: the item-space FSLIM kernel needs ratings > 0: with a rating <= 0 "
+                                      "a co-rating sum can cancel to 0 and G cannot mark the column as co-rated "
+                                      "(the tile kernel solves such matrices)"};
+    if (std::min(opt.nnbrs, ncols - 1) > kFslimMaxNbrs)
+      throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: the item-space FSLIM kernel holds at most 4096 neighbours per "
+                                      "problem in LDS (min(nnbrs, ncols - 1) is larger)"};
+    if (m->G_ready && m->Gf_dropped) {  // (this path reads the floats: form them again; the planes stay)
+      m->G_ready = false;
+      m->Gf_dropped = false;
+    }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (!m->G_ready && G_bytes + (size_t(4) << 30) > free_b + m->ws_gram.bytes())
+      throw Refusal{SLIM_ERROR_MEMORY, "SLIMGPU_Learn: G = R^T R (4 ncols^2 bytes) does not fit the free HBM"};
+    p.use_fgram = true;
+    return p;
+  }
   if (p.kernel == SLIMGPU_KERNEL_GRAM) {
     if (!gram_fits) throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: the item-space kernel has no FSLIM form"};
     size_t free_b = 0, total_b = 0;
@@ -1261,7 +1293,9 @@ Path choose_kernel(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork) {
 }
 
 // G for an item-space solve, once per handle, timed into the handle (charged to this solve's stats).
-int32_t gram_for_solve(slimgpu_matrix* m, const LearnOptions& opt, int32_t trace_level) {
+// floats_only: neither packed into byte planes nor dropped (the FSLIM path reads the floats; a later
+// plain item-space solve finds G_ready && !Gp_tried and packs then)
+int32_t gram_for_solve(slimgpu_matrix* m, const LearnOptions& opt, int32_t trace_level, bool floats_only) {
   const double tb = now_ms();
   LearnOptions bo = opt;
   bo.col_begin = 0;
@@ -1278,11 +1312,13 @@ int32_t gram_for_solve(slimgpu_matrix* m, const LearnOptions& opt, int32_t trace
   const double sums_kernel_ms = last_stats().kernel_ms;
   m->G_ready = true;
   m->Gf_dropped = false;
-  if (!m->Gp_ready) {  // (planes of an earlier build of the same G are still right)
-    m->Gp_tried = false;
-    if (!pack_gram(m)) m->Gp_ready = false;
+  if (!floats_only) {
+    if (!m->Gp_ready) {  // (planes of an earlier build of the same G are still right)
+      m->Gp_tried = false;
+      if (!pack_gram(m)) m->Gp_ready = false;
+    }
+    drop_float_gram(m);
   }
-  drop_float_gram(m);
   m->G_build_ms = now_ms() - tb;
   m->G_alloc_ms = alloc_ms;
   m->G_sums_ms = t_sums - tb - alloc_ms;
@@ -1304,8 +1340,41 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
     p.kernel = p.lds_need <= 64 * 1024 ? SLIMGPU_KERNEL_WAVE_LDS : SLIMGPU_KERNEL_TILE;
   if (p.kernel == SLIMGPU_KERNEL_WAVE_LDS && p.lds_need > 160 * 1024)
     throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: work vectors do not fit the 160 KiB LDS of a CU"};
-  if (p.kernel < SLIMGPU_KERNEL_WAVE_LDS || p.kernel > SLIMGPU_KERNEL_GRAM)
+  if (p.kernel < SLIMGPU_KERNEL_WAVE_LDS || p.kernel > SLIMGPU_KERNEL_GRAM_FSLIM)
     throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: unknown kernel selection"};
+  if (p.use_fgram) {
+    // lists of min(nnbrs, ncols - 1) entries, rounded up to a wavefront; a tile's union holds at most
+    // 32 of them.  The nn x nn block of G goes to LDS up to 128 neighbours (16 KB / 64 KB per
+    // wavefront); beyond, or with SLIM_GPU_FSLIM_BLOCK=0, its entries are gathered per update.
+    p.f_stride = std::max(64, round_up(std::min(opt.nnbrs, m->ncols - 1), 64));
+    p.f_ustride = (int)std::min<int64_t>((int64_t)32 * p.f_stride, p.ncols_pad);
+    p.f_block = p.f_stride <= kFslimBlockMaxStride;
+    if (const char* e = std::getenv("SLIM_GPU_FSLIM_BLOCK")) p.f_block = p.f_block && std::atoi(e) != 0;
+    p.f_tab_n = p.f_block ? round_up(p.f_ustride, 8) : 0;
+    p.f_wave_lds = fslim_wave_lds(p.f_stride, p.f_block, p.f_tab_n);
+    p.f_waves = (int)std::max<size_t>(1, std::min<size_t>(p.f_block ? kFslimMaxWaves : 4, (size_t(150) << 10) / p.f_wave_lds));
+    p.fn_f = fslim_solve_fn(p.f_block);
+    p.f_union_lds = fslim_union_lds(m->ncols);
+    if (p.f_union_lds > (size_t(150) << 10))
+      throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_Learn: the item-space FSLIM kernel's item bitmap does not fit the LDS of a CU"};
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fslim_union_fn()),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.f_union_lds));
+    const size_t lds = p.f_wave_lds * (size_t)p.f_waves;
+    int per_cu = 0;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(p.fn_f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(p.fn_f), 64 * p.f_waves, lds));
+    if (per_cu < 1)
+      throw Refusal{SLIM_ERROR, "SLIMGPU_Learn: the item-space FSLIM kernel does not fit a compute unit of this device"};
+    p.nwaves = std::max(1, std::min((nwork + p.f_waves - 1) / p.f_waves, m->num_cus * per_cu));
+    if (warm_dev && warm_dev->device != m->device)
+      throw Refusal{SLIM_ERROR_INPUT, "SLIMGPU_LearnResident: the warm-start model lives on another device"};
+    p.has_imodel = false;  // (estimate.c:424-431: the FSLIM branch never warm-starts)
+    if (p.trace_level >= 1)
+      std::fprintf(stderr, "[trace] item-space FSLIM: form %s, lists of %d, %d wavefronts per workgroup (%zu KB of LDS "
+                   "each), %d workgroups per CU\n", p.f_block ? "block in LDS" : "gathered", p.f_stride, p.f_waves,
+                   p.f_wave_lds >> 10, per_cu);
+    return;
+  }
   p.use_lds = p.kernel == SLIMGPU_KERNEL_WAVE_LDS;
   if (p.use_gram && p.gram_v == 0)  // g in HBM: 8 or 16 wavefronts per workgroup
     if (const char* e = std::getenv("SLIM_GPU_GRAM_NW")) p.gram_nw = std::atoi(e) == 8 ? 8 : 16;
@@ -1580,13 +1649,37 @@ struct Slabs {
   // dynamic LDS of a tile workgroup: the user bitmap of the screen pass (FSLIM: the select
   // histograms)
   size_t tile_lds = 0;
+  // item-space FSLIM: the neighbour lists of one slice of the work list, f_slice_tiles tiles long
+  int32_t *f_n = nullptr, *f_id = nullptr, *f_slot = nullptr;
+  float* f_aty = nullptr;
+  int f_slice_tiles = 0;
 };
 
 Slabs alloc_slabs(slimgpu_matrix* m, const LearnOptions& opt, const Path& p, const TileGeom& t, int32_t nwork,
                   int nwaves) {
   Slabs s;
   const auto evict = evict_cache(m);
-  if (p.use_gram) {
+  if (p.use_fgram) {
+    // 12 bytes per list entry (id, aTy, union slot).  Lists beyond a quarter of the free memory:
+    // the work list goes through in slices of whole tiles (SLIM_GPU_FSLIM_SLICE_TILES forces a length)
+    const size_t ngroups0 = std::max<size_t>(1, ((size_t)nwork + 31) / 32);
+    const size_t per_tile = (size_t)32 * (size_t)p.f_stride * 12;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t have = free_b + m->ws_fid.bytes() + m->ws_faty.bytes() + m->ws_fslot.bytes();
+    size_t tiles = ngroups0;
+    if (tiles * per_tile > have / 4) tiles = std::max<size_t>(1, have / 4 / per_tile);
+    if (const char* e = std::getenv("SLIM_GPU_FSLIM_SLICE_TILES"); e && std::atoi(e) > 0)
+      tiles = std::min<size_t>(tiles, (size_t)std::atoi(e));
+    s.f_slice_tiles = (int)tiles;
+    const size_t npos = std::min<size_t>((size_t)std::max(nwork, 1), tiles * 32);
+    s.f_n = m->ws_fn.reserve(npos, evict);
+    s.f_id = m->ws_fid.reserve(npos * (size_t)p.f_stride, evict);
+    s.f_aty = m->ws_faty.reserve(npos * (size_t)p.f_stride, evict);
+    s.f_slot = m->ws_fslot.reserve(npos * (size_t)p.f_stride, evict);
+    s.ulist = m->ws_ulist.reserve((size_t)p.f_ustride * tiles, evict);
+    s.nunion = m->ws_nunion.reserve(tiles, evict);
+  } else if (p.use_gram) {
     const size_t ngroups0 = ((size_t)nwork + 31) / 32;
     s.xslab = m->ws_xslab.reserve((size_t)p.ncols_pad * (size_t)nwaves, evict);
     if (p.gram_v == 0) s.slab = m->ws_slab.reserve((size_t)p.ncols_pad * (size_t)nwaves, evict);
@@ -1887,6 +1980,10 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
     S.u_stride = (int64_t)p.ncols_pad;
     S.ngroups = (npend + 31) / 32;
   }
+  if (p.use_fgram) {
+    S.u_stride = (int64_t)p.f_ustride;
+    S.ngroups = (npend + 31) / 32;
+  }
   if (const char* e = std::getenv("SLIM_GPU_HI_PREFETCH")) S.hi_prefetch = std::atoi(e);
   if (p.use_tile)
     HIP_TRY(hipMemsetAsync(L.s.mailbox, 0, sizeof(unsigned long long) * L.s.mailbox_words, stream));
@@ -2171,7 +2268,30 @@ Entries run_launches(slimgpu_matrix* m, const LearnOptions& opt, const std::vect
       S.xcd_swizzle = 1;
       if (const char* e = std::getenv("SLIM_GPU_XCD")) S.xcd_swizzle = std::atoi(e) != 0;
     }
-    if (p.use_gramr)
+    if (p.use_fgram) {
+      // select -> union -> solve over every slice of the work list (whole tiles; one slice unless the
+      // lists would not fit): all inside kernel_ms
+      FslimArgs F{};
+      F.stride = p.f_stride;
+      F.nbr_n = L.s.f_n;
+      F.nbr_id = L.s.f_id;
+      F.nbr_aty = L.s.f_aty;
+      F.nbr_slot = L.s.f_slot;
+      F.wave_lds = (int32_t)p.f_wave_lds;
+      F.tab_n = p.f_tab_n;
+      const int slice = L.s.f_slice_tiles * 32;
+      for (int pos0 = 0; pos0 < npend; pos0 += slice) {
+        F.pos0 = pos0;
+        F.npos = std::min(slice, npend - pos0);
+        if (pos0 > 0) HIP_TRY(hipMemsetAsync(L.misc, 0, sizeof(int32_t), stream));  // (the queue head)
+        hipLaunchKernelGGL(fslim_select_fn(), dim3(F.npos), dim3(kFslimSelectThreads), 0, stream, A, S, F);
+        hipLaunchKernelGGL(fslim_union_fn(), dim3((F.npos + 31) / 32), dim3(kFslimUnionThreads), p.f_union_lds, stream,
+                           A, S, F);
+        hipLaunchKernelGGL(p.fn_f, dim3(std::max(1, std::min((F.npos + p.f_waves - 1) / p.f_waves, L.nwaves))),
+                           dim3(64 * p.f_waves), p.f_wave_lds * (size_t)p.f_waves, stream, A, S, F);
+        HIP_TRY(hipGetLastError());
+      }
+    } else if (p.use_gramr)
       hipLaunchKernelGGL(p.fn_r, dim3(launch_now), dim3(kGramrNT), p.gram_lds, stream, A, S, P);
     else
       hipLaunchKernelGGL(p.fn, dim3(launch_now), dim3(p.use_gram ? 64 * p.gram_nw : (p.use_tile ? 64 * p.tileNW : 64)),
@@ -2296,7 +2416,7 @@ Counters read_counters(const slimgpu_matrix* m, const Launch& L, const std::vect
       k.gram_bytes = (double)k.gram_rows * 4.0 * (double)L.p.ncols_pad;
     }
   }
-  if (L.p.use_tile || L.p.use_gram)  // the Gram work of a column is the staging pass's cost figure
+  if (L.p.use_tile || L.p.use_gram || L.p.use_fgram)  // the Gram work of a column is the staging pass's cost figure
     for (int32_t c : requested) cs.G[(size_t)c] = m->h_cost[(size_t)c];
   HIP_TRY(hipMemcpy(cs.D.data(), L.stl + ncols, sizeof(int64_t) * ncols, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(cs.U.data(), L.stl + 2 * ncols, sizeof(int64_t) * ncols, hipMemcpyDeviceToHost));
@@ -2477,7 +2597,7 @@ slimgpu_stats_t solve_stats(slimgpu_matrix* m, const Launch& L, const Entries& E
   st.nnzW = tnnz;
   st.alg_bytes = m->binary ? 4.0 * st.G + 8.0 * st.D + 4.0 * st.U + 8.0 * st.nnzW
                            : 8.0 * st.G + 12.0 * st.D + 4.0 * st.U + 8.0 * st.nnzW;
-  if (p.use_gram) {
+  if (p.use_gram || p.use_fgram) {
     st.gram_build_ms = m->G_build_ms;
     st.gram_alloc_ms = m->G_alloc_ms;
     st.gram_sums_ms = m->G_sums_ms;
@@ -2524,8 +2644,8 @@ slim_csr_t* learn_cd(slimgpu_matrix_t* m, const LearnOptions& opt, const slim_cs
     L.G_block = w.G_block;
     L.p = choose_kernel(m, opt, nwork);
     L.p.trace_level = trace_env ? std::atoi(trace_env) : 0;
-    if (L.p.use_gram && !m->G_ready) {
-      if (const int32_t st = gram_for_solve(m, opt, L.p.trace_level); st != SLIM_OK) return fail(st);
+    if ((L.p.use_gram || L.p.use_fgram) && !m->G_ready) {
+      if (const int32_t st = gram_for_solve(m, opt, L.p.trace_level, L.p.use_fgram); st != SLIM_OK) return fail(st);
     }
     finish_path(m, opt, nwork, imodel, warm_dev, L.p);
     prepare_launch(m, opt, requested, imodel, warm_dev, resident, columns == nullptr, L);

@@ -9,13 +9,14 @@ int main(int argc, char** argv) {
       {"ifmt", true},    {"binarize", false}, {"l1r", true},     {"l2r", true},
       {"optTol", true},  {"niters", true},    {"nnbrs", true},   {"simtype", true},
       {"algo", true},    {"ordered", false},  {"nthreads", true}, {"ipmdlfile", true},
-      {"dbglvl", true},  {"ngpus", true},   {"help", false}};
+      {"dbglvl", true},  {"ngpus", true},   {"gpukernel", true}, {"help", false}};
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.empty() || a.pos.size() > 2) {
     std::printf("\n Usage: slim_learn [options] train-file [model-file]\n"
                 "   -ifmt=csr|csrnv|cluto|ijv  -binarize  -l1r=f  -l2r=f  -optTol=f  -niters=i\n"
                 "   -nnbrs=i  -simtype=cos|jac|dotp  -algo=cd  -nthreads=i  -ipmdlfile=file  -dbglvl=i\n"
-                "   -ngpus=i   (engine extension: shard the item columns over i GPUs of this node)\n\n");
+                "   -ngpus=i   (engine extension: shard the item columns over i GPUs of this node)\n"
+                "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n\n");
     return 0;
   }
   const Fmt fmt = parse_fmt(a.str("ifmt", "csr"));
@@ -57,6 +58,7 @@ int main(int argc, char** argv) {
   io[SLIM_OPTION_NTHREADS] = a.integer("nthreads", 1);
   io[SLIM_OPTION_MAXNITERS] = niters;
   if (a.has("ngpus")) io[SLIM_OPTION_GPU_NGPUS] = a.integer("ngpus", 1);
+  if (a.has("gpukernel")) io[SLIM_OPTION_GPU_KERNEL] = a.integer("gpukernel", SLIMGPU_KERNEL_AUTO);
   dopt[SLIM_OPTION_L1R] = l1r;
   dopt[SLIM_OPTION_L2R] = l2r;
   dopt[SLIM_OPTION_OPTTOL] = optTol;

@@ -14,6 +14,7 @@ from . import _lib
 from .constants import SLIM_NOPTIONS, SLIM_OK, Opt
 
 KERNEL_AUTO, KERNEL_WAVE_LDS, KERNEL_WAVE_HBM, KERNEL_TILE, KERNEL_TILE16, KERNEL_GRAM = 0, 1, 2, 3, 4, 5
+KERNEL_GRAM_FSLIM = 6   # FSLIM in item space (nnbrs > 0, ratings > 0); never chosen by KERNEL_AUTO
 
 
 def make_options(l1r=1.0, l2r=1.0, optTol=1e-7, niters=10000, seed=1, col_begin=None,
