@@ -308,5 +308,7 @@ const char *SLIMGPU_LastError(void);
 #include "slim_gpu_eval.h"
 /* A look at the byte planes of G = R^T R (SLIMGPU_MatrixGramPlanes). */
 #include "slim_gpu_planes.h"
+/* The rank of every held-out item: evaluation of resident models at any list length. */
+#include "slim_gpu_rank.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

@@ -62,9 +62,10 @@ slimgpu_evalset_t *SLIMGPU_EvalSetCreateAt(slimgpu_matrix_t *mat, slim_t *tsthan
 int32_t SLIMGPU_ModelEvaluateAt(slimgpu_evalset_t *es, const slimgpu_model_t *model,
                                 int32_t ncutoffs, double *metrics, int32_t *nvalid);
 /* Option slot of Py_SLIM_Mselect (and slim_mselect -evalstride=K): with K > 1 the grid evaluates users
- * 0, K, 2K, ... only; -1 or 1: every user.  Needs the evaluation in HBM: with ADMM, several GPUs, nrcmds above 128,
+ * 0, K, 2K, ... only; -1 or 1: every user.  Needs the evaluation in HBM: with ADMM, several GPUs,
  * SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0 or a matrix whose duplicates were merged the call fails
- * with SLIM_ERROR_INPUT before the first solve. */
+ * with SLIM_ERROR_INPUT before the first solve.  (nrcmds above 128 is served from the ranks of the held-out
+ * items, slim_gpu_rank.h.) */
 enum { SLIM_OPTION_GPU_EVALSTRIDE = 22 };
 /* Top-N of every row of the resident matrix through a resident model: only the lists come down.
  * Bit-identical to SLIMGPU_ModelPredict on the host handle of the same rows. */
@@ -72,7 +73,7 @@ int32_t SLIMGPU_MatrixPredict(int32_t nrcmds, const slimgpu_model_t *model,
                               slimgpu_matrix_t *mat, int32_t *output, float *scores);
 /* Counters of the most recent SLIMGPU_ModelEvaluate / SLIMGPU_MatrixPredict on this thread. */
 typedef struct slimgpu_eval_stats_t {
-  int32_t path;          /* 1 fused chunk kernel, 2 wave kernel + k_user_terms */
+  int32_t path;          /* 1 fused chunk kernel, 2 wave kernel + k_user_terms, 3 ranks (slim_gpu_rank.h) */
   int32_t device_allocs; /* device allocations made by this call               */
   int64_t h2d_bytes, d2h_bytes;
   double kernel_ms, total_ms;

@@ -21,6 +21,12 @@ evaluated at these list lengths in ONE pass (SLIMGPU_ModelEvaluateAt), against o
 rows of the one pass must equal the single passes.  With SLIM_AMD_LIB pointing at a build from before these
 entry points (an A / B run against it) the grid part still runs; --stride and --cutoffs need the new build.
 
+--ranked: instead of the grid, ONE model (the file's first pair) evaluated in the same process, alternating, --runs
+times each: (A) SLIMGPU_ModelEvaluate at --nrcmds from the build at --parent-lib (the parent commit's libslim.so, with
+a matrix handle, a model and an eval set of its own over the same device arrays; skipped without it), (B) the same
+call from this build, (C) SLIMGPU_ModelEvaluateRanked at the cutoff --nrcmds, (D) the same at --ranked-cutoffs.
+C and D report the pre-pass (k_test_keys) from its own events; B and C must give the same figures.
+
 --pairs 0 (default): the short grid -- the cold pair, three l2 steps and one l1 change; N > 0: the first
 N pairs of the file; -1: all of them (each warm-started from the one before it in the list).  The run stops adding pairs when --budget-s is used up and says so.
 """
@@ -65,6 +71,128 @@ def make_evaluator(mat, T, fm, nrcmds=10, cutoffs=None, users=None):
     return Evaluator(lib, h, mat, (int(nrcmds),))
 
 
+class ParentBuild(object):
+    """The few entry points run A needs, from another build of the library (its handles are its own)."""
+
+    def __init__(self, path, shape, T, fm, l1, l2, seed):
+        import numpy as np
+        from slim_amd import _lib as _l
+        from slim_amd.engine import _wrap_rows, make_options
+        self.lib = lib = C.CDLL(path)
+        for table in (_l._SIGNATURES, _l._EVAL_SIGNATURES):
+            for name, (res, argt) in table.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = res, argt
+        nrows, ncols, ptr, ind = shape
+        iopt, dopt = make_options(device=0)
+        st = C.c_int32(0)
+        self.mat = C.c_void_p(lib.SLIMGPU_MatrixFromDevice(nrows, ncols, C.c_void_p(ptr.data_ptr()),
+                                                           C.c_void_p(ind.data_ptr()), None,
+                                                           iopt.ctypes.data_as(C.c_void_p), C.byref(st)))
+        assert self.mat, lib.SLIMGPU_LastError()
+        iopt, dopt = make_options(l1r=l1, l2r=l2, optTol=1e-7, niters=10000, seed=seed)
+        self.model = C.c_void_p(lib.SLIMGPU_LearnResident(self.mat, iopt.ctypes.data_as(C.c_void_p),
+                                                          dopt.ctypes.data_as(C.c_void_p), None, C.byref(st)))
+        assert self.model, lib.SLIMGPU_LastError()
+        self.nnz = int(lib.SLIMGPU_ModelNnz(self.model))
+        ht = _wrap_rows(lib, T)
+        fm = np.ascontiguousarray(fm, dtype=np.int32)
+        self.es = C.c_void_p(lib.SLIMGPU_EvalSetCreate(self.mat, ht, fm, fm.size, 10, C.byref(st)))
+        lib.Py_csr_free(ht)
+        assert self.es, lib.SLIMGPU_LastError()
+
+    def evaluate(self):
+        import numpy as np
+        from slim_amd import _lib as _l
+        from slim_amd.constants import SLIM_OK
+        met, nv = np.zeros(4), np.zeros(3, np.int32)
+        t0 = time.time()
+        rc = self.lib.SLIMGPU_ModelEvaluate(self.es, self.model, met, nv)
+        s = time.time() - t0
+        assert rc == SLIM_OK, (rc, self.lib.SLIMGPU_LastError())
+        st = _l.EvalStats()
+        self.lib.SLIMGPU_LastEvalStats(C.byref(st))
+        return s, (met.tolist(), nv.tolist()), st.as_dict()
+
+    def close(self):
+        self.lib.SLIMGPU_EvalSetFree(C.byref(self.es))
+        self.lib.SLIMGPU_ModelFree(C.byref(self.model))
+        self.lib.SLIMGPU_MatrixFree(C.byref(self.mat))
+
+
+def ranked_comparison(args, mat, T, fm, shape, say):
+    assert args.nrcmds == 10 or not args.parent_lib, "run A is made for nrcmds 10"
+    l1, l2 = [tuple(map(float, l.split())) for l in open(os.path.join(ROOT, "tests", "golden", "l12file")) if l.strip()][0]
+    model, _ = mat.learn_resident(l1r=l1, l2r=l2, optTol=1e-7, niters=10000, seed=args.seed)
+    say("# one model, l1 %g l2 %g: nnz %d" % (l1, l2, model.nnz))
+    ev = mat.evaluator(T, nrcmds=args.nrcmds, fmarker=fm)
+    evr = mat.evaluator(T, fmarker=fm, ranked=True)
+    parent = None
+    if args.parent_lib:
+        parent = ParentBuild(args.parent_lib, shape, T, fm, l1, l2, args.seed)
+        say("# parent build %s: its own handle and eval set over the same device arrays; its model is LEARNED SEPARATELY by "
+            "that build with the same options (nnz %d, this build's %d): A evaluates that model, B / C / D this build's"
+            % (args.parent_lib, parent.nnz, model.nnz))
+    many = [int(v) for v in args.ranked_cutoffs.split(",") if v]
+    KEYS = ("hr", "hr_head", "hr_tail", "arhr")
+    NK = ("nvalid", "nvalid_head", "nvalid_tail")
+    fig = lambda d: ([d[k] for k in KEYS], [d[k] for k in NK])
+
+    def run_b():
+        t0 = time.time()
+        g = ev.evaluate(model)
+        return time.time() - t0, fig(g), ev.stats(), 0.0
+
+    def run_c():
+        t0 = time.time()
+        g = evr.evaluate_ranked(model, [args.nrcmds])
+        return time.time() - t0, fig(g[0]), evr.stats(), evr.prepass_ms()
+
+    def run_d():
+        t0 = time.time()
+        g = evr.evaluate_ranked(model, many)
+        return time.time() - t0, [(r["nrcmds"], r["hr"], r["arhr"]) for r in g], evr.stats(), evr.prepass_ms()
+
+    def run_a():
+        s, f, st = parent.evaluate()
+        return s, f, st, 0.0
+
+    variants = ([("A", run_a)] if parent else []) + [("B", run_b), ("C", run_c), ("D", run_d)]
+    for name, fn in variants:            # a warm-up of each: workspaces made, code objects loaded
+        fn()
+    say("# %-3s %-3s %9s %10s %11s %5s %6s %6s %9s | figures" % ("run", "var", "eval_s", "kernel_ms", "prepass_ms", "path",
+                                                               "allocs", "d2h", "w_GB"))
+    res = {n: [] for n, _ in variants}
+    figs = {}
+    for r in range(args.runs):
+        for name, fn in variants:
+            s, f, st, pre = fn()
+            res[name].append((st["kernel_ms"], pre))
+            figs[name] = f
+            say("  %-3d %-3s %9.3f %10.1f %11.1f %5d %6d %6d %9.1f | %s"
+                % (r, name, s, st["kernel_ms"], pre, st["path"], st["device_allocs"], st["d2h_bytes"],
+                   st["w_bytes"] / 1e9, f))
+    assert figs["B"] == figs["C"], "B and C disagree: %r vs %r" % (figs["B"], figs["C"])
+    say("# B and C gave equal figures%s" % ("; A (the parent's own model) too" if parent and figs["A"] == figs["B"] else ""))
+    for name, _ in variants:
+        k = [x[0] for x in res[name]]
+        p = [x[1] for x in res[name]]
+        say("# %s: kernel_ms %.1f .. %.1f%s" % (name, min(k), max(k),
+                                               "" if name in "AB" else ", pre-pass %.1f .. %.1f ms" % (min(p), max(p))))
+    kb = [x[0] for x in res["B"]]
+    kc, pc = [x[0] for x in res["C"]], [x[1] for x in res["C"]]
+    say("# C against B: slowest C %.1f ms; B's slowest run plus the pre-pass = %.1f ms: %s"
+        % (max(kc), max(kb) + max(pc), "inside" if max(kc) <= max(kb) + max(pc) else "EXCEEDS"))
+    if parent:
+        ka = [x[0] for x in res["A"]]
+        say("# B against A: A's band %.1f .. %.1f ms, B %.1f .. %.1f ms: %s"
+            % (min(ka), max(ka), min(kb), max(kb), "inside" if min(ka) <= min(kb) and max(kb) <= max(ka) else "outside"))
+        parent.close()
+    ev.close()
+    evr.close()
+    model.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c5")
@@ -76,6 +204,10 @@ def main():
     ap.add_argument("--no-a", action="store_true", help="skip path A (no host copy of the training rows)")
     ap.add_argument("--stride", default="", help="comma-separated strides K: the last model on every K-th user")
     ap.add_argument("--cutoffs", default="", help="comma-separated list lengths: one pass against one pass each")
+    ap.add_argument("--ranked", action="store_true", help="the four-way comparison of the ranked evaluation")
+    ap.add_argument("--parent-lib", default="", help="--ranked: libslim.so of the parent commit (run A)")
+    ap.add_argument("--runs", type=int, default=4, help="--ranked: runs of each variant")
+    ap.add_argument("--ranked-cutoffs", default="5,10,20,50,100,200,500", help="--ranked: the cutoffs of run D")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_eval_c5.txt"))
     args = ap.parse_args()
     import numpy as np
@@ -125,6 +257,14 @@ def main():
     mat = DeviceMatrix.from_device_ptrs(nrows, ncols, trn_ptr.data_ptr(), trn_ind.data_ptr(), 0,
                                         keepalive=(trn_ptr, trn_ind), device=0)
     lib = mat._lib
+    if args.ranked:
+        ranked_comparison(args, mat, T, fm, (nrows, ncols, trn_ptr, trn_ind), say)
+        say("# whole run: %.1f s" % (time.time() - t_start))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        mat.close()
+        return
     t0 = time.time()
     ev = make_evaluator(mat, T, fm, nrcmds=args.nrcmds)
     say("# eval set staged once: %.2f s" % (time.time() - t0))

@@ -1,8 +1,24 @@
 #!/bin/bash
 # Register / spill figures of every tile-kernel instantiation and the per-loop spill remarks of the
 # dominant one (cross-compiled here, no GPU needed):  bash scripts/isa_metadata.sh > profiles/rNN/isa_metadata.txt
+#
+# bash scripts/isa_metadata.sh topn [path/to/topn.hip]: the same figures of every instantiation of the top-N
+# scorers (topn_chunk_kernel / topn_chunk_eval_kernel / topn_chunk_rank_kernel <NW, KeyT>; y = 32-bit keys,
+# j = 64-bit keys) -- of this tree's topn.hip, or of another revision's copied into slim_amd/csrc under
+# another name (it needs the tree's headers)
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
+if [ "$1" = "topn" ]; then
+  SRC=${2:-$R/slim_amd/csrc/topn.hip}
+  echo "# topn_chunk_*kernel<NW, KeyT> : VGPRs, SGPRs, VGPR spills, SGPR spills, scratch bytes per lane, LDS bytes"
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics --cuda-device-only -I$R/slim_amd/csrc \
+    -Rpass-analysis=kernel-resource-usage -c -o $T/x.o -x hip $SRC 2>&1 |
+  grep -E "Function Name|VGPRs:|TotalSGPRs|VGPRs Spill|SGPRs Spill|ScratchSize|LDS Size" | sed 's/.*remark: *//;s/ \[-Rpass.*//' |
+  awk '/Function Name/{if (n) print n, v; n=$3; v=""; next} {v=v" | "$0} END{print n, v}' | grep "topn_" |
+  sed 's/_ZN7slimamd[0-9]*_GLOBAL__N_1[0-9]*//;s/_ZN7slimamd[0-9]*//;s/ILi\([0-9]*\)E\([yj]\)EEvNS[0-9_]*[A-Za-z0-9]*E/<\1,\2>/' | sort
+  rm -rf $T
+  exit 0
+fi
 echo "# hipcc -O3 --offload-arch=gfx950 -munsafe-fp-atomics -Rpass-analysis=kernel-resource-usage, $(/opt/rocm/bin/hipcc --version | grep -m1 -i 'hip version')"
 echo "# cd_tile_kernel<P, HAS_VAL, PROFILE, NW, FSLIM, FOLD>, cd_gram_kernel<NW, V>, cd_gramr_kernel<KR, KL, DMA> : VGPRs, SGPRs, VGPR spills, SGPR spills (to VGPR lanes), scratch bytes per lane, LDS bytes"
 for f in tile_p32_nw16 tile_p32_nw8 tile_p32_cold tile_p32_rowfold tile_p32_fslim tile_p16_nw16 tile_p16_nw8 gram_inst gramr_inst gramr_k13; do

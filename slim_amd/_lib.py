@@ -164,6 +164,20 @@ _PLANES_SIGNATURES = {
 PLANES_SYMBOLS = tuple(_PLANES_SIGNATURES)
 MAX_CUTOFFS = 8     # SLIMGPU_MAX_CUTOFFS
 
+# the rank of every held-out item: evaluation at any list length (include/slim_gpu_rank.h)
+_RANK_SIGNATURES = {
+    "SLIMGPU_EvalSetCreateRanked": (C.c_void_p, [C.c_void_p, C.c_void_p, i32_1d, C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.POINTER(C.c_int32)]),
+    "SLIMGPU_EvalSetEntries": (C.c_int64, [C.c_void_p]),
+    "SLIMGPU_ModelRanks": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_ModelEvaluateRanked": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, f64_1d, i32_1d]),
+    "SLIMGPU_ModelFromHost": (C.c_void_p, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "SLIMGPU_LastRankPrepassMs": (C.c_double, []),
+}
+
+RANK_SYMBOLS = tuple(_RANK_SIGNATURES)
+MAX_RANK_CUTOFFS = 32   # SLIMGPU_MAX_RANK_CUTOFFS
+
 _lib = None
 
 
@@ -178,7 +192,8 @@ def load():
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for SLIM training." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
-                              list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items())):
+                              list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
+                              list(_RANK_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

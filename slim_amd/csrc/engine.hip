@@ -2717,6 +2717,70 @@ slimgpu_model* learn_resident(slimgpu_matrix_t* m, const LearnOptions& opt, cons
   return out;
 }
 
+// A host model made resident (saved models, hand-made test models): its rows go up as they are, the
+// column view is formed on the device like a learned model's row view (transpose_on_device: entries of a
+// column in ascending row order, the layout SaveModel gives), k_row_facts finds the longest row and
+// refuses rows whose ids do not ascend strictly.  W is square with n = max(nrows, ncols); rows the host
+// model lacks are empty.  No carried g: as a warm start it is folded like any model without one.
+slimgpu_model* model_from_host(slimgpu_matrix_t* m, const slim_csr_t* W, int32_t* status) {
+  auto fail = [&](int32_t st, const std::string& why) {
+    set_error("SLIMGPU_ModelFromHost: " + why);
+    if (status) *status = st;
+    return static_cast<slimgpu_model*>(nullptr);
+  };
+  if (!m || !W || !W->rowptr || W->nrows < 0 || W->ncols < 0)
+    return fail(SLIM_ERROR_INPUT, "bad arguments (a staged matrix, a model handle with a row view)");
+  if (!m->replicas.empty()) return fail(SLIM_ERROR_INPUT, "a model resident in HBM belongs to one device (ngpus = 1)");
+  const int32_t n = std::max(W->nrows, W->ncols);
+  const int64_t nnz = W->rowptr[W->nrows];
+  if (W->rowptr[0] != 0) return fail(SLIM_ERROR_INPUT, "the row pointer does not start at 0");
+  for (int32_t r = 0; r < W->nrows; ++r)
+    if (W->rowptr[r + 1] < W->rowptr[r]) return fail(SLIM_ERROR_INPUT, "the row pointer descends");
+  if (nnz > 0 && (!W->rowind || !W->rowval)) return fail(SLIM_ERROR_INPUT, "the model has no values");
+  for (int64_t j = 0; j < nnz; ++j)
+    if (W->rowind[j] < 0 || W->rowind[j] >= n) return fail(SLIM_ERROR_INPUT, "an item id outside the model");
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t stream = m->stream;
+    std::unique_ptr<slimgpu_model> dm(new slimgpu_model());
+    dm->device = m->device;
+    dm->n = n;
+    dm->nnz = nnz;
+    std::vector<int64_t> h_ptr((size_t)n + 1, nnz);
+    for (int32_t r = 0; r <= W->nrows; ++r) h_ptr[(size_t)r] = W->rowptr[r];
+    dm->d_rowptr = DeviceBuffer<int64_t>((size_t)n + 1);
+    dm->d_rowind = DeviceBuffer<int32_t>((size_t)std::max<int64_t>(nnz, 1));
+    dm->d_rowval = DeviceBuffer<float>((size_t)std::max<int64_t>(nnz, 1));
+    HIP_TRY(hipMemcpyAsync(dm->d_rowptr.get(), h_ptr.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice,
+                           stream));
+    if (nnz > 0) {
+      HIP_TRY(hipMemcpyAsync(dm->d_rowind.get(), W->rowind, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(dm->d_rowval.get(), W->rowval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, stream));
+    }
+    int32_t* d_facts = m->ws_misc.reserve(16);
+    int32_t facts[2] = {0, 0};
+    HIP_TRY(hipMemsetAsync(d_facts, 0, sizeof(facts), stream));
+    queue_row_facts(stream, m->num_cus, n, dm->d_rowptr.get(), dm->d_rowind.get(), d_facts);
+    HIP_TRY(hipMemcpyAsync(facts, d_facts, sizeof(facts), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (facts[1] != 0) return fail(SLIM_ERROR_INPUT, "the item ids of a model row do not ascend strictly");
+    dm->max_row = facts[0];
+    dm->rows_sorted = true;
+    transpose_on_device(m, n, nnz, dm->d_rowptr.get(), dm->d_rowind.get(), dm->d_rowval.get(), dm->d_colptr,
+                        dm->d_colind, dm->d_colval);
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (status) *status = SLIM_OK;
+    return dm.release();
+  } catch (const HipFail& e) {
+    report(e, "SLIMGPU_ModelFromHost");
+    if (status) *status = status_of(e);
+    return nullptr;
+  } catch (const std::bad_alloc&) {
+    return fail(SLIM_ERROR_MEMORY, "out of host memory");
+  }
+}
+
 int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out) {
   if (!w || !w->d_rowptr.get() || !out) {
     set_error("resident model: no row view");

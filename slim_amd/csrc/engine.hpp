@@ -89,6 +89,8 @@ slim_csr_t* learn_cd(slimgpu_matrix_t* m, const LearnOptions& opt, const slim_cs
 // the arrays SaveModel would have formed) can run on the DMA engines beside the next solve.
 slimgpu_model* learn_resident(slimgpu_matrix_t* m, const LearnOptions& opt, const slimgpu_model* warm,
                               int32_t* status);
+// a host model made resident on m's device (slim_gpu_rank.h: SLIMGPU_ModelFromHost)
+slimgpu_model* model_from_host(slimgpu_matrix_t* m, const slim_csr_t* W, int32_t* status);
 int64_t model_nnz(const slimgpu_model* w);
 int32_t model_ncols(const slimgpu_model* w);
 int32_t model_fetch_begin(slimgpu_model* w);                      // starts the D2H on a host thread + copy stream
@@ -152,6 +154,15 @@ int32_t matrix_csr_view(const slimgpu_matrix_t* m, DeviceCsrView* out);
 slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
                                   int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
                                   const int32_t* users, int32_t* status);
+// slim_gpu_rank.h: an eval set with no list length; the rank (and score) of every test entry of its users
+// among the user's candidates; HR / ARHR at any cutoffs (out[0 .. ncutoffs)) from those ranks
+slimgpu_evalset_t* evalset_create_ranked(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                         int32_t fm_ncols, int32_t nusers, const int32_t* users, int32_t* status);
+int64_t evalset_entries(const slimgpu_evalset_t* es);
+int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores);
+int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs,
+                              const int32_t* cutoffs, EvalResult* out);
+double last_rank_prepass_ms();
 void evalset_free(slimgpu_evalset_t* es);
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es);
 int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out);

@@ -73,6 +73,60 @@ __global__ void k_user_terms(int32_t nsel, const int32_t* __restrict__ users, in
   }
 }
 
+// The same records from the ranks of the test entries (slim_gpu_rank.h) instead of lists: a test item is in
+// the list of length c exactly when 0 < rank <= c, and it stands at position rank - 1 there.  One lane per
+// position.  The hits are the DISTINCT non-zero ranks (distinct candidates have distinct ranks, so one id
+// listed twice in the test row gives one rank twice and, like one list slot, one hit), walked ascending: the
+// additions of k_user_terms in the same order.  Everything about the test row is formed as there.
+__global__ void k_rank_terms(int32_t nsel, const int32_t* __restrict__ users, const Cutoffs cut,
+                             const int32_t* __restrict__ ranks, const int64_t* __restrict__ tbase,
+                             const int64_t* __restrict__ tptr, const int32_t* __restrict__ tind,
+                             const int32_t* __restrict__ fmarker, int32_t fm_ncols, UserTerms* __restrict__ out) {
+  for (int32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nsel; q += gridDim.x * blockDim.x) {
+    const int32_t u = users ? users[q] : q;
+    const int64_t t0 = tptr[u], t1 = tptr[u + 1];
+    const int32_t* rk = ranks + tbase[q];
+    int ntrue0 = 0, ntrue1 = 0, flags = 0;
+    float ideal = 0.0f;
+    if (t1 - t0 >= 1) {
+      flags = 1;
+      for (int64_t z = t0; z < t1; ++z) {
+        const int32_t it = tind[z];
+        const int cls = (it >= 0 && it < fm_ncols) ? fmarker[it] : 1;
+        if (cls) ++ntrue1; else ++ntrue0;
+        flags |= cls ? 4 : 2;
+        ideal = (float)((double)ideal + 1.0 / (1.0 + double(z - t0)));
+      }
+    }
+    HitWalk w;
+    // the smallest rank above `prev`, and its item
+    int32_t prev = 0, nxt = 0, nxt_id = 0;
+    auto advance = [&] {
+      nxt = 0;
+      for (int64_t z = t0; z < t1; ++z) {
+        const int32_t r = rk[z - t0];
+        if (r > prev && (nxt == 0 || r < nxt)) {
+          nxt = r;
+          nxt_id = tind[z];
+        }
+      }
+    };
+    advance();
+#pragma unroll
+    for (int k = 0; k < SLIMGPU_MAX_CUTOFFS; ++k) {  // (constant indices into the kernel argument)
+      if (k < cut.n) {
+        const int32_t c = cut.c[k];
+        while (nxt != 0 && nxt <= c) {
+          w.hit(nxt - 1, (nxt_id >= 0 && nxt_id < fm_ncols) ? fmarker[nxt_id] : 1);
+          prev = nxt;
+          advance();
+        }
+        out[(int64_t)k * nsel + q] = w.terms(ntrue0, ntrue1, t1 - t0, ideal, flags);
+      }
+    }
+  }
+}
+
 // one wavefront per cutoff: 64 positions' terms per coalesced load, added by lane order = position order
 __global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nsel, const UserTerms* __restrict__ terms,
                                                           EvalSums* __restrict__ out) {
@@ -219,6 +273,15 @@ void launch_user_terms(hipStream_t stream, int num_cus, int32_t nsel, const int3
   const int blocks = std::max(1, std::min((nsel + 255) / 256, num_cus * 8));
   hipLaunchKernelGGL(k_user_terms, dim3(blocks), dim3(256), 0, stream, nsel, users, nrcmds, cut, lists, counts,
                      tptr, tind, fmarker, fm_ncols, terms);
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_rank_terms(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* users, const Cutoffs& cut,
+                       const int32_t* ranks, const int64_t* tbase, const int64_t* tptr, const int32_t* tind,
+                       const int32_t* fmarker, int32_t fm_ncols, UserTerms* terms) {
+  const int blocks = std::max(1, std::min((nsel + 255) / 256, num_cus * 8));
+  hipLaunchKernelGGL(k_rank_terms, dim3(blocks), dim3(256), 0, stream, nsel, users, cut, ranks, tbase, tptr, tind,
+                     fmarker, fm_ncols, terms);
   HIP_TRY(hipGetLastError());
 }
 

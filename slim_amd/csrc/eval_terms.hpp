@@ -87,6 +87,12 @@ struct HitWalk {
 void launch_user_terms(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* users, int32_t nrcmds,
                        const Cutoffs& cut, const int32_t* lists, const int32_t* counts, const int64_t* tptr,
                        const int32_t* tind, const int32_t* fmarker, int32_t fm_ncols, UserTerms* terms);
+// terms[k*nsel + q] from the RANKS of the test entries of the user at position q (slim_gpu_rank.h; ranks[tbase[q]
+// + z] belongs to entry z of the user's test row): the distinct non-zero ranks <= cut.c[k], walked ascending.
+// Any cutoff >= 1 (cut.c is read as it is, not through the packed word).
+void launch_rank_terms(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* users, const Cutoffs& cut,
+                       const int32_t* ranks, const int64_t* tbase, const int64_t* tptr, const int32_t* tind,
+                       const int32_t* fmarker, int32_t fm_ncols, UserTerms* terms);
 // out[k] = the accumulators of cutoff k, positions added in position order (one wavefront per cutoff)
 void launch_sum_in_user_order(hipStream_t stream, int32_t nsel, int32_t ncut, const UserTerms* terms,
                               EvalSums* out);

@@ -18,6 +18,7 @@ int main(int argc, char** argv) {
                 "   -nrcmds=i  -nthreads=i  -dbglvl=i  -nomodels (do not write '<l1 l2>.model' files)\n"
                 "   -ngpus=i   (engine extension: R replicated on i GPUs, every model sharded over them)\n"
                 "   -evalstride=i  (engine extension: evaluate users 0, i, 2i, ... only; needs the evaluation in HBM)\n"
+                "   (-nrcmds above 128 is evaluated in HBM from the ranks of the held-out items: no lists are formed)\n"
                 "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n\n");
     return 0;
   }
@@ -81,18 +82,26 @@ int main(int argc, char** argv) {
   std::vector<int32_t> sel;  // -evalstride: the evaluated users
   if (stride > 1)
     for (int64_t u = 0; u < nall; u += stride) sel.push_back((int32_t)u);
-  if (resident && nrcmds >= 1 && nrcmds <= 128 && !(evr_env && std::atoi(evr_env) == 0)) {
+  // lists of more than 128 have no device scorer; the figures then come from the ranks of the held-out items
+  const int32_t cutoff = nrcmds;
+  bool ranked = false;
+  if (resident && nrcmds >= 1 && !(evr_env && std::atoi(evr_env) == 0)) {
     slim_t* th = to_handle(tst);
-    const int32_t cutoff = nrcmds;
-    evalset = SLIMGPU_EvalSetCreateAt(R, th, fmarker, ncols, 1, &cutoff, (int32_t)sel.size(),
-                                      sel.empty() ? nullptr : sel.data(), &status);
+    if (nrcmds <= 128) {
+      evalset = SLIMGPU_EvalSetCreateAt(R, th, fmarker, ncols, 1, &cutoff, (int32_t)sel.size(),
+                                        sel.empty() ? nullptr : sel.data(), &status);
+    } else {
+      evalset = SLIMGPU_EvalSetCreateRanked(R, th, fmarker, ncols, (int32_t)sel.size(),
+                                            sel.empty() ? nullptr : sel.data(), &status);
+      ranked = evalset != nullptr;
+    }
     Py_csr_free(th);
   }
   // the host loop has no subset form: a stride without the evaluation in HBM fails before the first solve
   if (stride > 1 && !evalset)
-    die(std::string("-evalstride needs the evaluation in HBM (one GPU, 1 <= nrcmds <= 128, SLIM_GPU_RESIDENT and "
+    die(std::string("-evalstride needs the evaluation in HBM (one GPU, nrcmds >= 1, SLIM_GPU_RESIDENT and "
                     "SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ") +
-        (nrcmds < 1 || nrcmds > 128 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
+        (nrcmds < 1 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
   if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
   std::printf("\nEstimating & evaluating models...\n\n");
   double best_hr = 0, best_ar = 0, bh_l1 = 0, bh_l2 = 0, ba_l1 = 0, ba_l2 = 0;
@@ -135,7 +144,8 @@ int main(int argc, char** argv) {
     Eval e;
     double em[4];
     int32_t env[3];
-    const bool evaluated = evalset && SLIMGPU_ModelEvaluate(evalset, dmodel, em, env) == SLIM_OK;
+    const bool evaluated = evalset && (ranked ? SLIMGPU_ModelEvaluateRanked(evalset, dmodel, 1, &cutoff, em, env)
+                                              : SLIMGPU_ModelEvaluate(evalset, dmodel, em, env)) == SLIM_OK;
     if (!evaluated && stride > 1) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
     if (evaluated) {
       e.hr = em[0]; e.hr_head = em[1]; e.hr_tail = em[2]; e.arhr = em[3];

@@ -217,9 +217,14 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   // One GPU, CD: the models of the grid stay in HBM (engine.hpp: learn_resident) -- each pair is
   // warm-started from the previous one without an upload and scored where it lies; only its nnz is
   // printed, so nothing of it ever crosses PCIe.  SLIM_GPU_RESIDENT=0: host models as before.
+  // Lists of more than 128 have no device scorer, but the evaluation does not need the lists: the ranks of the
+  // held-out items (slim_gpu_rank.h) give the figures at any length.  Such a grid runs resident when the
+  // ranked eval set can be made, and as before (host models, the host scorer) when it cannot.
   const char* res_env = std::getenv("SLIM_GPU_RESIDENT");
-  const bool resident = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 && nrcmds <= 128 &&
-                        !(res_env && std::atoi(res_env) == 0);
+  const bool may_reside = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 &&
+                          !(res_env && std::atoi(res_env) == 0);
+  bool resident = may_reside && nrcmds <= 128;
+  bool ranked = false;
   // ... and evaluated where they lie: the test rows and the marker go to HBM once (evalset_create), a
   // pair brings down its four sums and three counts.  SLIM_GPU_EVAL_RESIDENT=0, or a refusal (a matrix
   // whose repeated pairs were merged), keeps the lists-through-the-host path below -- which has no
@@ -234,13 +239,18 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
     evalset = evalset_create(mat, tst, fmarker, ncols, 1, &nrcmds, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
                              &status);
     if (!evalset && stride == 1) set_error("");
+  } else if (may_reside && nrcmds > 128 && !(evr_env && std::atoi(evr_env) == 0)) {
+    evalset = evalset_create_ranked(mat, tst, fmarker, ncols, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
+                                    &status);
+    ranked = resident = evalset != nullptr;
+    if (!evalset && stride == 1) set_error("");
   }
   if (stride > 1 && !evalset) {
     const std::string why = SLIMGPU_LastError();
     set_error("Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALSTRIDE needs the evaluation in HBM (cd on one GPU, "
-              "1 <= nrcmds <= 128, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without "
-              "merged pairs)" +
-              (nrcmds < 1 || nrcmds > 128 ? ": nrcmds is " + std::to_string(nrcmds) : std::string()) +
+              "nrcmds >= 1, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without "
+              "merged pairs; above 128 a model the chunk scorer serves)" +
+              (nrcmds < 1 ? ": nrcmds is " + std::to_string(nrcmds) : std::string()) +
               (why.empty() ? std::string() : ": " + why));
     std::free(fmarker);
     matrix_free(mat);
@@ -290,7 +300,8 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
           break;
         }
         model_nnz_now = (ssize_t)model_nnz(dmodel);
-        evaluated = evalset && model_evaluate(evalset, dmodel, 1, &ev) == SLIM_OK;
+        evaluated = evalset && (ranked ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev)
+                                       : model_evaluate(evalset, dmodel, 1, &ev)) == SLIM_OK;
         if (!evaluated && stride > 1) {  // (no silent evaluation of everybody)
           rc = SLIM_ERROR;
           break;
@@ -639,6 +650,51 @@ int32_t SLIMGPU_ModelEvaluate(slimgpu_evalset_t* es, const slimgpu_model_t* mode
   nvalid[0] = e.nvalid; nvalid[1] = e.nvalid_head; nvalid[2] = e.nvalid_tail;
   return SLIM_OK;
 }
+
+// ---------------------------------------------------- slim_gpu_rank.h ------
+
+slimgpu_evalset_t* SLIMGPU_EvalSetCreateRanked(slimgpu_matrix_t* mat, slim_t* tsthandle, const int32_t* fmarker,
+                                               int32_t fm_ncols, int32_t nusers, const int32_t* users,
+                                               int32_t* r_status) {
+  set_error("");
+  int32_t status = SLIM_ERROR;
+  slimgpu_evalset_t* es = evalset_create_ranked(mat, as_csr(tsthandle), fmarker, fm_ncols, nusers, users, &status);
+  if (r_status) *r_status = status;
+  return es;
+}
+
+int64_t SLIMGPU_EvalSetEntries(const slimgpu_evalset_t* es) { return evalset_entries(es); }
+
+int32_t SLIMGPU_ModelRanks(slimgpu_evalset_t* es, const slimgpu_model_t* model, int32_t* ranks, float* scores) {
+  set_error("");
+  return model_ranks(es, model, ranks, scores);
+}
+
+int32_t SLIMGPU_ModelEvaluateRanked(slimgpu_evalset_t* es, const slimgpu_model_t* model, int32_t ncutoffs,
+                                    const int32_t* cutoffs, double* metrics, int32_t* nvalid) {
+  set_error("");
+  if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
+  EvalResult ev[SLIMGPU_MAX_RANK_CUTOFFS];
+  const int32_t rc = model_evaluate_ranked(es, model, ncutoffs, cutoffs, ev);
+  if (rc != SLIM_OK) return rc;
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    double* m = metrics + 4 * k;
+    int32_t* n = nvalid + 3 * k;
+    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
+    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
+  }
+  return SLIM_OK;
+}
+
+slimgpu_model_t* SLIMGPU_ModelFromHost(slimgpu_matrix_t* mat, slim_t* model, int32_t* r_status) {
+  set_error("");
+  int32_t status = SLIM_ERROR;
+  slimgpu_model_t* dm = model_from_host(mat, as_csr(model), &status);
+  if (r_status) *r_status = status;
+  return dm;
+}
+
+double SLIMGPU_LastRankPrepassMs(void) { return last_rank_prepass_ms(); }
 
 int32_t SLIMGPU_MatrixPredict(int32_t nrcmds, const slimgpu_model_t* model, slimgpu_matrix_t* mat,
                               int32_t* output, float* scores) {

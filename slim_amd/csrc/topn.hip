@@ -19,8 +19,8 @@
 // The score/discovery vectors (12 bytes per item) live in a per-wavefront HBM slab.  A second kernel
 // (topn_chunk_kernel, below) keeps them in LDS and serves lists of up to 64 from models with sorted rows.
 //
-// Host side: every entry point -- predict_device / predict_device_view (a host history), matrix_predict
-// and model_evaluate (the resident matrix) -- stages what it lacks on the device (host_stage.hpp),
+// Host side: every entry point -- predict_device / predict_device_view (a host history), matrix_predict,
+// model_evaluate and the ranked calls model_ranks / model_evaluate_ranked (the resident matrix) -- stages what it lacks on the device (host_stage.hpp),
 // describes the model and the histories as views and goes through queue_scorer, the one place that
 // chooses the kernel, builds the split table, fills the kernel arguments and launches.
 #include <hip/hip_runtime.h>
@@ -49,6 +49,10 @@ struct ScorerWorkspace {
   DeviceBuffer<int32_t> queue, oid, ocnt;  // work queue; lists and their lengths (when they are wanted)
   DeviceBuffer<float> osc, score;          // list scores; wave kernel: score vectors
   DeviceBuffer<unsigned long long> disc;   // wave kernel: discovery vectors
+  // rank mode: (key, score) of every test entry from the pre-pass, (rank, score) out
+  DeviceBuffer<unsigned long long> tkey;
+  DeviceBuffer<float> tscore, rscore;
+  DeviceBuffer<int32_t> rank;
   int allocs = 0;                          // device allocations since the caller last cleared it
   template <class T>
   T* need(DeviceBuffer<T>& b, size_t n) {
@@ -75,10 +79,20 @@ struct slimgpu_evalset {
   slimamd::DeviceBuffer<unsigned long long> d_out;    // EvalOut
   slimamd::ScorerWorkspace ws;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // ranks of the held-out items (slim_gpu_rank.h): the test entries of the evaluated users and the longest of
+  // their test rows; where a position's entries start (listed users only: else the staged row pointer serves);
+  // the workspaces of SLIMGPU_ModelEvaluateRanked, made on first use; the pre-pass's own events
+  int64_t entries = 0, max_test = 0;
+  slimamd::DeviceBuffer<int64_t> d_tbase;
+  slimamd::DeviceBuffer<slimamd::UserTerms> d_rterms;  // [SLIMGPU_MAX_CUTOFFS][nsel]: one slice of cutoffs
+  slimamd::DeviceBuffer<unsigned long long> d_rout;    // RankOut
+  hipEvent_t evk0 = nullptr, evk1 = nullptr;
   ~slimgpu_evalset() {
     (void)hipSetDevice(device);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
+    if (evk0) (void)hipEventDestroy(evk0);
+    if (evk1) (void)hipEventDestroy(evk1);
   }
 };
 
@@ -288,6 +302,18 @@ struct TopN2Args {
   Cutoffs cut = {};
 };
 
+// rank mode (slim_gpu_rank.h): the scorer counts, for every test entry of the user, the candidates that stand
+// before it.  (score, key) of the test entries come from k_test_keys, which ran before the scorer.
+constexpr unsigned long long kNoCandidate = ~0ull;  // key of a test entry that is no candidate (every KeyT's kUnt)
+struct TopNRankArgs : TopN2Args {
+  const int64_t* tbase = nullptr;  // [nusers + 1]: where a position's test entries start in the arrays below
+  const unsigned long long* tkey = nullptr;  // discovery key of every test entry, kNoCandidate: not a candidate
+  const float* tscore = nullptr;
+  int32_t* rank = nullptr;    // out: 1 + candidates ahead, 0: not a candidate
+  float* rscore = nullptr;    // out: the entry's score, 0 when it is no candidate
+  int32_t g0 = 0, gsize = 0;  // this pass serves entries [g0, g0 + gsize) of every test row
+};
+
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
@@ -358,6 +384,87 @@ __global__ void k_row_split(int32_t nrows, int32_t nchunks, int32_t cw,
   }
 }
 
+// The pre-pass of the rank mode: (score, discovery key) of every test entry of the evaluated users, as the
+// scorer forms them for that item -- a chunk can only be counted against keys known before it is scanned.
+// One wavefront per position, its test entries one after the other.  For an entry t the LANES stand over the
+// history items: each finds t in its item's model row by binary search (rows ascend), so the dependent
+// searches of 64 history items run side by side; the found products are then added in lane order = history
+// order, starting from 0.0f + the first, products and sums rounded separately -- the additions of `update`
+// in the same order.  The first history index that has t, and t's position in that row, form the key.  An
+// entry equal to a history item, outside [0, ncols) or never touched is no candidate (kNoCandidate, score 0).
+__global__ __launch_bounds__(256) void k_test_keys(int32_t nsel, const int32_t* __restrict__ users, int32_t wrows,
+                                                   int32_t ncols, int32_t pos_bits, const int64_t* __restrict__ wptr,
+                                                   const int32_t* __restrict__ wind, const float* __restrict__ wval,
+                                                   const int64_t* __restrict__ hptr, const int32_t* __restrict__ hind,
+                                                   const float* __restrict__ hval, const int64_t* __restrict__ tptr,
+                                                   const int32_t* __restrict__ tind, const int64_t* __restrict__ tbase,
+                                                   unsigned long long* __restrict__ tkey,
+                                                   float* __restrict__ tscore) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t q = wave; q < nsel; q += nwaves) {
+    const int32_t u = users ? users[q] : (int32_t)q;
+    const int64_t h0 = hptr[u], h1 = hptr[u + 1];
+    const int64_t t0 = tptr[u], t1 = tptr[u + 1];
+    const int64_t out = tbase[q];
+    for (int64_t z = t0; z < t1; ++z) {
+      const int32_t t = tind[z];
+      unsigned long long key = kNoCandidate;
+      float acc = 0.0f;
+      bool in_hist = false, touched = false;
+      if (t >= 0 && t < ncols) {
+        for (int64_t hb = h0; hb < h1 && !in_hist; hb += 64) {
+          const int64_t h = hb + lane;
+          bool found = false, same = false;
+          float prod = 0.0f;
+          uint32_t pos = 0;
+          if (h < h1) {
+            const int32_t i = hind[h];
+            same = i == t;
+            if (i >= 0 && i < wrows) {
+              const int64_t s = wptr[i], e = wptr[i + 1];
+              int64_t lo = s, hi = e;
+              while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (wind[mid] < t) lo = mid + 1; else hi = mid;
+              }
+              if (lo < e && wind[lo] == t) {
+#pragma clang fp contract(off)
+                found = true;
+                prod = (hval ? hval[h] : 1.0f) * wval[lo];
+                pos = (uint32_t)(lo - s);
+              }
+            }
+          }
+          in_hist = __ballot(same) != 0;
+          unsigned long long mask = __ballot(found);
+          if (mask && !touched) {
+            const int l = __builtin_ctzll(mask);
+            key = ((unsigned long long)(uint32_t)(hb - h0 + l) << pos_bits) |
+                  (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)pos, l);
+            touched = true;
+          }
+          while (mask) {  // the in-order float sum over the lanes
+#pragma clang fp contract(off)
+            const int l = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(prod), l));
+          }
+        }
+      }
+      if (in_hist || !touched) {
+        key = kNoCandidate;
+        acc = 0.0f;
+      }
+      if (lane == 0) {
+        tkey[out + (z - t0)] = key;
+        tscore[out + (z - t0)] = acc;
+      }
+    }
+  }
+}
+
 // KeyT: discovery key (history index << pos_bits | position in the model row).  32 bits when
 // the longest history and the longest model row allow it (8 bytes of LDS per item: chunks of
 // 2304 ids), else 64.
@@ -370,8 +477,12 @@ __global__ void k_row_split(int32_t nrows, int32_t nchunks, int32_t cw,
 // cut.c[k] (eval_terms.hpp: the additions behind a cutoff are a prefix of those behind the next one, so
 // every record is the one a separate evaluation with lists of that length forms).  Lists are written only
 // when an output pointer is given.
-template <int NW, typename KeyT, bool EVAL>
-__device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
+// RANK (Args = TopNRankArgs): no lists.  The merge area holds the user's test keys and one integer count per
+// key; the candidate scan of a chunk adds to each count the chunk's slots that stand before the key (a ballot
+// and a popcount per 64 slots, gathered in registers -- lane j owns key j -- and added to LDS once per chunk);
+// after the chunks wavefront 0 writes rank = 1 + count.  Everything up to and including `update` is shared.
+template <int NW, typename KeyT, bool EVAL, bool RANK = false, class Args = TopN2Args>
+__device__ __forceinline__ void topn_chunk_body(const Args& T) {
   constexpr KeyT kUnt = ~KeyT(0), kExc = ~KeyT(0) - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int D = kT2Depth;
@@ -396,6 +507,34 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
     if (u >= T.nusers) break;
     if (T.users) u = __builtin_amdgcn_readfirstlane(T.users[u]);
     const int64_t h0 = uni64(T.hptr[u]), h1 = uni64(T.hptr[u + 1]);
+
+    // rank mode: the user's test keys of this pass into the merge area, counts zeroed
+    float* r_s = reinterpret_cast<float*>(marea);
+    KeyT* r_d = reinterpret_cast<KeyT*>(marea + NW * kT2MaxN * 4);
+    int* r_c = reinterpret_cast<int*>(marea + NW * kT2MaxN * 12);
+    int ng = 0;          // test entries of this user served by this pass
+    int64_t rbase = 0;   // ... and where they start in the rank arrays
+    if constexpr (RANK) {
+      const int64_t tlen = uni64(T.tptr[u + 1]) - uni64(T.tptr[u]);
+      const int64_t left = tlen - (int64_t)T.g0;
+      ng = left < 0 ? 0 : (left < (int64_t)T.gsize ? (int)left : T.gsize);
+      if (ng == 0 || h0 == h1) {  // nothing to count (an empty history: k_test_keys said "no candidate")
+        rbase = uni64(T.tbase[__builtin_amdgcn_readfirstlane(s_user)]) + T.g0;
+        for (int z = tid; z < ng; z += 64 * NW) {
+          T.rank[rbase + z] = 0;
+          T.rscore[rbase + z] = 0.0f;
+        }
+        __syncthreads();  // s_user is read: the next position may be drawn
+        continue;
+      }
+      rbase = uni64(T.tbase[__builtin_amdgcn_readfirstlane(s_user)]) + T.g0;
+      for (int z = tid; z < ng; z += 64 * NW) {
+        r_s[z] = T.tscore[rbase + z];
+        r_d[z] = (KeyT)T.tkey[rbase + z];
+        r_c[z] = 0;
+      }
+      __syncthreads();
+    }
 
     // this wavefront's N best so far: lane t holds rank t
     float ls = 0.0f;
@@ -516,6 +655,37 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
         }
       }
 
+      if constexpr (RANK) {
+        // candidates of this chunk against the user's test keys: integer adds, so any order
+        for (int jb = 0; jb < ng; jb += 64) {
+          const int nj = (ng - jb) < 64 ? (ng - jb) : 64;
+          float my_ts = 0.0f;
+          KeyT my_td = kUnt;
+          if (lane < nj) {
+            my_ts = r_s[jb + lane];
+            my_td = r_d[jb + lane];
+          }
+          int my_cnt = 0;
+          for (int kb = 0; kb < width; kb += 64) {
+            const int k = kb + lane;
+            KeyT d = kUnt;
+            float sc = 0.0f;
+            if (k < width) {
+              d = disc[k];
+              sc = score[k];
+            }
+            const bool cand = d < kExc;
+            if (__ballot(cand) == 0) continue;
+            for (int j = 0; j < nj; ++j) {
+              const float ts = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_ts), j));
+              const KeyT td = readlane_key(my_td, j);
+              const int ahead = __popcll(__ballot(cand && better(sc, d, ts, td)));
+              if (lane == j) my_cnt += ahead;
+            }
+          }
+          if (lane < nj && my_cnt) atomicAdd(&r_c[jb + lane], my_cnt);
+        }
+      } else
       // candidates of this chunk against the wavefront's N best
       for (int kb = 0; kb < width; kb += 64) {
         const int k = kb + lane;
@@ -538,6 +708,17 @@ __device__ __forceinline__ void topn_chunk_body(const TopN2Args& T) {
       }
     }
 
+    if constexpr (RANK) {
+      __syncthreads();  // every wavefront's counts are in
+      if (wave == 0)
+        for (int z = lane; z < ng; z += 64) {
+          const bool cand = r_d[z] != kUnt;
+          T.rank[rbase + z] = cand ? 1 + r_c[z] : 0;
+          T.rscore[rbase + z] = cand ? r_s[z] : 0.0f;
+        }
+      __syncthreads();
+      continue;
+    }
     // merge the wavefronts' lists (wavefront 0), write the user's row
     if (lane < kT2MaxN) {
       m_s[wave * kT2MaxN + lane] = ls;
@@ -623,6 +804,10 @@ __global__ __launch_bounds__(64 * NW) void topn_chunk_kernel(const TopN2Args T) 
 template <int NW, typename KeyT>
 __global__ __launch_bounds__(64 * NW) void topn_chunk_eval_kernel(const TopN2Args T) {
   topn_chunk_body<NW, KeyT, true>(T);
+}
+template <int NW, typename KeyT>
+__global__ __launch_bounds__(64 * NW) void topn_chunk_rank_kernel(const TopNRankArgs T) {
+  topn_chunk_body<NW, KeyT, false, true, TopNRankArgs>(T);
 }
 
 // facts[0] = entries of the longest row, facts[1] = 1 when some row's ids are not strictly ascending
@@ -742,6 +927,15 @@ struct EvalTargets {  // the fused epilogue's inputs and output
   Cutoffs cut;       // cut.c[cut.n - 1] == the nrcmds the scorer is queued with
 };
 
+struct RankTargets {  // the rank mode's inputs; the outputs are ws.rank / ws.rscore
+  const int64_t* tptr;
+  const int32_t* tind;
+  const int64_t* tbase;    // [positions + 1]: where a position's test entries start
+  int64_t entries;         // test entries of all positions
+  int64_t max_test;        // the longest test row among them
+  hipEvent_t pre0, pre1;   // around the pre-pass (k_test_keys)
+};
+
 int wave_kernel_waves(int32_t nusers, int32_t nrcmds, int num_cus, size_t* lds_out) {
   const size_t lds = (size_t)nrcmds * 64 * (sizeof(float) + sizeof(unsigned long long) + sizeof(int));
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (128 * 1024) / lds));
@@ -778,7 +972,7 @@ void reserve_scorer(ScorerWorkspace& ws, int path, int32_t wrows, int32_t ncols,
 
 // How queue_scorer served a call.
 struct ScorerLaunch {
-  int path = 0;    // scorer_path
+  int path = 0;    // scorer_path; 3: the chunk kernel in rank mode; 0: rank mode refused (set_error says why)
   int groups = 0;  // workgroups of the chunk kernel, wavefronts of the wave kernel
   ChunkPlan plan;  // the chunk kernel's geometry
   std::chrono::steady_clock::time_point launched;  // host time at which the scorer kernel itself was queued
@@ -786,15 +980,36 @@ struct ScorerLaunch {
 
 // Queues the scorer on `stream`: lists into ws.oid / osc / ocnt when `lists` (always on path 2), the
 // users' terms into ev->terms when ev is given.
+// Rank mode (rk given; nrcmds, ev and lists are not used): the ranks and scores of the positions' test entries
+// into ws.rank / ws.rscore.  Only the chunk kernel has a rank form.
 ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, int num_cus,
-                          hipStream_t stream, ScorerWorkspace& ws, const EvalTargets* ev, bool lists) {
+                          hipStream_t stream, ScorerWorkspace& ws, const EvalTargets* ev, bool lists,
+                          const RankTargets* rk = nullptr) {
   const int32_t ncols = std::max(W.ncols, 1);
   const ChunkPlan P = plan_chunks(ncols, W.max_row, H.max_hist, false);
+  if (rk) {
+    nrcmds = 1;
+    ev = nullptr;
+    lists = false;
+  }
   const int path = scorer_path(W, nrcmds, P);
   ScorerLaunch L;
   L.path = path;
   L.plan = P;
+  if (rk && path != 1) {
+    set_error("ranks of the held-out items need the chunk scorer: model rows ascending by id, fewer than 2^31 model "
+              "entries, a split table of at most 2 GB" +
+              std::string(std::getenv("SLIM_TOPN_KERNEL") ? " (SLIM_TOPN_KERNEL is set)" : ""));
+    L.path = 0;
+    return L;
+  }
   reserve_scorer(ws, path, W.nrows, ncols, P, H.nusers, nrcmds, num_cus, lists);
+  if (rk) {
+    ws.need(ws.tkey, (size_t)rk->entries);
+    ws.need(ws.tscore, (size_t)rk->entries);
+    ws.need(ws.rank, (size_t)rk->entries);
+    ws.need(ws.rscore, (size_t)rk->entries);
+  }
   HIP_TRY(hipMemsetAsync(ws.queue.get(), 0, 2 * sizeof(int32_t), stream));
   if (lists || path == 2) HIP_TRY(hipMemsetAsync(ws.ocnt.get(), 0, sizeof(int32_t) * (size_t)H.nusers, stream));
   if (path == 1) {
@@ -804,7 +1019,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t 
                          0, stream, W.nrows, P.nchunks, P.cw, W.d_ptr, W.d_ind, ws.split.get());
       HIP_TRY(hipGetLastError());
     }
-    TopN2Args T{};
+    TopNRankArgs T{};
     T.nusers = H.nusers;
     T.users = H.users;
     T.nitems_rows = W.nrows;
@@ -825,6 +1040,43 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t 
       T.cut = ev->cut;
     }
     const bool w16 = P.t2w == 16;
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / P.t2w, (160 * 1024) / (P.lds + 64)));
+    const int nwg = std::max(1, std::min<int>(H.nusers, num_cus * per_cu));
+    L.groups = nwg;
+    if (rk) {
+      L.path = 3;
+      if (rk->entries <= 0) return L;  // (no test entry: nothing to rank)
+      HIP_TRY(hipEventRecord(rk->pre0, stream));
+      const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)H.nusers + 3) / 4, (int64_t)num_cus * 16));
+      hipLaunchKernelGGL(k_test_keys, dim3(blocks), dim3(256), 0, stream, H.nusers, H.users, W.nrows, ncols, P.pos_bits,
+                         W.d_ptr, W.d_ind, W.d_val, H.ptr, H.ind, H.val, rk->tptr, rk->tind, rk->tbase, ws.tkey.get(),
+                         ws.tscore.get());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(rk->pre1, stream));
+      T.tptr = rk->tptr; T.tind = rk->tind; T.tbase = rk->tbase;
+      T.tkey = ws.tkey.get(); T.tscore = ws.tscore.get(); T.rank = ws.rank.get(); T.rscore = ws.rscore.get();
+      // a test row longer than the merge area holds keys for: one scoring pass per group of entries
+      int group = P.t2w * kT2MaxN;
+      if (const char* e = std::getenv("SLIM_TOPN_RANK_GROUP")) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v < group) group = v;
+      }
+      T.gsize = group;
+      auto rfn = P.key32 ? (w16 ? topn_chunk_rank_kernel<16, uint32_t> : topn_chunk_rank_kernel<8, uint32_t>)
+                         : (w16 ? topn_chunk_rank_kernel<16, unsigned long long>
+                                : topn_chunk_rank_kernel<8, unsigned long long>);
+      if (P.lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rfn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)P.lds));
+      L.launched = std::chrono::steady_clock::now();
+      for (int64_t g0 = 0; g0 < rk->max_test; g0 += group) {
+        if (g0 > 0) HIP_TRY(hipMemsetAsync(ws.queue.get(), 0, 2 * sizeof(int32_t), stream));
+        T.g0 = (int32_t)g0;
+        hipLaunchKernelGGL(rfn, dim3(nwg), dim3(64 * P.t2w), P.lds, stream, T);
+        HIP_TRY(hipGetLastError());
+      }
+      return L;
+    }
     auto kfn = ev ? (P.key32 ? (w16 ? topn_chunk_eval_kernel<16, uint32_t> : topn_chunk_eval_kernel<8, uint32_t>)
                              : (w16 ? topn_chunk_eval_kernel<16, unsigned long long>
                                     : topn_chunk_eval_kernel<8, unsigned long long>))
@@ -834,11 +1086,8 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t 
     if (P.lds > 64 * 1024)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)P.lds));
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / P.t2w, (160 * 1024) / (P.lds + 64)));
-    const int nwg = std::max(1, std::min<int>(H.nusers, num_cus * per_cu));
-    L.groups = nwg;
     L.launched = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(kfn, dim3(nwg), dim3(64 * P.t2w), P.lds, stream, T);
+    hipLaunchKernelGGL(kfn, dim3(nwg), dim3(64 * P.t2w), P.lds, stream, static_cast<const TopN2Args&>(T));
     HIP_TRY(hipGetLastError());
   } else {
     size_t lds = 0;
@@ -1022,9 +1271,12 @@ void queue_row_facts(void* stream, int num_cus, int32_t nrows, const int64_t* d_
   HIP_TRY(hipGetLastError());
 }
 
-slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
-                                  int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
-                                  const int32_t* users, int32_t* status) {
+namespace {
+
+// ranked: an eval set with no list length (SLIMGPU_EvalSetCreateRanked; ncutoffs == 0, cutoffs unused)
+slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                       int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
+                                       const int32_t* users, int32_t* status, bool ranked) {
   auto fail = [&](int32_t st) {
     if (status) *status = st;
     return static_cast<slimgpu_evalset_t*>(nullptr);
@@ -1034,9 +1286,9 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
     return fail(SLIM_ERROR_INPUT);
   };
   DeviceCsrView R;
-  if (!mat || !tst || !tst->rowptr || !fmarker || fm_ncols < 0 || !cutoffs)
+  if (!mat || !tst || !tst->rowptr || !fmarker || fm_ncols < 0 || (!cutoffs && !ranked))
     return refuse("bad arguments (a staged matrix, a test handle, a marker, the list lengths)");
-  if (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS)
+  if (!ranked && (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS))
     return refuse("between 1 and " + std::to_string(SLIMGPU_MAX_CUTOFFS) + " list lengths, not " + std::to_string(ncutoffs));
   Cutoffs cut = {};
   cut.n = ncutoffs;
@@ -1058,7 +1310,7 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
       return refuse("user " + std::to_string(users[q]) + " is outside [0, " + std::to_string(nall) + ")");
     if (q > 0 && users[q] <= users[q - 1]) return refuse("the user ids must ascend strictly");
   }
-  const int32_t nrcmds = cut.c[cut.n - 1];
+  const int32_t nrcmds = ranked ? 1 : cut.c[cut.n - 1];
   slimgpu_evalset* es = nullptr;
   try {
     (void)hipGetLastError();
@@ -1081,6 +1333,26 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
     if (users) {  // (pageable source: the copy has left the caller's array when the call returns)
       es->d_users = DeviceBuffer<int32_t>((size_t)nsel);
       HIP_TRY(hipMemcpyAsync(es->d_users.get(), users, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
+    }
+    // the test entries of the evaluated users, the longest of their test rows and, for listed users, where
+    // every position's entries start in the rank arrays (every user: the staged row pointer is that)
+    std::vector<int64_t> h_tbase;
+    if (users || tst->rowptr[0] != 0) {
+      h_tbase.resize((size_t)nsel + 1);
+      h_tbase[0] = 0;
+      for (int32_t q = 0; q < nsel; ++q) {
+        const int32_t u = users ? users[q] : q;
+        const int64_t len = tst->rowptr[u + 1] - tst->rowptr[u];
+        es->max_test = std::max(es->max_test, len);
+        h_tbase[(size_t)q + 1] = h_tbase[(size_t)q] + len;
+      }
+      es->entries = h_tbase[(size_t)nsel];
+      es->d_tbase = DeviceBuffer<int64_t>((size_t)nsel + 1);
+      HIP_TRY(hipMemcpyAsync(es->d_tbase.get(), h_tbase.data(), sizeof(int64_t) * ((size_t)nsel + 1),
+                             hipMemcpyHostToDevice, stream));  // (h_tbase outlives the synchronize below)
+    } else {
+      es->entries = es->tst.nnz;
+      es->max_test = es->tst.max_row;
     }
     // the longest history of the evaluated users and the number of their history entries, once (the
     // scorer's key width needs the first)
@@ -1109,6 +1381,8 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
                    /*lists=*/false);
     HIP_TRY(hipEventCreate(&es->ev0));
     HIP_TRY(hipEventCreate(&es->ev1));
+    HIP_TRY(hipEventCreate(&es->evk0));
+    HIP_TRY(hipEventCreate(&es->evk1));
     if (status) *status = SLIM_OK;
     return es;
   } catch (const HipFail& e) {
@@ -1121,6 +1395,21 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
   }
 }
 
+}  // namespace
+
+slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                  int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
+                                  const int32_t* users, int32_t* status) {
+  return evalset_create_impl(mat, tst, fmarker, fm_ncols, ncutoffs, cutoffs, nusers, users, status, /*ranked=*/false);
+}
+
+slimgpu_evalset_t* evalset_create_ranked(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                         int32_t fm_ncols, int32_t nusers, const int32_t* users, int32_t* status) {
+  return evalset_create_impl(mat, tst, fmarker, fm_ncols, 0, nullptr, nusers, users, status, /*ranked=*/true);
+}
+
+int64_t evalset_entries(const slimgpu_evalset_t* es) { return es ? es->entries : -1; }
+
 void evalset_free(slimgpu_evalset_t* es) { delete es; }
 
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es) { return es ? es->cut.n : 0; }
@@ -1132,7 +1421,7 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
     set_error("SLIMGPU_ModelEvaluate: needs an eval set and a resident model with a row view");
     return SLIM_ERROR_INPUT;
   }
-  if (ncutoffs != es->cut.n) {
+  if (ncutoffs != es->cut.n || es->cut.n < 1) {
     set_error("SLIMGPU_ModelEvaluate: the eval set holds " + std::to_string(es->cut.n) + " list lengths, the call asks for " +
               std::to_string(ncutoffs));
     return SLIM_ERROR_INPUT;
@@ -1197,6 +1486,181 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
     return SLIM_OK;
   } catch (const HipFail& e) {
     return hip_failure("SLIMGPU_ModelEvaluate", e);
+  }
+}
+
+// ---- the rank of every held-out item (slim_gpu_rank.h) ------------------------------------------
+namespace {
+
+thread_local double g_rank_prepass_ms = 0;
+
+struct RankOut {  // what SLIMGPU_ModelEvaluateRanked brings down: the first 8 + 32 * ncutoffs bytes
+  unsigned long long streamed;
+  EvalSums sums[SLIMGPU_MAX_RANK_CUTOFFS];
+};
+
+// the checks both ranked calls share, then the scorer in rank mode on the matrix's stream: ranks and scores of
+// the eval set's test entries are in es->ws.rank / rscore when the stream has run.  SLIM_OK or a refusal.
+int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, DeviceRowView& W,
+                    DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st) {
+  if (!es || !model || model_row_view(model, &W) != SLIM_OK || matrix_csr_view(es->mat, &R) != SLIM_OK) {
+    set_error(std::string(who) + ": needs an eval set and a resident model with a row view");
+    return SLIM_ERROR_INPUT;
+  }
+  if (const int32_t rc = check_pair(who, R, W); rc != SLIM_OK) return rc;
+  if (es->device != R.device) {
+    set_error(std::string(who) + ": the eval set and the matrix live on different devices");
+    return SLIM_ERROR_INPUT;
+  }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(R.device));
+  hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  es->ws.allocs = 0;
+  g_rank_prepass_ms = 0;
+  if (es->nsel <= 0) {
+    st.path = 3;
+    return SLIM_OK;
+  }
+  H.nusers = es->nsel;
+  H.users = es->listed ? es->d_users.get() : nullptr;
+  H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
+  H.max_hist = es->max_hist;
+  const RankTargets rk = {es->tst.ptr.get(), es->tst.ind.get(),
+                          es->d_tbase.get() ? es->d_tbase.get() : es->tst.ptr.get(),
+                          es->entries, es->max_test, es->evk0, es->evk1};
+  HIP_TRY(hipEventRecord(es->ev0, stream));
+  const ScorerLaunch L = queue_scorer(W, H, 1, R.num_cus, stream, es->ws, nullptr, false, &rk);
+  if (L.path != 3) {
+    set_error(std::string(who) + ": " + last_error());
+    return SLIM_ERROR_INPUT;
+  }
+  st.path = 3;
+  return SLIM_OK;
+}
+
+// after the stream has run: the times of the scorer (ev0 .. ev1) and of its pre-pass
+void read_rank_times(slimgpu_evalset_t* es, slimgpu_eval_stats_t& st) {
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, es->ev0, es->ev1));
+  st.kernel_ms = ms;
+  if (es->entries > 0) {
+    HIP_TRY(hipEventElapsedTime(&ms, es->evk0, es->evk1));
+    g_rank_prepass_ms = ms;
+  }
+}
+
+}  // namespace
+
+double last_rank_prepass_ms() { return g_rank_prepass_ms; }
+
+int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    DeviceRowView W;
+    DeviceCsrView R;
+    HistoryView H;
+    if (const int32_t rc = queue_ranks("SLIMGPU_ModelRanks", es, model, W, R, H, st); rc != SLIM_OK) return rc;
+    if (es->nsel > 0) {
+      hipStream_t stream = static_cast<hipStream_t>(R.stream);
+      HIP_TRY(hipEventRecord(es->ev1, stream));
+      const size_t n = (size_t)es->entries;
+      if (ranks && n) {
+        HIP_TRY(hipMemcpyAsync(ranks, es->ws.rank.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+        st.d2h_bytes += (int64_t)(sizeof(int32_t) * n);
+      }
+      if (scores && n) {
+        HIP_TRY(hipMemcpyAsync(scores, es->ws.rscore.get(), sizeof(float) * n, hipMemcpyDeviceToHost, stream));
+        st.d2h_bytes += (int64_t)(sizeof(float) * n);
+      }
+      HIP_TRY(hipStreamSynchronize(stream));
+      read_rank_times(es, st);
+    }
+    st.device_allocs = es->ws.allocs;
+    st.w_rows_read = es->hist_entries;
+    st.total_ms = ms_since(t_begin);
+    g_eval_stats = st;
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_ModelRanks", e);
+  }
+}
+
+int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs,
+                              const int32_t* cutoffs, EvalResult* out) {
+  if (!cutoffs || !out || ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_RANK_CUTOFFS) {
+    set_error("SLIMGPU_ModelEvaluateRanked: between 1 and " + std::to_string(SLIMGPU_MAX_RANK_CUTOFFS) +
+              " cutoffs, not " + std::to_string(ncutoffs));
+    return SLIM_ERROR_INPUT;
+  }
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    if (cutoffs[k] < 1) {
+      set_error("SLIMGPU_ModelEvaluateRanked: a cutoff must be at least 1, not " + std::to_string(cutoffs[k]));
+      return SLIM_ERROR_INPUT;
+    }
+    if (k > 0 && cutoffs[k] <= cutoffs[k - 1]) {
+      set_error("SLIMGPU_ModelEvaluateRanked: the cutoffs must ascend strictly");
+      return SLIM_ERROR_INPUT;
+    }
+    out[k] = EvalResult();
+  }
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    DeviceRowView W;
+    DeviceCsrView R;
+    HistoryView H;
+    if (const int32_t rc = queue_ranks("SLIMGPU_ModelEvaluateRanked", es, model, W, R, H, st); rc != SLIM_OK) return rc;
+    RankOut h = {};
+    if (es->nsel > 0) {
+      hipStream_t stream = static_cast<hipStream_t>(R.stream);
+      const size_t nterms = (size_t)SLIMGPU_MAX_CUTOFFS * (size_t)es->nsel;
+      if (es->d_rterms.bytes() < sizeof(UserTerms) * nterms) ++es->ws.allocs;
+      UserTerms* d_terms = es->d_rterms.reserve(nterms);
+      if (!es->d_rout.get()) ++es->ws.allocs;
+      RankOut* d_out = reinterpret_cast<RankOut*>(es->d_rout.reserve(sizeof(RankOut) / sizeof(unsigned long long)));
+      // the terms workspace holds 8 records per position: the cutoffs in slices of SLIMGPU_MAX_CUTOFFS
+      for (int32_t k0 = 0; k0 < ncutoffs; k0 += SLIMGPU_MAX_CUTOFFS) {
+        Cutoffs cut = {};
+        cut.n = std::min<int32_t>(SLIMGPU_MAX_CUTOFFS, ncutoffs - k0);
+        for (int32_t k = 0; k < cut.n; ++k) cut.c[k] = cutoffs[k0 + k];
+        launch_rank_terms(stream, R.num_cus, es->nsel, H.users, cut, es->ws.rank.get(),
+                          es->d_tbase.get() ? es->d_tbase.get() : es->tst.ptr.get(), es->tst.ptr.get(),
+                          es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, d_terms);
+        launch_sum_in_user_order(stream, es->nsel, cut.n, d_terms, d_out->sums + k0);
+      }
+      HIP_TRY(hipEventRecord(es->ev1, stream));
+      HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
+      if (es->hist_entries > 0 && W.nnz > 0) {
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)es->nsel + 3) / 4, R.num_cus * 8));
+        hipLaunchKernelGGL(k_streamed_entries, dim3(blocks), dim3(256), 0, stream, es->nsel, H.users, R.d_ptr, R.d_ind,
+                           W.nrows, W.d_ptr, &d_out->streamed);
+        HIP_TRY(hipGetLastError());
+      }
+      const size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncutoffs;
+      HIP_TRY(hipMemcpyAsync(&h, d_out, down, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      st.d2h_bytes = (int64_t)down;
+      read_rank_times(es, st);
+    }
+    for (int32_t k = 0; k < ncutoffs; ++k) {
+      const EvalSums& s = h.sums[k];
+      out[k].nvalid = s.n[0];
+      out[k].nvalid_head = s.n[1];
+      out[k].nvalid_tail = s.n[2];
+      out[k].hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0;
+      out[k].hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0;
+      out[k].hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
+      out[k].arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
+    }
+    st.device_allocs = es->ws.allocs;
+    st.w_rows_read = es->hist_entries;
+    st.w_bytes = 8.0 * (double)h.streamed;
+    st.total_ms = ms_since(t_begin);
+    g_eval_stats = st;
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_ModelEvaluateRanked", e);
   }
 }
 

@@ -158,11 +158,12 @@ class Evaluator(object):
     the model against the staged training matrix and brings down HR / ARHR only -- of the longest
     lists; `evaluate_at(resident_model)` gives the figures of every list length, from the same pass."""
 
-    def __init__(self, lib, handle, matrix, cutoffs=(10,)):
+    def __init__(self, lib, handle, matrix, cutoffs=(10,), indptr=None):
         self._lib = lib
         self.handle = C.c_void_p(handle)
         self._matrix = matrix      # borrowed by the eval set: keep it alive
         self.cutoffs = tuple(int(c) for c in cutoffs)
+        self.indptr = indptr       # ranks(): where every position's test entries start
 
     def evaluate(self, model):
         met = np.zeros(4, np.float64)
@@ -184,6 +185,38 @@ class Evaluator(object):
         return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
+
+    def ranks(self, model, scores=False):
+        """SLIMGPU_ModelRanks: the rank of every test entry of the evaluated users among the user's candidates
+        (1 = the head of every list; 0 = in no list of any length).  Returns (ranks, indptr[, scores]): the
+        entries of position q are ranks[indptr[q]:indptr[q + 1]], in the order of the user's test row."""
+        n = int(self._lib.SLIMGPU_EvalSetEntries(self.handle))
+        rk = np.zeros(max(n, 1), np.int32)
+        sc = np.zeros(max(n, 1), np.float32) if scores else None
+        st = self._lib.SLIMGPU_ModelRanks(self.handle, model.handle, rk.ctypes.data_as(C.c_void_p),
+                                          None if sc is None else sc.ctypes.data_as(C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_ModelRanks failed (%d): %s" % (st, _lib.last_error()))
+        return (rk[:n], self.indptr, sc[:n]) if scores else (rk[:n], self.indptr)
+
+    def evaluate_ranked(self, model, cutoffs):
+        """SLIMGPU_ModelEvaluateRanked: one dict per cutoff (evaluate_at()'s keys), at ANY list lengths
+        (ascending, at most 32), from the ranks of the held-out items -- no list is formed."""
+        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
+        n = cut.size
+        met = np.zeros(4 * max(n, 1), np.float64)
+        nv = np.zeros(3 * max(n, 1), np.int32)
+        st = self._lib.SLIMGPU_ModelEvaluateRanked(self.handle, model.handle, n, cut.ctypes.data_as(C.c_void_p),
+                                                   met, nv)
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_ModelEvaluateRanked failed (%d): %s" % (st, _lib.last_error()))
+        return [{"nrcmds": int(c), "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
+                 "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
+                 "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(cut)]
+
+    def prepass_ms(self):
+        """Milliseconds of the pre-pass (the test entries' scores and keys) of the most recent ranked call."""
+        return float(self._lib.SLIMGPU_LastRankPrepassMs())
 
     def stats(self):
         return eval_stats(self._lib)
@@ -319,13 +352,37 @@ class DeviceMatrix(object):
         self._lib.SLIMGPU_LastStats(C.byref(stats))
         return ResidentModel(self._lib, h), stats.as_dict()
 
-    def evaluator(self, T, nrcmds=10, fmarker=None, R=None, cutoffs=None, users=None):
+    def model_from_scipy(self, W):
+        """SLIMGPU_ModelFromHost: a model given as a scipy matrix (row i = the scores item i gives; the transpose
+        of what learn() returns as columns is the same matrix) made resident on this matrix's device, for the
+        resident scorers and as a warm start.  The ids of every row must ascend strictly."""
+        W = sp.csr_matrix(W)
+        ptr = np.ascontiguousarray(W.indptr, dtype=np.intp)
+        ind = np.ascontiguousarray(W.indices, dtype=np.int32)
+        val = np.ascontiguousarray(W.data, dtype=np.float32)
+        hw = C.c_void_p()
+        st = self._lib.Py_csr_wrapper(W.shape[0], ptr, ind, val.ctypes.data_as(C.c_void_p), C.byref(hw))
+        if st != SLIM_OK:
+            raise RuntimeError("Py_csr_wrapper failed (%d)" % st)
+        C.cast(hw, C.POINTER(_lib.CsrView)).contents.ncols = W.shape[1]
+        st = C.c_int32(0)
+        try:
+            h = self._lib.SLIMGPU_ModelFromHost(self.handle, hw, C.byref(st))
+        finally:
+            self._lib.Py_csr_free(hw)
+        if not h:
+            raise RuntimeError("SLIMGPU_ModelFromHost failed (%d): %s" % (st.value, _lib.last_error()))
+        return ResidentModel(self._lib, h)
+
+    def evaluator(self, T, nrcmds=10, fmarker=None, R=None, cutoffs=None, users=None, ranked=False):
         """SLIMGPU_EvalSetCreateAt: stage the test matrix T (scipy, one row per user) for evaluations
         of resident models against this matrix.  cutoffs: the list lengths (ascending, at most 8 of
         1..128; None: [nrcmds]), all served by one scoring pass.  users: ascending user ids to evaluate
         (None: every user).  fmarker=None: SLIM_DetermineHeadAndTail over the
         training rows with ncols = the larger of the two matrices' widths, as Py_SLIM_Mselect does
-        (the rows from_scipy staged; R, a scipy matrix, for a matrix adopted from device pointers)."""
+        (the rows from_scipy staged; R, a scipy matrix, for a matrix adopted from device pointers).
+        ranked=True: SLIMGPU_EvalSetCreateRanked, an eval set with no list length, for ranks() and
+        evaluate_ranked() (which every eval set serves)."""
         T = sp.csr_matrix(T)
         if fmarker is None:
             if R is not None:
@@ -346,17 +403,25 @@ class DeviceMatrix(object):
         sel = None if users is None else np.ascontiguousarray(users, dtype=np.int32).ravel()
         ht = _wrap_rows(self._lib, T)
         st = C.c_int32(0)
+        nsel, psel = (0, None) if sel is None else (sel.size, sel.ctypes.data_as(C.c_void_p))
         try:
-            h = self._lib.SLIMGPU_EvalSetCreateAt(self.handle, ht, fmarker, fmarker.size, cut.size,
-                                                  cut.ctypes.data_as(C.c_void_p),
-                                                  0 if sel is None else sel.size,
-                                                  None if sel is None else sel.ctypes.data_as(C.c_void_p),
-                                                  C.byref(st))
+            if ranked:
+                h = self._lib.SLIMGPU_EvalSetCreateRanked(self.handle, ht, fmarker, fmarker.size, nsel, psel,
+                                                          C.byref(st))
+            else:
+                h = self._lib.SLIMGPU_EvalSetCreateAt(self.handle, ht, fmarker, fmarker.size, cut.size,
+                                                      cut.ctypes.data_as(C.c_void_p), nsel, psel, C.byref(st))
         finally:
             self._lib.Py_csr_free(ht)
         if not h:
-            raise RuntimeError("SLIMGPU_EvalSetCreateAt failed (%d): %s" % (st.value, _lib.last_error()))
-        return Evaluator(self._lib, h, self, cut.tolist())
+            raise RuntimeError("SLIMGPU_EvalSetCreate%s failed (%d): %s" % ("Ranked" if ranked else "At", st.value,
+                                                                            _lib.last_error()))
+        # where every position's test entries start (ranks()): the evaluated users are the listed ones, or the
+        # first min(matrix rows, test rows)
+        nall = min(self.nrows, T.shape[0])
+        lens = np.diff(T.indptr)[:nall] if sel is None else np.diff(T.indptr)[sel]
+        indptr = np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
+        return Evaluator(self._lib, h, self, () if ranked else cut.tolist(), indptr)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)
