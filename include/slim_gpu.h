@@ -310,5 +310,6 @@ const char *SLIMGPU_LastError(void);
 #include "slim_gpu_planes.h"
 /* The rank of every held-out item: evaluation of resident models at any list length. */
 #include "slim_gpu_rank.h"
+#include "slim_gpu_lists.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

@@ -3,7 +3,7 @@
 # dominant one (cross-compiled here, no GPU needed):  bash scripts/isa_metadata.sh > profiles/rNN/isa_metadata.txt
 #
 # bash scripts/isa_metadata.sh topn [path/to/topn.hip]: the same figures of every instantiation of the top-N
-# scorers (topn_chunk_kernel / topn_chunk_eval_kernel / topn_chunk_rank_kernel <NW, KeyT>; y = 32-bit keys,
+# scorers (topn_chunk_kernel / topn_chunk_eval_kernel / topn_chunk_rank_kernel / topn_chunk_long_kernel <NW, KeyT>; y = 32-bit keys,
 # j = 64-bit keys) -- of this tree's topn.hip, or of another revision's copied into slim_amd/csrc under
 # another name (it needs the tree's headers)
 R=$(cd "$(dirname "$0")/.." && pwd)

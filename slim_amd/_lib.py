@@ -178,6 +178,30 @@ _RANK_SIGNATURES = {
 RANK_SYMBOLS = tuple(_RANK_SIGNATURES)
 MAX_RANK_CUTOFFS = 32   # SLIMGPU_MAX_RANK_CUTOFFS
 
+
+class ListStats(C.Structure):
+    """slimgpu_list_stats_t (include/slim_gpu_lists.h)."""
+    _fields_ = [("path", C.c_int32), ("slices", C.c_int32), ("candidates", C.c_int64), ("contenders", C.c_int64),
+                ("refine_passes", C.c_int64), ("lds_sorts", C.c_int64), ("key_refines", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# top-N lists of up to SLIMGPU_MAX_LIST items on the device (include/slim_gpu_lists.h); output / scores /
+# counts / users are passed as pointers (counts and users may be None)
+_LIST_SIGNATURES = {
+    "SLIMGPU_PredictLists": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_ModelPredictLists": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "SLIMGPU_MatrixPredictLists": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_LastListStats": (C.c_int32, [C.POINTER(ListStats)]),
+}
+
+LIST_SYMBOLS = tuple(_LIST_SIGNATURES)
+MAX_LIST = 4096         # SLIMGPU_MAX_LIST
+
 _lib = None
 
 
@@ -193,7 +217,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
                               list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
-                              list(_RANK_SIGNATURES.items())):
+                              list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

@@ -64,3 +64,5 @@ SLIM_DBG_TIME = 2
 SLIM_DBG_PROGRESS = 4
 SLIM_DBG_PROGRESS2 = 16
 SLIM_DBG_MEMORY = 2048
+
+SLIMGPU_MAX_LIST = 4096    # longest top-N list the device scorers form (include/slim_gpu_lists.h)

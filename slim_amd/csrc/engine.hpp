@@ -133,6 +133,13 @@ struct DeviceRowView {
 };
 int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
                             int32_t* output, float* scores, int32_t* counts);
+// slim_gpu_lists.h: lists of up to SLIMGPU_MAX_LIST (up to 128 on the paths of the calls above, beyond on the
+// chunk kernel's long-list form); SLIM_ERROR_INPUT with the outputs untouched where nothing on the device serves
+int32_t predict_lists(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
+                      int32_t* output, float* scores, int32_t* counts);
+int32_t predict_lists_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
+                           int32_t* output, float* scores, int32_t* counts);
+slimgpu_list_stats_t& last_list_stats();
 int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out);
 // the CSR of a staged matrix where it lies (the history of the resident scorer)
 struct DeviceCsrView {
@@ -168,6 +175,9 @@ int32_t evalset_cutoffs(const slimgpu_evalset_t* es);
 int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out);
 int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
                        float* scores);
+// users[nusers]: the rows scored, ascending (nullptr and 0: every row); counts may be null
+int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t nusers,
+                             const int32_t* users, int32_t* output, float* scores, int32_t* counts);
 slimgpu_eval_stats_t& last_eval_stats();
 // facts of a row view, for the scorers: d_facts[0] = entries of its longest row, d_facts[1] = 1 when the
 // ids of some row do not ascend strictly (both preset to 0 by the caller).  Queues one kernel on

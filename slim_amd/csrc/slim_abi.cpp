@@ -17,6 +17,8 @@
 
 using namespace slimamd;
 
+static int predict_policy();  // SLIM_PREDICT (below)
+
 namespace {
 
 slim_csr_t* as_csr(slim_t* h) { return static_cast<slim_csr_t*>(h); }
@@ -217,9 +219,9 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   // One GPU, CD: the models of the grid stay in HBM (engine.hpp: learn_resident) -- each pair is
   // warm-started from the previous one without an upload and scored where it lies; only its nnz is
   // printed, so nothing of it ever crosses PCIe.  SLIM_GPU_RESIDENT=0: host models as before.
-  // Lists of more than 128 have no device scorer, but the evaluation does not need the lists: the ranks of the
-  // held-out items (slim_gpu_rank.h) give the figures at any length.  Such a grid runs resident when the
-  // ranked eval set can be made, and as before (host models, the host scorer) when it cannot.
+  // Above 128 the evaluation does not need the lists: the ranks of the held-out items (slim_gpu_rank.h) give the
+  // figures at any length.  Such a grid runs resident when the ranked eval set can be made, and on host models
+  // when it cannot -- their lists of up to SLIMGPU_MAX_LIST come from the long-list scorer (slim_gpu_lists.h).
   const char* res_env = std::getenv("SLIM_GPU_RESIDENT");
   const bool may_reside = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 &&
                           !(res_env && std::atoi(res_env) == 0);
@@ -330,8 +332,9 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
       }
       model_nnz_now = model->rowptr[model->nrows];
       host_lists();
-      on_gpu = nrcmds <= 128 && predict_device(model, trn, nrcmds, lists.data(),
-                                               lsc.data(), lens.data()) == SLIM_OK;
+      on_gpu = nrcmds <= 128 ? predict_device(model, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK
+                             : nrcmds <= SLIMGPU_MAX_LIST && predict_policy() != 0 &&
+                                   predict_lists(model, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK;
       }
       if (evaluated) {
         // the figures came from the device: no lists, no host loop
@@ -397,7 +400,10 @@ int32_t Py_SLIM_GetTopN_1vsk(slim_t* model, int32_t nratings, int32_t* itemids, 
 }
 
 // Where Py_SLIM_Predict scores: SLIM_PREDICT=gpu|cpu|auto (default auto: the GPU scorer when
-// a device is present and nrcmds <= 128, else the host scorer; both give identical lists).
+// a device is present and nrcmds <= SLIMGPU_MAX_LIST -- the chunk or the wave kernel up to 128, the
+// long-list form of the chunk kernel beyond -- else the host scorer; all give identical lists).
+// A refusal of the device (above 128: model rows that do not ascend, a split table beyond 2 GB) falls
+// back to the host scorer under auto and is the call's status under gpu.
 static int predict_policy() {
   const char* e = std::getenv("SLIM_PREDICT");
   if (e && std::strcmp(e, "cpu") == 0) return 0;
@@ -417,9 +423,10 @@ int32_t Py_SLIM_Predict(int32_t nrcmds, slim_t* slimhandle, slim_t* trnhandle, i
   const slim_csr_t* trn = as_csr(trnhandle);
   if (!W || !trn || !W->rowptr || !trn->rowptr || nrcmds < 0) return SLIM_ERROR;
   const int policy = predict_policy();
-  if (policy == 2 || (policy == 1 && nrcmds >= 1 && nrcmds <= 128 && trn->nrows > 0 &&
+  if (policy == 2 || (policy == 1 && nrcmds >= 1 && nrcmds <= SLIMGPU_MAX_LIST && trn->nrows > 0 &&
                       device_count() > 0)) {
-    const int32_t rc = predict_device(W, trn, nrcmds, output, scores, nullptr);
+    const int32_t rc = nrcmds > 128 ? predict_lists(W, trn, nrcmds, output, scores, nullptr)
+                                    : predict_device(W, trn, nrcmds, output, scores, nullptr);
     if (rc == SLIM_OK || policy == 2) return rc;
   }
   TopNScratch ws(W->ncols > W->nrows ? W->ncols : W->nrows);
@@ -700,6 +707,39 @@ int32_t SLIMGPU_MatrixPredict(int32_t nrcmds, const slimgpu_model_t* model, slim
                               int32_t* output, float* scores) {
   set_error("");
   return matrix_predict(nrcmds, model, mat, output, scores);
+}
+
+// ---------------------------------------------------- slim_gpu_lists.h ------
+
+int32_t SLIMGPU_PredictLists(int32_t nrcmds, slim_t* model, slim_t* trn, int32_t* output, float* scores,
+                             int32_t* counts) {
+  set_error("");
+  return predict_lists(as_csr(model), as_csr(trn), nrcmds, output, scores, counts);
+}
+
+int32_t SLIMGPU_ModelPredictLists(int32_t nrcmds, const slimgpu_model_t* model, slim_t* trn, int32_t* output,
+                                  float* scores, int32_t* counts) {
+  set_error("");
+  DeviceRowView v;
+  if (!model || nrcmds < 1 || nrcmds > SLIMGPU_MAX_LIST || model_row_view(model, &v) != SLIM_OK) {
+    set_error("SLIMGPU_ModelPredictLists: bad arguments (a resident model with a row view, 1 <= nrcmds <= " +
+              std::to_string(SLIMGPU_MAX_LIST) + ")");
+    return SLIM_ERROR_INPUT;
+  }
+  return predict_lists_view(v, as_csr(trn), nrcmds, output, scores, counts);
+}
+
+int32_t SLIMGPU_MatrixPredictLists(int32_t nrcmds, const slimgpu_model_t* model, slimgpu_matrix_t* mat,
+                                   int32_t nusers, const int32_t* users, int32_t* output, float* scores,
+                                   int32_t* counts) {
+  set_error("");
+  return matrix_predict_lists(nrcmds, model, mat, nusers, users, output, scores, counts);
+}
+
+int32_t SLIMGPU_LastListStats(slimgpu_list_stats_t* out) {
+  if (!out) return SLIM_ERROR_INPUT;
+  *out = last_list_stats();
+  return SLIM_OK;
 }
 
 int32_t SLIMGPU_LastEvalStats(slimgpu_eval_stats_t* out) {

@@ -17,9 +17,11 @@
 //   * selection: one pass over the score vector with a per-lane sorted list of the N best
 //     (LDS), then N rounds of a wave-wide arg-max over the 64 list heads.
 // The score/discovery vectors (12 bytes per item) live in a per-wavefront HBM slab.  A second kernel
-// (topn_chunk_kernel, below) keeps them in LDS and serves lists of up to 64 from models with sorted rows.
+// (topn_chunk_kernel, below) keeps them in LDS and serves lists of up to 64 from models with sorted rows; its
+// long-list form (topn_chunk_long_kernel) selects by threshold and serves lists of up to SLIMGPU_MAX_LIST.
 //
-// Host side: every entry point -- predict_device / predict_device_view (a host history), matrix_predict,
+// Host side: every entry point -- predict_device / predict_device_view (a host history), matrix_predict, their
+// forms for lists of up to SLIMGPU_MAX_LIST (predict_lists / predict_lists_view / matrix_predict_lists),
 // model_evaluate and the ranked calls model_ranks / model_evaluate_ranked (the resident matrix) -- stages what it lacks on the device (host_stage.hpp),
 // describes the model and the histories as views and goes through queue_scorer, the one place that
 // chooses the kernel, builds the split table, fills the kernel arguments and launches.
@@ -53,6 +55,9 @@ struct ScorerWorkspace {
   DeviceBuffer<unsigned long long> tkey;
   DeviceBuffer<float> tscore, rscore;
   DeviceBuffer<int32_t> rank;
+  // long lists: one slab of ncols (image, key, id) records per workgroup; the counters of slimgpu_list_stats_t
+  DeviceBuffer<uint4> slab;
+  DeviceBuffer<unsigned long long> lstats;
   int allocs = 0;                          // device allocations since the caller last cleared it
   template <class T>
   T* need(DeviceBuffer<T>& b, size_t n) {
@@ -314,6 +319,19 @@ struct TopNRankArgs : TopN2Args {
   int32_t g0 = 0, gsize = 0;  // this pass serves entries [g0, g0 + gsize) of every test row
 };
 
+// long lists (slim_gpu_lists.h): the candidates of a user go to the workgroup's slab, a histogram over the
+// leading bits of their order finds the N-th, the winners are put in order in LDS.
+constexpr int kLongMaxN = SLIMGPU_MAX_LIST;
+constexpr int kLongBins = 2048;      // 11 bits per selection pass
+constexpr int kLongSortCap = 2048;   // contenders that are sorted in LDS rather than refined further
+struct TopNLongArgs : TopN2Args {
+  uint4* slab = nullptr;               // [workgroups][ncols]: (image, key high, key low, id)
+  unsigned long long* stats = nullptr; // candidates, contenders, refine passes, LDS sorts, key refinements
+  int32_t user0 = 0;                   // without a user list: position q is user user0 + q
+  int32_t sort_cap = kLongSortCap;
+  int32_t area = 0;                    // bytes of the chunk / selection area; the histogram lies behind it
+};
+
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
@@ -465,6 +483,220 @@ __global__ __launch_bounds__(256) void k_test_keys(int32_t nsel, const int32_t* 
   }
 }
 
+// ---- long lists: selection by threshold ------------------------------------------------------------
+// A candidate's place in the scorer's order is the 96-bit number (image : key), ascending: `image` is the
+// complement of the usual order-preserving integer image of a float, so that a higher score is a smaller
+// number, and the discovery key breaks ties as better() does.
+// The image is taken from the raw bits, which would tell -0.0 from +0.0 where better() does not.  A score is
+// never -0.0: its first addition is 0.0f + prod, which is +0.0 for prod == -0.0, and a sum of finite terms
+// rounds to -0.0 only when every term is -0.0.  Scores are finite, so no image is that of a NaN either.
+__device__ __forceinline__ uint32_t score_image(const float s) {
+  const uint32_t b = __float_as_uint(s);
+  return ~(b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u));
+}
+__device__ __forceinline__ float image_score(const uint32_t image) {
+  const uint32_t v = ~image;
+  return __uint_as_float((v >> 31) ? v ^ 0x80000000u : ~v);
+}
+// 11 bits of (image : key) from bit `shift` up (shift <= 85)
+__device__ __forceinline__ uint32_t long_digit(const uint4 r, const int shift) {
+  const unsigned long long key = ((unsigned long long)r.y << 32) | r.z;
+  unsigned long long v;
+  if (shift >= 64) v = r.x >> (shift - 64);
+  else if (shift == 0) v = key;
+  else v = (key >> shift) | ((unsigned long long)r.x << (64 - shift));
+  return (uint32_t)v & (kLongBins - 1);
+}
+__device__ __forceinline__ bool long_before(const uint4 a, const uint4 b) {
+  return a.x < b.x || (a.x == b.x && (a.y < b.y || (a.y == b.y && a.z < b.z)));
+}
+// bitonic sort of n = 2^k records in LDS, ascending, by the whole workgroup (ends on a barrier)
+template <int NW>
+__device__ __forceinline__ void long_sort(uint4* rec, const int n) {
+  const int tid = threadIdx.x;
+  for (int k = 2; k <= n; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (n >> 1); t += 64 * NW) {
+        const int lo = 2 * t - (t & (j - 1)), hi = lo + j;
+        const bool up = (lo & k) == 0;
+        const uint4 a = rec[lo], b = rec[hi];
+        if (long_before(b, a) == up) {
+          rec[lo] = b;
+          rec[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+}
+// control words of the selection, behind the histogram
+enum { kLcAppended = 0, kLcWinners, kLcContenders, kLcBin, kLcAbove, kLcInBin, kLcAnd, kLcOr = kLcAnd + 3, kLcWords = 16 };
+
+// The first `N` of the `ncand` records in `slab`, in order, to position q of the outputs.  On entry hist holds
+// the counts of the records' leading 11 bits and ctl[kLcWinners] is 0; every thread of the workgroup calls.
+// A pass finds the bin that holds the last missing place (wavefront 0, a prefix over the bins), then sweeps
+// the contenders once: records of earlier bins go to the winners in LDS, records of that bin are compacted to
+// the front of the slab -- in place: a sweep step reads 4 * 64 * NW records, and only behind a barrier writes
+// at most as many to places that were read already.  Few enough contenders are sorted in LDS; otherwise the
+// next pass takes the 11 bits from the highest bit in which the contenders still differ (known from the AND
+// and the OR of their records, gathered in the sweep): below bit 64 they share one score and only the key is
+// left to split them.  Nothing depends on the order of the slab.
+template <int NW>
+__device__ __forceinline__ void long_select(uint4* __restrict__ slab, char* area, uint32_t* hist, int* ctl, const int N,
+                            const int sort_cap, const int ncand, int32_t* __restrict__ out_ids,
+                            float* __restrict__ out_scores, int32_t* __restrict__ out_cnt, const int64_t q,
+                            unsigned long long* __restrict__ stats) {
+  constexpr int T = 64 * NW;
+  constexpr int kSweep = 4;  // records a thread reads per sweep step: the loads of a step are in flight together
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int winp2 = 1;
+  while (winp2 < N) winp2 <<= 1;
+  uint4* win = reinterpret_cast<uint4*>(area);
+  uint4* srt = win + winp2;
+  const uint4 last = make_uint4(~0u, ~0u, ~0u, ~0u);  // sorts behind every record
+  const unsigned long long below = (1ull << lane) - 1;
+  int nwin = 0, passes = 0, first_bin = 0, sorted = 0, key_pass = 0;
+  if (ncand <= N) {
+    for (int i = tid; i < ncand; i += T) win[i] = slab[i];
+    nwin = ncand;
+  } else {
+    int ncont = ncand, missing = N, shift = 85;
+    for (;;) {
+      if (wave == 0) {  // lane l: bins [32 l, 32 l + 32)
+        int s = 0;
+        for (int j = 0; j < kLongBins / 64; ++j) s += (int)hist[lane * (kLongBins / 64) + j];
+        int incl = s;
+        for (int off = 1; off < 64; off <<= 1) {
+          const int t = __shfl_up(incl, off);
+          if (lane >= off) incl += t;
+        }
+        int c = incl - s;
+        if (c < missing && missing <= incl)
+          for (int j = 0; j < kLongBins / 64; ++j) {
+            const int h = (int)hist[lane * (kLongBins / 64) + j];
+            if (c + h >= missing) {
+              ctl[kLcBin] = lane * (kLongBins / 64) + j;
+              ctl[kLcAbove] = c;
+              ctl[kLcInBin] = h;
+              break;
+            }
+            c += h;
+          }
+        if (lane == 0) {
+          ctl[kLcContenders] = 0;
+          for (int j = 0; j < 3; ++j) {
+            ctl[kLcAnd + j] = -1;
+            ctl[kLcOr + j] = 0;
+          }
+        }
+      }
+      __syncthreads();
+      const int bin = ctl[kLcBin], above = ctl[kLcAbove], in_bin = ctl[kLcInBin];
+      const bool take_bin = in_bin == missing - above;  // the bin ends exactly at the N-th: all of it wins
+      if (passes == 0) first_bin = in_bin;
+      uint32_t a0 = ~0u, a1 = ~0u, a2 = ~0u, o0 = 0, o1 = 0, o2 = 0;
+      for (int b0 = 0; b0 < ncont; b0 += kSweep * T) {
+        uint4 r[kSweep];
+        int cls[kSweep];  // 0 wins, 1 contends, 2 is out
+#pragma unroll
+        for (int j = 0; j < kSweep; ++j) {
+          const int i = b0 + j * T + tid;
+          r[j] = last;
+          if (i < ncont) r[j] = slab[i];
+        }
+#pragma unroll
+        for (int j = 0; j < kSweep; ++j) {
+          const int dg = (int)long_digit(r[j], shift);
+          cls[j] = b0 + j * T + tid >= ncont ? 2 : ((dg < bin || (take_bin && dg == bin)) ? 0 : (dg == bin ? 1 : 2));
+        }
+        __syncthreads();  // the records of this step are read: places before them may be written
+#pragma unroll
+        for (int j = 0; j < kSweep; ++j) {
+          const unsigned long long wm = __ballot(cls[j] == 0);
+          if (wm) {
+            int at = 0;
+            if (lane == 0) at = atomicAdd(&ctl[kLcWinners], __popcll(wm));
+            at = __builtin_amdgcn_readfirstlane(at) + __popcll(wm & below);
+            if (cls[j] == 0) win[at] = r[j];
+          }
+          const unsigned long long cm = __ballot(cls[j] == 1);
+          if (cm) {
+            int at = 0;
+            if (lane == 0) at = atomicAdd(&ctl[kLcContenders], __popcll(cm));
+            at = __builtin_amdgcn_readfirstlane(at) + __popcll(cm & below);
+            if (cls[j] == 1) {
+              slab[at] = r[j];
+              a0 &= r[j].x; a1 &= r[j].y; a2 &= r[j].z;
+              o0 |= r[j].x; o1 |= r[j].y; o2 |= r[j].z;
+            }
+          }
+        }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        a0 &= (uint32_t)__shfl_xor((int)a0, off); a1 &= (uint32_t)__shfl_xor((int)a1, off);
+        a2 &= (uint32_t)__shfl_xor((int)a2, off);
+        o0 |= (uint32_t)__shfl_xor((int)o0, off); o1 |= (uint32_t)__shfl_xor((int)o1, off);
+        o2 |= (uint32_t)__shfl_xor((int)o2, off);
+      }
+      if (lane == 0) {
+        atomicAnd(&ctl[kLcAnd], (int)a0); atomicAnd(&ctl[kLcAnd + 1], (int)a1); atomicAnd(&ctl[kLcAnd + 2], (int)a2);
+        atomicOr(&ctl[kLcOr], (int)o0); atomicOr(&ctl[kLcOr + 1], (int)o1); atomicOr(&ctl[kLcOr + 2], (int)o2);
+      }
+      __syncthreads();
+      nwin = ctl[kLcWinners];
+      ncont = ctl[kLcContenders];
+      missing = N - nwin;
+      if (missing <= 0 || ncont <= 0) break;
+      if (ncont <= sort_cap) {
+        int p2 = 1;
+        while (p2 < ncont) p2 <<= 1;
+        for (int i = tid; i < p2; i += T) {
+          uint4 v = last;
+          if (i < ncont) v = slab[i];
+          srt[i] = v;
+        }
+        __syncthreads();
+        long_sort<NW>(srt, p2);
+        for (int i = tid; i < missing; i += T) win[nwin + i] = srt[i];
+        nwin += missing;
+        sorted = 1;
+        break;
+      }
+      // the contenders differ (keys are distinct): the next 11 bits start at the highest differing bit
+      const uint32_t d0 = (uint32_t)(ctl[kLcAnd] ^ ctl[kLcOr]), d1 = (uint32_t)(ctl[kLcAnd + 1] ^ ctl[kLcOr + 1]),
+                     d2 = (uint32_t)(ctl[kLcAnd + 2] ^ ctl[kLcOr + 2]);
+      const int top = d0 ? 95 - __clz((int)d0) : (d1 ? 63 - __clz((int)d1) : 31 - __clz((int)(d2 | 1u)));
+      shift = top > 10 ? top - 10 : 0;
+      ++passes;
+      if (top < 64) key_pass = 1;
+      for (int z = tid; z < kLongBins; z += T) hist[z] = 0;
+      __syncthreads();
+      for (int i = tid; i < ncont; i += T) atomicAdd(&hist[long_digit(slab[i], shift)], 1u);
+      __syncthreads();
+    }
+  }
+  // the winners in order, then out
+  int p2 = 1;
+  while (p2 < nwin) p2 <<= 1;
+  __syncthreads();
+  for (int i = nwin + tid; i < p2; i += T) win[i] = last;
+  __syncthreads();
+  long_sort<NW>(win, p2);
+  for (int r = tid; r < nwin; r += T) {
+    const uint4 w = win[r];
+    out_ids[q * N + r] = (int32_t)w.w;
+    out_scores[q * N + r] = image_score(w.x);
+  }
+  if (tid == 0) {
+    out_cnt[q] = nwin;
+    atomicAdd(stats, (unsigned long long)ncand);
+    if (first_bin) atomicAdd(stats + 1, (unsigned long long)first_bin);
+    if (passes) atomicAdd(stats + 2, (unsigned long long)passes);
+    if (sorted) atomicAdd(stats + 3, 1ull);
+    if (key_pass) atomicAdd(stats + 4, 1ull);
+  }
+}
+
 // KeyT: discovery key (history index << pos_bits | position in the model row).  32 bits when
 // the longest history and the longest model row allow it (8 bytes of LDS per item: chunks of
 // 2304 ids), else 64.
@@ -481,7 +713,12 @@ __global__ __launch_bounds__(256) void k_test_keys(int32_t nsel, const int32_t* 
 // key; the candidate scan of a chunk adds to each count the chunk's slots that stand before the key (a ballot
 // and a popcount per 64 slots, gathered in registers -- lane j owns key j -- and added to LDS once per chunk);
 // after the chunks wavefront 0 writes rank = 1 + count.  Everything up to and including `update` is shared.
-template <int NW, typename KeyT, bool EVAL, bool RANK = false, class Args = TopN2Args>
+// LONG (Args = TopNLongArgs): lists of up to SLIMGPU_MAX_LIST.  No lists in registers and no merge: the
+// candidate scan of a chunk appends the chunk's candidates to the workgroup's slab (a ballot and a popcount
+// per 64 slots, one LDS atomic per wavefront step for the place) and counts the leading bits of their order in
+// a histogram that lies where the merge area would; long_select picks and orders the list after the chunks,
+// in the LDS of the chunks, which are free by then.
+template <int NW, typename KeyT, bool EVAL, bool RANK = false, class Args = TopN2Args, bool LONG = false>
 __device__ __forceinline__ void topn_chunk_body(const Args& T) {
   constexpr KeyT kUnt = ~KeyT(0), kExc = ~KeyT(0) - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -506,6 +743,16 @@ __device__ __forceinline__ void topn_chunk_body(const Args& T) {
     int u = __builtin_amdgcn_readfirstlane(s_user);
     if (u >= T.nusers) break;
     if (T.users) u = __builtin_amdgcn_readfirstlane(T.users[u]);
+    uint32_t* l_hist = nullptr;
+    int* l_ctl = nullptr;
+    if constexpr (LONG) {
+      if (!T.users) u += T.user0;
+      l_hist = reinterpret_cast<uint32_t*>(smem + T.area);
+      l_ctl = reinterpret_cast<int*>(l_hist + kLongBins);
+      for (int z = tid; z < kLongBins; z += 64 * NW) l_hist[z] = 0;
+      if (tid == 0) l_ctl[kLcAppended] = l_ctl[kLcWinners] = 0;
+      __syncthreads();
+    }
     const int64_t h0 = uni64(T.hptr[u]), h1 = uni64(T.hptr[u + 1]);
 
     // rank mode: the user's test keys of this pass into the merge area, counts zeroed
@@ -685,6 +932,30 @@ __device__ __forceinline__ void topn_chunk_body(const Args& T) {
           }
           if (lane < nj && my_cnt) atomicAdd(&r_c[jb + lane], my_cnt);
         }
+      } else if constexpr (LONG) {
+        // candidates of this chunk to the slab, their leading bits to the histogram
+        uint4* slab = T.slab + (size_t)blockIdx.x * (size_t)T.ncols;
+        for (int kb = 0; kb < width; kb += 64) {
+          const int k = kb + lane;
+          KeyT d = kUnt;
+          float sc = 0.0f;
+          if (k < width) {
+            d = disc[k];
+            sc = score[k];
+          }
+          const bool cand = d < kExc;
+          const unsigned long long mask = __ballot(cand);
+          if (mask == 0) continue;
+          int at = 0;
+          if (lane == 0) at = atomicAdd(&l_ctl[kLcAppended], __popcll(mask));
+          at = __builtin_amdgcn_readfirstlane(at) + __popcll(mask & ((1ull << lane) - 1));
+          if (cand) {  // (a user has at most ncols candidates: every slot of every chunk once)
+            const uint32_t image = score_image(sc);
+            const unsigned long long key = (unsigned long long)d;
+            slab[at] = make_uint4(image, (uint32_t)(key >> 32), (uint32_t)key, (uint32_t)(base + k));
+            atomicAdd(&l_hist[image >> 21], 1u);
+          }
+        }
       } else
       // candidates of this chunk against the wavefront's N best
       for (int kb = 0; kb < width; kb += 64) {
@@ -716,6 +987,14 @@ __device__ __forceinline__ void topn_chunk_body(const Args& T) {
           T.rank[rbase + z] = cand ? 1 + r_c[z] : 0;
           T.rscore[rbase + z] = cand ? r_s[z] : 0.0f;
         }
+      __syncthreads();
+      continue;
+    }
+    if constexpr (LONG) {
+      __syncthreads();  // every wavefront's candidates are in the slab and in the histogram
+      const int ncand = l_ctl[kLcAppended];
+      long_select<NW>(T.slab + (size_t)blockIdx.x * (size_t)T.ncols, smem, l_hist, l_ctl, N, T.sort_cap, ncand,
+                      T.out_ids, T.out_scores, T.out_cnt, (int64_t)__builtin_amdgcn_readfirstlane(s_user), T.stats);
       __syncthreads();
       continue;
     }
@@ -808,6 +1087,10 @@ __global__ __launch_bounds__(64 * NW) void topn_chunk_eval_kernel(const TopN2Arg
 template <int NW, typename KeyT>
 __global__ __launch_bounds__(64 * NW) void topn_chunk_rank_kernel(const TopNRankArgs T) {
   topn_chunk_body<NW, KeyT, false, true, TopNRankArgs>(T);
+}
+template <int NW, typename KeyT>
+__global__ __launch_bounds__(64 * NW) void topn_chunk_long_kernel(const TopNLongArgs T) {
+  topn_chunk_body<NW, KeyT, false, false, TopNLongArgs, true>(T);
 }
 
 // facts[0] = entries of the longest row, facts[1] = 1 when some row's ids are not strictly ascending
@@ -917,6 +1200,7 @@ struct HistoryView {
   const int32_t* ind = nullptr;
   const float* val = nullptr;
   int64_t max_hist = 0;
+  int32_t user0 = 0;                // long lists without a user list: position q is user user0 + q (a slice)
 };
 struct EvalTargets {  // the fused epilogue's inputs and output
   const int64_t* tptr;
@@ -944,19 +1228,45 @@ int wave_kernel_waves(int32_t nusers, int32_t nrcmds, int num_cus, size_t* lds_o
 }
 
 // which kernel serves: 1 the chunk kernel, 2 the wave kernel (lists of more than 64, a split table
-// beyond 2 GB, model rows not sorted, SLIM_TOPN_KERNEL=wave)
-int scorer_path(const DeviceRowView& W, int32_t nrcmds, const ChunkPlan& P) {
+// beyond 2 GB, model rows not sorted, SLIM_TOPN_KERNEL=wave).  With long_ok (a call that wants lists and may
+// have them of any length up to SLIMGPU_MAX_LIST): 4, the chunk kernel's long-list form, above 128 and at
+// any length under SLIM_TOPN_KERNEL=long -- where the chunk scorer can serve; 0 above 128 where it cannot.
+int scorer_path(const DeviceRowView& W, int32_t nrcmds, const ChunkPlan& P, bool long_ok = false) {
   const char* kenv = std::getenv("SLIM_TOPN_KERNEL");
-  const bool chunked = nrcmds <= kT2MaxN && W.nnz < (int64_t(1) << 31) && (W.rows_sorted || W.nnz == 0) &&
-                       !(kenv && std::strcmp(kenv, "wave") == 0) &&
-                       (size_t)std::max(W.nrows, 1) * ((size_t)P.nchunks + 1) * sizeof(uint32_t) <= kSplitLimit;
+  const bool chunk_ok = W.nnz < (int64_t(1) << 31) && (W.rows_sorted || W.nnz == 0) &&
+                        (size_t)std::max(W.nrows, 1) * ((size_t)P.nchunks + 1) * sizeof(uint32_t) <= kSplitLimit;
+  if (long_ok && chunk_ok && (nrcmds > 128 || (kenv && std::strcmp(kenv, "long") == 0))) return 4;
+  if (nrcmds > 128) return 0;
+  const bool chunked = nrcmds <= kT2MaxN && chunk_ok && !(kenv && std::strcmp(kenv, "wave") == 0);
   return chunked ? 1 : 2;
+}
+
+// LDS of the long-list form: the chunks, or the winners and the sort area that take their place after the
+// chunks, whichever is larger; then the histogram and the control words
+int long_sort_cap() {
+  int cap = kLongSortCap;
+  if (const char* e = std::getenv("SLIM_TOPN_LONG_SORT")) {
+    const int v = std::atoi(e);
+    if (v >= 1 && v <= kLongMaxN) cap = v;
+  }
+  return cap;
+}
+size_t long_area_bytes(const ChunkPlan& P, int32_t nrcmds, int sort_cap) {
+  auto p2 = [](size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; };
+  const size_t chunks = (size_t)P.t2w * P.cw * P.item_bytes;
+  const size_t select = (p2((size_t)nrcmds) + p2((size_t)sort_cap)) * sizeof(uint4);
+  return (std::max(chunks, select) + 15) / 16 * 16;
+}
+size_t long_lds_bytes(size_t area) { return area + kLongBins * sizeof(uint32_t) + kLcWords * sizeof(int); }
+int long_groups(size_t lds, int t2w, int32_t nusers, int num_cus) {
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / t2w, (160 * 1024) / (lds + 64)));
+  return std::max(1, std::min<int>(nusers, num_cus * per_cu));
 }
 
 void reserve_scorer(ScorerWorkspace& ws, int path, int32_t wrows, int32_t ncols, const ChunkPlan& P, int32_t nusers,
                     int32_t nrcmds, int num_cus, bool lists) {
   ws.need(ws.queue, 2);
-  if (path == 1) {
+  if (path == 1 || path == 4) {
     ws.need(ws.split, (size_t)std::max(wrows, 1) * ((size_t)P.nchunks + 1));
   } else {
     const int nwaves = wave_kernel_waves(nusers, nrcmds, num_cus, nullptr);
@@ -982,9 +1292,11 @@ struct ScorerLaunch {
 // users' terms into ev->terms when ev is given.
 // Rank mode (rk given; nrcmds, ev and lists are not used): the ranks and scores of the positions' test entries
 // into ws.rank / ws.rscore.  Only the chunk kernel has a rank form.
+// long_ok: lists of up to SLIMGPU_MAX_LIST may be asked for (scorer_path's 4; ws.lstats is the caller's to
+// provide and to clear, it adds up over the slices of one call); path 0 with set_error where nothing serves.
 ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, int num_cus,
                           hipStream_t stream, ScorerWorkspace& ws, const EvalTargets* ev, bool lists,
-                          const RankTargets* rk = nullptr) {
+                          const RankTargets* rk = nullptr, bool long_ok = false) {
   const int32_t ncols = std::max(W.ncols, 1);
   const ChunkPlan P = plan_chunks(ncols, W.max_row, H.max_hist, false);
   if (rk) {
@@ -992,10 +1304,17 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t 
     ev = nullptr;
     lists = false;
   }
-  const int path = scorer_path(W, nrcmds, P);
+  const int path = scorer_path(W, nrcmds, P, long_ok && lists && !ev && !rk);
   ScorerLaunch L;
   L.path = path;
   L.plan = P;
+  if (path == 0) {
+    set_error(!(W.rows_sorted || W.nnz == 0)
+                  ? "lists of more than 128 need the chunk scorer: the model's rows do not ascend by id (row order)"
+                  : "lists of more than 128 need the chunk scorer: fewer than 2^31 model entries, a split table of at "
+                    "most 2 GB");
+    return L;
+  }
   if (rk && path != 1) {
     set_error("ranks of the held-out items need the chunk scorer: model rows ascending by id, fewer than 2^31 model "
               "entries, a split table of at most 2 GB" +
@@ -1012,7 +1331,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t 
   }
   HIP_TRY(hipMemsetAsync(ws.queue.get(), 0, 2 * sizeof(int32_t), stream));
   if (lists || path == 2) HIP_TRY(hipMemsetAsync(ws.ocnt.get(), 0, sizeof(int32_t) * (size_t)H.nusers, stream));
-  if (path == 1) {
+  if (path == 1 || path == 4) {
     if (W.nrows > 0) {
       const int64_t total = (int64_t)W.nrows * (P.nchunks + 1);
       hipLaunchKernelGGL(k_row_split, dim3((unsigned)std::min<int64_t>((total + 255) / 256, num_cus * 16)), dim3(256),
@@ -1040,6 +1359,28 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, int32_t 
       T.cut = ev->cut;
     }
     const bool w16 = P.t2w == 16;
+    if (path == 4) {
+      TopNLongArgs A{};
+      static_cast<TopN2Args&>(A) = static_cast<const TopN2Args&>(T);
+      A.sort_cap = long_sort_cap();
+      A.area = (int32_t)long_area_bytes(P, nrcmds, A.sort_cap);
+      const size_t lds = long_lds_bytes((size_t)A.area);
+      const int nwg = long_groups(lds, P.t2w, H.nusers, num_cus);
+      L.groups = nwg;
+      A.slab = ws.need(ws.slab, (size_t)nwg * (size_t)ncols);
+      A.stats = ws.lstats.get();
+      A.user0 = H.user0;
+      auto lfn = P.key32 ? (w16 ? topn_chunk_long_kernel<16, uint32_t> : topn_chunk_long_kernel<8, uint32_t>)
+                         : (w16 ? topn_chunk_long_kernel<16, unsigned long long>
+                                : topn_chunk_long_kernel<8, unsigned long long>);
+      if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lfn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds));
+      L.launched = std::chrono::steady_clock::now();
+      hipLaunchKernelGGL(lfn, dim3(nwg), dim3(64 * P.t2w), lds, stream, A);
+      HIP_TRY(hipGetLastError());
+      return L;
+    }
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(32 / P.t2w, (160 * 1024) / (P.lds + 64)));
     const int nwg = std::max(1, std::min<int>(H.nusers, num_cus * per_cu));
     L.groups = nwg;
@@ -1142,7 +1483,74 @@ double ms_since(const std::chrono::steady_clock::time_point& t) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
+thread_local slimgpu_list_stats_t g_list_stats;
+
+// Users of one slice of a long-list call: the device lists of a slice (8 bytes per slot) stay under a quarter
+// of the HBM that is free when the call begins.  SLIM_TOPN_LONG_SLICE=<users> forces a length.
+int32_t long_slice_users(int32_t nusers, int32_t nrcmds) {
+  if (const char* e = std::getenv("SLIM_TOPN_LONG_SLICE")) {
+    const long v = std::atol(e);
+    if (v >= 1) return (int32_t)std::min<long>(v, std::max(nusers, 1));
+  }
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t per_user = (size_t)nrcmds * (sizeof(int32_t) + sizeof(float)) + sizeof(int32_t);
+  return (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)std::max(nusers, 1), free_b / 4 / per_user));
+}
+
+// The lists of every position of H through queue_scorer, brought down into output / scores / counts (counts
+// may be null).  Up to 128 this is one launch on the chunk or the wave kernel, as ever.  On the long-list
+// path the users go through in slices, each brought down before the next is queued, and the slab counters
+// of all slices are added into g_list_stats.  Returns the path (0: refused, set_error says why); *down gets
+// the bytes that came down.
+int score_lists(const DeviceRowView& W, const HistoryView& H, int32_t nrcmds, int num_cus, hipStream_t stream,
+                ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts, ScorerLaunch* launch,
+                size_t* down) {
+  slimgpu_list_stats_t ls = {};
+  const ChunkPlan P = plan_chunks(std::max(W.ncols, 1), W.max_row, H.max_hist, false);
+  const int path = scorer_path(W, nrcmds, P, /*long_ok=*/true);
+  size_t bytes = 0;
+  if (path != 4) {
+    const ScorerLaunch L = queue_scorer(W, H, nrcmds, num_cus, stream, ws, nullptr, /*lists=*/true, nullptr, true);
+    if (launch) *launch = L;
+    if (L.path == 0) return 0;
+    bytes = fetch_lists(ws, H.nusers, nrcmds, stream, output, scores, counts);
+    ls.path = L.path;
+    ls.slices = 1;
+  } else {
+    ws.need(ws.lstats, 8);
+    HIP_TRY(hipMemsetAsync(ws.lstats.get(), 0, 8 * sizeof(unsigned long long), stream));
+    const int32_t step = long_slice_users(H.nusers, nrcmds);
+    for (int32_t s0 = 0; s0 < H.nusers; s0 += step) {
+      HistoryView S = H;
+      S.nusers = std::min(step, H.nusers - s0);
+      if (H.users) S.users = H.users + s0; else S.user0 = H.user0 + s0;
+      const ScorerLaunch L = queue_scorer(W, S, nrcmds, num_cus, stream, ws, nullptr, /*lists=*/true, nullptr, true);
+      if (launch && s0 == 0) *launch = L;
+      if (L.path != 4) return 0;
+      bytes += fetch_lists(ws, S.nusers, nrcmds, stream, output + (int64_t)s0 * nrcmds, scores + (int64_t)s0 * nrcmds,
+                           counts ? counts + s0 : nullptr);
+      ++ls.slices;
+    }
+    unsigned long long h[5] = {};
+    HIP_TRY(hipMemcpyAsync(h, ws.lstats.get(), sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    bytes += sizeof(h);
+    ls.path = 4;
+    ls.candidates = (int64_t)h[0];
+    ls.contenders = (int64_t)h[1];
+    ls.refine_passes = (int64_t)h[2];
+    ls.lds_sorts = (int64_t)h[3];
+    ls.key_refines = (int64_t)h[4];
+  }
+  if (down) *down = bytes;
+  g_list_stats = ls;
+  return ls.path;
+}
+
 }  // namespace
+
+slimgpu_list_stats_t& last_list_stats() { return g_list_stats; }
 
 // Top-N lists of every history row.  output/scores are [nusers][nrcmds], slots beyond a
 // user's list length are left as the caller filled them; counts (optional) = list lengths.
@@ -1150,12 +1558,11 @@ double ms_since(const std::chrono::steady_clock::time_point& t) {
 // already holds it (nothing of W crosses PCIe).  The history is staged, the scorer queued on the null
 // stream through queue_scorer, the lists brought down.  Only here, SLIM_TOPN_KERNEL=chunk is an error
 // when the chunk kernel cannot serve (the resident entry points fall back to the wave kernel).
-int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
-                            int32_t* output, float* scores, int32_t* counts) {
-  if (!hist || !hist->rowptr || !W.d_ptr || nrcmds < 1 || nrcmds > 128) {
-    set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
-    return SLIM_ERROR_INPUT;
-  }
+namespace {
+
+// predict_device_view (long_ok false: lists of up to 128) and predict_lists_view (up to SLIMGPU_MAX_LIST)
+int32_t predict_view_impl(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds, int32_t* output,
+                          float* scores, int32_t* counts, bool long_ok) {
   const int32_t nusers = hist->nrows;
   const auto t_begin = std::chrono::steady_clock::now();
   try {
@@ -1179,6 +1586,13 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
       return SLIM_ERROR_INPUT;
     }
     ScorerWorkspace ws;
+    if (long_ok) {
+      if (score_lists(V, H, nrcmds, num_cus, /*stream=*/nullptr, ws, output, scores, counts, nullptr, nullptr) == 0) {
+        set_error("SLIMGPU_PredictLists: " + std::string(last_error()));
+        return SLIM_ERROR_INPUT;
+      }
+      return SLIM_OK;
+    }
     const ScorerLaunch L =
         queue_scorer(V, H, nrcmds, num_cus, /*stream=*/nullptr, ws, /*ev=*/nullptr, /*lists=*/true);
     HIP_TRY(hipDeviceSynchronize());
@@ -1190,11 +1604,35 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
     fetch_lists(ws, nusers, nrcmds, nullptr, output, scores, counts);
     return SLIM_OK;
   } catch (const HipFail& e) {
-    return hip_failure("SLIMGPU_Predict", e);
+    return hip_failure(long_ok ? "SLIMGPU_PredictLists" : "SLIMGPU_Predict", e);
   } catch (const std::bad_alloc&) {
-    set_error("SLIMGPU_Predict: out of host memory");
+    set_error(std::string(long_ok ? "SLIMGPU_PredictLists" : "SLIMGPU_Predict") + ": out of host memory");
     return SLIM_ERROR_MEMORY;
   }
+}
+
+int32_t predict_impl(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds, int32_t* output, float* scores,
+                     int32_t* counts, bool long_ok);
+
+}  // namespace
+
+int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
+                            int32_t* output, float* scores, int32_t* counts) {
+  if (!hist || !hist->rowptr || !W.d_ptr || nrcmds < 1 || nrcmds > 128) {
+    set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
+    return SLIM_ERROR_INPUT;
+  }
+  return predict_view_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/false);
+}
+
+int32_t predict_lists_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
+                           int32_t* output, float* scores, int32_t* counts) {
+  if (!hist || !hist->rowptr || !W.d_ptr || !output || !scores || nrcmds < 1 || nrcmds > SLIMGPU_MAX_LIST) {
+    set_error("SLIMGPU_PredictLists: bad arguments (a model, a history, output arrays, 1 <= nrcmds <= " +
+              std::to_string(SLIMGPU_MAX_LIST) + ")");
+    return SLIM_ERROR_INPUT;
+  }
+  return predict_view_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/true);
 }
 
 int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
@@ -1204,6 +1642,24 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
     set_error("SLIMGPU_Predict: bad arguments (1 <= nrcmds <= 128)");
     return SLIM_ERROR_INPUT;
   }
+  return predict_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/false);
+}
+
+int32_t predict_lists(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
+                      int32_t* output, float* scores, int32_t* counts) {
+  if (!W || !hist || !W->rowptr || !hist->rowptr || (!W->rowval && W->rowptr[W->nrows] > 0) || !output || !scores ||
+      nrcmds < 1 || nrcmds > SLIMGPU_MAX_LIST) {
+    set_error("SLIMGPU_PredictLists: bad arguments (a model, a history, output arrays, 1 <= nrcmds <= " +
+              std::to_string(SLIMGPU_MAX_LIST) + ")");
+    return SLIM_ERROR_INPUT;
+  }
+  return predict_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/true);
+}
+
+namespace {
+
+int32_t predict_impl(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds, int32_t* output, float* scores,
+                     int32_t* counts, bool long_ok) {
   try {
     (void)hipGetLastError();
     int ndev = 0;
@@ -1218,11 +1674,13 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
     v.d_ptr = w.ptr.get();
     v.d_ind = w.ind.get();
     v.d_val = w.val.get();
-    return predict_device_view(v, hist, nrcmds, output, scores, counts);
+    return predict_view_impl(v, hist, nrcmds, output, scores, counts, long_ok);
   } catch (const HipFail& e) {
-    return hip_failure("SLIMGPU_Predict", e);
+    return hip_failure(long_ok ? "SLIMGPU_PredictLists" : "SLIMGPU_Predict", e);
   }
 }
+
+}  // namespace
 
 // ---- a resident model against the resident matrix ----------------------------------------------
 //
@@ -1664,16 +2122,36 @@ int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model,
   }
 }
 
-int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
-                       float* scores) {
+namespace {
+
+// SLIMGPU_MatrixPredict (every row, lists of up to 128) and SLIMGPU_MatrixPredictLists (who names the caller)
+int32_t matrix_predict_impl(const char* who, int32_t max_n, int32_t nrcmds, const slimgpu_model* model,
+                            slimgpu_matrix_t* mat, int32_t nusers, const int32_t* users, int32_t* output,
+                            float* scores, int32_t* counts) {
   DeviceRowView W;
   DeviceCsrView R;
-  if (!model || !mat || !output || !scores || nrcmds < 1 || nrcmds > 128 || model_row_view(model, &W) != SLIM_OK ||
+  const bool long_ok = max_n > 128;
+  if (!model || !mat || !output || !scores || nrcmds < 1 || nrcmds > max_n || model_row_view(model, &W) != SLIM_OK ||
       matrix_csr_view(mat, &R) != SLIM_OK) {
-    set_error("SLIMGPU_MatrixPredict: bad arguments (a resident model, a staged matrix, 1 <= nrcmds <= 128)");
+    set_error(std::string(who) + ": bad arguments (a resident model, a staged matrix, 1 <= nrcmds <= " +
+              std::to_string(max_n) + ")");
     return SLIM_ERROR_INPUT;
   }
-  if (const int32_t rc = check_pair("SLIMGPU_MatrixPredict", R, W); rc != SLIM_OK) return rc;
+  if (users ? nusers < 1 : nusers != 0) {
+    set_error(std::string(who) + (users ? ": a user list needs at least one user" : ": nusers must be 0 without a user list"));
+    return SLIM_ERROR_INPUT;
+  }
+  for (int32_t q = 0; q < nusers; ++q) {
+    if (users[q] < 0 || users[q] >= R.nrows) {
+      set_error(std::string(who) + ": user " + std::to_string(users[q]) + " is outside [0, " + std::to_string(R.nrows) + ")");
+      return SLIM_ERROR_INPUT;
+    }
+    if (q > 0 && users[q] <= users[q - 1]) {
+      set_error(std::string(who) + ": the user ids must ascend strictly");
+      return SLIM_ERROR_INPUT;
+    }
+  }
+  if (const int32_t rc = check_pair(who, R, W); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1682,14 +2160,19 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
     (void)hipGetLastError();
     HIP_TRY(hipSetDevice(R.device));
     hipStream_t stream = static_cast<hipStream_t>(R.stream);
-    const int32_t nu = R.nrows;
+    const int32_t nu = users ? nusers : R.nrows;
     if (nu > 0) {
       ScorerWorkspace ws;
-      DeviceBuffer<int32_t> d_max(1);
+      DeviceBuffer<int32_t> d_max(1), d_users;
       ++ws.allocs;
+      if (users) {  // (pageable source: the copy has left the caller's array before the scorer is queued)
+        d_users = DeviceBuffer<int32_t>((size_t)nu);
+        ++ws.allocs;
+        HIP_TRY(hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)nu, hipMemcpyHostToDevice, stream));
+      }
       HIP_TRY(hipMemsetAsync(d_max.get(), 0, sizeof(int32_t), stream));
       hipLaunchKernelGGL(k_longest_row, dim3(std::max(1, std::min((nu + 255) / 256, R.num_cus * 8))), dim3(256), 0,
-                         stream, nu, static_cast<const int32_t*>(nullptr), R.d_ptr, d_max.get(),
+                         stream, nu, static_cast<const int32_t*>(d_users.get()), R.d_ptr, d_max.get(),
                          static_cast<unsigned long long*>(nullptr));
       HIP_TRY(hipGetLastError());
       int32_t h_max = 0;
@@ -1697,15 +2180,28 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
       HIP_TRY(hipStreamSynchronize(stream));
       HistoryView H;
       H.nusers = nu;
+      H.users = d_users.get();
       H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
       H.max_hist = h_max;
       HIP_TRY(hipEventCreate(&ev0));
       HIP_TRY(hipEventCreate(&ev1));
       HIP_TRY(hipEventRecord(ev0, stream));
+      if (long_ok) {  // (kernel_ms then spans the slices and their copies)
+        size_t down = 0;
+        st.path = score_lists(W, H, nrcmds, R.num_cus, stream, ws, output, scores, counts, nullptr, &down);
+        if (st.path == 0) {
+          set_error(std::string(who) + ": " + std::string(last_error()));
+          rc = SLIM_ERROR_INPUT;
+        }
+        HIP_TRY(hipEventRecord(ev1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        st.d2h_bytes = (int64_t)(down + sizeof(int32_t));
+      } else {
       st.path = queue_scorer(W, H, nrcmds, R.num_cus, stream, ws, nullptr, /*lists=*/true).path;
       HIP_TRY(hipEventRecord(ev1, stream));
       // only the lists come down (and the longest history's length before them)
       st.d2h_bytes = (int64_t)(fetch_lists(ws, nu, nrcmds, stream, output, scores, nullptr) + sizeof(int32_t));
+      }
       float ms = 0;
       HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
       st.kernel_ms = ms;
@@ -1713,16 +2209,32 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
       st.w_rows_read = R.nnz;
     }
     st.total_ms = ms_since(t_begin);
-    g_eval_stats = st;
+    if (rc == SLIM_OK) g_eval_stats = st;
+    if (rc == SLIM_OK && long_ok && nu <= 0) {
+      g_list_stats = slimgpu_list_stats_t{};
+    }
   } catch (const HipFail& e) {
-    rc = hip_failure("SLIMGPU_MatrixPredict", e);
+    rc = hip_failure(who, e);
   } catch (const std::bad_alloc&) {
-    set_error("SLIMGPU_MatrixPredict: out of host memory");
+    set_error(std::string(who) + ": out of host memory");
     rc = SLIM_ERROR_MEMORY;
   }
   if (ev0) (void)hipEventDestroy(ev0);
   if (ev1) (void)hipEventDestroy(ev1);
   return rc;
+}
+
+}  // namespace
+
+int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
+                       float* scores) {
+  return matrix_predict_impl("SLIMGPU_MatrixPredict", 128, nrcmds, model, mat, 0, nullptr, output, scores, nullptr);
+}
+
+int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t nusers,
+                             const int32_t* users, int32_t* output, float* scores, int32_t* counts) {
+  return matrix_predict_impl("SLIMGPU_MatrixPredictLists", SLIMGPU_MAX_LIST, nrcmds, model, mat, nusers, users, output,
+                             scores, counts);
 }
 
 }  // namespace slimamd

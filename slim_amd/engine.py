@@ -109,17 +109,26 @@ class ResidentModel(object):
             raise RuntimeError("SLIMGPU_ModelFetch failed (%d): %s" % (st.value, _lib.last_error()))
         return h if return_handle else model_to_scipy(self._lib, h)
 
-    def predict(self, device_matrix, nrcmds=10):
-        """SLIMGPU_MatrixPredict: top-N of every row of the staged matrix, scored in HBM (only the
-        lists come down).  Returns (ids, scores) of shape [nusers, nrcmds]; ids are -1 and scores 0
-        beyond a user's list."""
-        n = device_matrix.nrows
+    def predict(self, device_matrix, nrcmds=10, users=None, return_counts=False):
+        """SLIMGPU_MatrixPredictLists: top-N (1 <= nrcmds <= 4096) of every row of the staged matrix, or of
+        the rows in `users` (strictly ascending ids), scored in HBM (only the lists come down).  Returns
+        (ids, scores) of shape [rows, nrcmds], and the list lengths with return_counts; ids are -1 and
+        scores 0 beyond a user's list."""
+        nrcmds = int(nrcmds)
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = device_matrix.nrows if users is None else users.size
         ids = np.full(n * nrcmds, -1, np.int32)
         scores = np.zeros(n * nrcmds, np.float32)
-        st = self._lib.SLIMGPU_MatrixPredict(int(nrcmds), self.handle, device_matrix.handle, ids, scores)
+        counts = np.zeros(n, np.int32)
+        st = self._lib.SLIMGPU_MatrixPredictLists(
+            nrcmds, self.handle, device_matrix.handle, 0 if users is None else users.size,
+            None if users is None else users.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
+            scores.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p))
         if st != SLIM_OK:
-            raise RuntimeError("SLIMGPU_MatrixPredict failed (%d): %s" % (st, _lib.last_error()))
-        return ids.reshape(n, nrcmds), scores.reshape(n, nrcmds)
+            raise RuntimeError("SLIMGPU_MatrixPredictLists failed (%d): %s" % (st, _lib.last_error()))
+        out = (ids.reshape(n, nrcmds), scores.reshape(n, nrcmds))
+        return out + (counts,) if return_counts else out
 
     def free(self):
         if self.handle:
@@ -137,6 +146,13 @@ def eval_stats(lib=None):
     """Counters of the most recent ModelEvaluate / MatrixPredict on this thread, as a dict."""
     st = _lib.EvalStats()
     (lib or _lib.load()).SLIMGPU_LastEvalStats(C.byref(st))
+    return st.as_dict()
+
+
+def list_stats(lib=None):
+    """Counters of the most recent PredictLists / ModelPredictLists / MatrixPredictLists on this thread."""
+    st = _lib.ListStats()
+    (lib or _lib.load()).SLIMGPU_LastListStats(C.byref(st))
     return st.as_dict()
 
 
