@@ -4,8 +4,8 @@
 #
 # bash scripts/isa_metadata.sh topn [path/to/topn.hip]: the same figures of every instantiation of the top-N
 # scorers (topn_chunk_kernel / topn_chunk_eval_kernel / topn_chunk_rank_kernel / topn_chunk_long_kernel <NW, KeyT>; y = 32-bit keys,
-# j = 64-bit keys) -- of this tree's topn.hip, or of another revision's copied into slim_amd/csrc under
-# another name (it needs the tree's headers)
+# j = 64-bit keys) -- of this tree's topn.hip (which instantiates the kernels of topn_kernels.hpp), or of another
+# revision's copied into slim_amd/csrc under another name (it needs the tree's headers)
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 if [ "$1" = "topn" ]; then

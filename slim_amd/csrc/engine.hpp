@@ -154,7 +154,7 @@ struct DeviceCsrView {
 };
 int32_t matrix_csr_view(const slimgpu_matrix_t* m, DeviceCsrView* out);
 
-// topn.hip: a resident model scored and evaluated against the resident matrix (slim_gpu_eval.h:
+// resident_eval.hip: a resident model scored and evaluated against the resident matrix (slim_gpu_eval.h:
 // SLIMGPU_EvalSetCreateAt & co).  Per evaluation only the four sums and three counts of every list length
 // come down.  cutoffs[ncutoffs]: list lengths, ascending; users[nusers]: the evaluated users, ascending
 // (nullptr and 0: every user).  model_evaluate fills out[0 .. ncutoffs), which must be the eval set's count.

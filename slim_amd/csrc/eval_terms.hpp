@@ -1,4 +1,4 @@
-// eval_terms.hpp -- what eval.hip's HR / ARHR kernels share with the fused scorer of topn.hip: the
+// eval_terms.hpp -- what eval.hip's HR / ARHR kernels share with the fused scorer of topn_kernels.hpp: the
 // per-user record, the list of cutoffs and the two launches (per-user terms from lists in HBM, the sum
 // in position order).
 //

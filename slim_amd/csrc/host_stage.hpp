@@ -1,4 +1,4 @@
-// host_stage.hpp -- what the scorers' host code (topn.hip, eval.hip) shares: the rows of a host CSR staged
+// host_stage.hpp -- what the scorers' host code (topn.hip, resident_eval.hip, eval.hip) shares: the rows of a host CSR staged
 // in device memory, the report of a HIP failure, the CU count of the current device.
 #pragma once
 
@@ -42,6 +42,12 @@ inline StagedCsr stage_csr(const slim_csr_t* m, int32_t nrows, bool values, hipS
     put(s.val.get(), m->rowval, sizeof(float) * (size_t)s.nnz);
   }
   return s;
+}
+
+// a refusal of the caller's input: the message for last_error(), the status to return
+inline int32_t refuse(const std::string& why) {
+  set_error(why);
+  return SLIM_ERROR_INPUT;
 }
 
 inline int32_t hip_failure(const char* who, const HipFail& e) {

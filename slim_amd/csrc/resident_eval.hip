@@ -1,0 +1,478 @@
+// resident_eval.hip -- a resident model against the resident matrix (slim_gpu_eval.h, slim_gpu_rank.h,
+// slim_gpu_lists.h): the eval set, model_evaluate, model_ranks / model_evaluate_ranked, matrix_predict(_lists).
+// The evaluate half of a model-selection cell without the host: the history is the staged matrix's CSR
+// where it lies, the model is a resident model's row view, the test rows and the head / tail marker
+// were staged once (slimgpu_evalset).  One fused kernel scores, selects and forms every user's terms;
+// k_sum_in_user_order adds them; 8 + 32 bytes per cutoff come down.  The evaluated users are the matrix's
+// first rows or a sorted list of them (positions, eval_terms.hpp); several list lengths are served by the
+// one scoring pass of the longest.  Everything is queued through the scorer's one launch path (scorer.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "host_stage.hpp"
+#include "scorer.hpp"
+
+// What an evaluation needs besides the model (slim_gpu_eval.h: SLIMGPU_EvalSetCreate).  Owns its buffers;
+// borrows the matrix.
+struct slimgpu_evalset {
+  slimgpu_matrix_t* mat = nullptr;
+  int device = 0;
+  int32_t nsel = 0, fm_ncols = 0;  // positions evaluated: the listed users, or every user
+  bool listed = false;             // d_users holds the user of every position (else position q is user q)
+  slimamd::Cutoffs cut = {};       // list lengths; the lists scored have the last one's
+  int64_t hist_entries = 0;  // history entries of the evaluated users: the model rows one evaluation streams
+  int64_t max_hist = 0;      // the longest of those histories
+  slimamd::StagedCsr tst;  // the test rows of the matrix's users (ids only)
+  slimamd::DeviceBuffer<int32_t> d_fm, d_users;
+  slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;  // [cut.n][nsel]
+  slimamd::DeviceBuffer<unsigned long long> d_out;    // EvalOut
+  slimamd::ScorerWorkspace ws;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // ranks of the held-out items (slim_gpu_rank.h): the test entries of the evaluated users and the longest of
+  // their test rows; where a position's entries start (listed users only: else the staged row pointer serves);
+  // the terms of SLIMGPU_ModelEvaluateRanked, made on first use; the pre-pass's own events
+  int64_t entries = 0, max_test = 0;
+  slimamd::DeviceBuffer<int64_t> d_tbase;
+  slimamd::DeviceBuffer<slimamd::UserTerms> d_rterms;  // [SLIMGPU_MAX_CUTOFFS][nsel]: one slice of cutoffs
+  hipEvent_t evk0 = nullptr, evk1 = nullptr;
+  const int64_t* tbase() const { return d_tbase.get() ? d_tbase.get() : tst.ptr.get(); }
+  ~slimgpu_evalset() {
+    (void)hipSetDevice(device);
+    for (hipEvent_t e : {ev0, ev1, evk0, evk1})
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+namespace slimamd {
+namespace {
+thread_local slimgpu_eval_stats_t g_eval_stats;
+thread_local double g_rank_prepass_ms = 0;
+
+struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoffs bytes
+  unsigned long long streamed;  // entries of the model rows streamed
+  EvalSums sums[SLIMGPU_MAX_RANK_CUTOFFS];
+};
+
+// the matrix and the model of one call: one device, one width, rows that are the caller's
+int32_t check_pair(const char* who, const DeviceCsrView& R, const DeviceRowView& W) {
+  if (R.merged)
+    return refuse(std::string(who) + ": the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were "
+              "merged: its rows are not the caller's, score through the host handle");
+  if (W.device != R.device) return refuse(std::string(who) + ": the model and the matrix live on different devices");
+  if (W.nrows != R.ncols)
+    return refuse(std::string(who) + ": the model has " + std::to_string(W.nrows) + " items, the matrix " +
+              std::to_string(R.ncols));
+  return SLIM_OK;
+}
+
+// a list of users: at least one, without a list nusers is 0 (nrows < 0: no more); rows of [0, nrows), ascending
+int32_t check_user_list(const char* who, int32_t nusers, const int32_t* users, int32_t nrows) {
+  std::string what;
+  if (users ? nusers < 1 : nusers != 0)
+    what = users ? "a user list needs at least one user" : "nusers must be 0 without a user list";
+  for (int32_t q = 0; q < nusers && nrows >= 0 && what.empty(); ++q) {
+    if (users[q] < 0 || users[q] >= nrows)
+      what = "user " + std::to_string(users[q]) + " is outside [0, " + std::to_string(nrows) + ")";
+    else if (q > 0 && users[q] <= users[q - 1])
+      what = "the user ids must ascend strictly";
+  }
+  if (what.empty()) return SLIM_OK;
+  set_error(std::string(who) + ": " + what);
+  return SLIM_ERROR_INPUT;
+}
+
+HistoryView history_of(const DeviceCsrView& R, const slimgpu_evalset* es) {
+  return resident_history(R, es->nsel, es->listed ? es->d_users.get() : nullptr, es->max_hist);
+}
+
+// ranked: an eval set with no list length (SLIMGPU_EvalSetCreateRanked; ncutoffs == 0, cutoffs unused)
+slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                       int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
+                                       const int32_t* users, int32_t* status, bool ranked) {
+  auto fail = [&](int32_t st) {
+    if (status) *status = st;
+    return static_cast<slimgpu_evalset_t*>(nullptr);
+  };
+  auto refuse = [&](const std::string& what) {
+    set_error("SLIMGPU_EvalSetCreate: " + what);
+    return fail(SLIM_ERROR_INPUT);
+  };
+  DeviceCsrView R;
+  if (!mat || !tst || !tst->rowptr || !fmarker || fm_ncols < 0 || (!cutoffs && !ranked))
+    return refuse("bad arguments (a staged matrix, a test handle, a marker, the list lengths)");
+  if (!ranked && (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS))
+    return refuse("between 1 and " + std::to_string(SLIMGPU_MAX_CUTOFFS) + " list lengths, not " + std::to_string(ncutoffs));
+  Cutoffs cut = {};
+  cut.n = ncutoffs;
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    if (cutoffs[k] < 1 || cutoffs[k] > 128)
+      return refuse("bad arguments (1 <= nrcmds <= 128, not " + std::to_string(cutoffs[k]) + ")");
+    if (k > 0 && cutoffs[k] <= cutoffs[k - 1]) return refuse("the list lengths must ascend strictly");
+    cut.c[k] = cutoffs[k];
+  }
+  if (check_user_list("SLIMGPU_EvalSetCreate", nusers, users, -1) != SLIM_OK) return fail(SLIM_ERROR_INPUT);
+  if (matrix_csr_view(mat, &R) != SLIM_OK) return refuse("bad arguments (a staged matrix)");
+  if (R.merged)
+    return refuse("the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were "
+                  "merged: its rows are not the caller's, evaluate through the host handle");
+  const int32_t nall = std::min(R.nrows, tst->nrows);  // pyapi.c:309
+  if (check_user_list("SLIMGPU_EvalSetCreate", nusers, users, nall) != SLIM_OK) return fail(SLIM_ERROR_INPUT);
+  const int32_t nrcmds = ranked ? 1 : cut.c[cut.n - 1];
+  slimgpu_evalset* es = nullptr;
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    es = new slimgpu_evalset();
+    es->mat = mat; es->device = R.device; es->cut = cut; es->fm_ncols = fm_ncols;
+    es->listed = users != nullptr;
+    es->nsel = users ? nusers : nall;
+    const int32_t nsel = es->nsel;
+    es->tst = stage_csr(tst, nall, /*values=*/false, stream);
+    es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
+    es->d_terms = DeviceBuffer<UserTerms>((size_t)cut.n * (size_t)nsel);
+    es->d_out = DeviceBuffer<unsigned long long>(sizeof(EvalOut) / sizeof(unsigned long long));
+    if (fm_ncols > 0)
+      HIP_TRY(hipMemcpyAsync(es->d_fm.get(), fmarker, sizeof(int32_t) * (size_t)fm_ncols, hipMemcpyHostToDevice, stream));
+    if (users) {  // (pageable source: the copy has left the caller's array when the call returns)
+      es->d_users = DeviceBuffer<int32_t>((size_t)nsel);
+      HIP_TRY(hipMemcpyAsync(es->d_users.get(), users, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
+    }
+    // the test entries of the evaluated users, the longest of their test rows and, for listed users, where
+    // every position's entries start in the rank arrays (every user: the staged row pointer is that)
+    std::vector<int64_t> h_tbase;
+    if (users || tst->rowptr[0] != 0) {
+      h_tbase.resize((size_t)nsel + 1);
+      h_tbase[0] = 0;
+      for (int32_t q = 0; q < nsel; ++q) {
+        const int32_t u = users ? users[q] : q;
+        const int64_t len = tst->rowptr[u + 1] - tst->rowptr[u];
+        es->max_test = std::max(es->max_test, len);
+        h_tbase[(size_t)q + 1] = h_tbase[(size_t)q] + len;
+      }
+      es->entries = h_tbase[(size_t)nsel];
+      es->d_tbase = DeviceBuffer<int64_t>((size_t)nsel + 1);
+      HIP_TRY(hipMemcpyAsync(es->d_tbase.get(), h_tbase.data(), sizeof(int64_t) * ((size_t)nsel + 1),
+                             hipMemcpyHostToDevice, stream));  // (h_tbase outlives the synchronize below)
+    } else {
+      es->entries = es->tst.nnz;
+      es->max_test = es->tst.max_row;
+    }
+    // the longest history of the evaluated users and the number of their history entries, once (the
+    // scorer's key width needs the first)
+    HIP_TRY(hipMemsetAsync(es->d_out.get(), 0, sizeof(EvalOut), stream));
+    es->max_hist = longest_history(stream, R.num_cus, nsel, es->d_users.get(), R.d_ptr, &es->hist_entries);
+    // workspaces for the worst model: 64-bit keys, hence the smallest chunks and the largest split table
+    DeviceRowView worst;
+    worst.nrows = worst.ncols = R.ncols;
+    worst.rows_sorted = true;
+    reserve_scorer(es->ws, choose_scorer(worst, history_of(R, es), ListsRequest{nrcmds}, /*force_key64=*/true), R.ncols,
+                   std::max(R.ncols, 1), nsel, R.num_cus, /*lists=*/false);
+    for (hipEvent_t* e : {&es->ev0, &es->ev1, &es->evk0, &es->evk1}) HIP_TRY(hipEventCreate(e));
+    if (status) *status = SLIM_OK;
+    return es;
+  } catch (const HipFail& e) {
+    delete es;
+    return fail(hip_failure("SLIMGPU_EvalSetCreate", e));
+  } catch (const std::bad_alloc&) {
+    delete es;
+    set_error("SLIMGPU_EvalSetCreate: out of host memory");
+    return fail(SLIM_ERROR_MEMORY);
+  }
+}
+
+// The checks that every evaluation shares, in their order: the caller's own arguments (args_ok) and the handles,
+// the eval set's list lengths (ncutoffs given: the count the call asks for), one device, one width.
+int32_t check_evaluation(const char* who, bool args_ok, slimgpu_evalset_t* es, const slimgpu_model* model,
+                         const int32_t* ncutoffs, DeviceRowView& W, DeviceCsrView& R) {
+  if (!args_ok || !es || !model || model_row_view(model, &W) != SLIM_OK || matrix_csr_view(es->mat, &R) != SLIM_OK)
+    return refuse(std::string(who) + ": needs an eval set and a resident model with a row view");
+  if (ncutoffs && (*ncutoffs != es->cut.n || es->cut.n < 1))
+    return refuse(std::string(who) + ": the eval set holds " + std::to_string(es->cut.n) +
+              " list lengths, the call asks for " + std::to_string(*ncutoffs));
+  if (const int32_t rc = check_pair(who, R, W); rc != SLIM_OK) return rc;
+  if (es->device != R.device)
+    return refuse(std::string(who) + ": the eval set and the matrix live on different devices");
+  return SLIM_OK;
+}
+
+// What every call of an eval set leaves in last_eval_stats() once its stream has run, with the time of the
+// scorer and what followed it (ev0 .. ev1) and, for a ranked call, of the pre-pass.
+void close_stats(slimgpu_evalset_t* es, bool ranked, slimgpu_eval_stats_t& st,
+                 const std::chrono::steady_clock::time_point& t_begin) {
+  float ms = 0;
+  if (es->nsel > 0) {
+    HIP_TRY(hipEventElapsedTime(&ms, es->ev0, es->ev1));
+    st.kernel_ms = ms;
+    if (ranked && es->entries > 0) {
+      HIP_TRY(hipEventElapsedTime(&ms, es->evk0, es->evk1));
+      g_rank_prepass_ms = ms;
+    }
+  }
+  st.device_allocs = es->ws.allocs;
+  st.w_rows_read = es->hist_entries;
+  st.total_ms = ms_since(t_begin);
+  g_eval_stats = st;
+}
+
+// The end of an evaluation whose sums of `ncut` cutoffs are queued into the eval set's EvalOut (ev0 was recorded
+// before its scorer): ev1, the scorer's byte model, 8 + 32 * ncut bytes down, the sums as results, the stats.
+void finish_evaluation(slimgpu_evalset_t* es, const DeviceCsrView& R, const DeviceRowView& W, const HistoryView& H,
+                       int32_t ncut, EvalResult* out, bool ranked, slimgpu_eval_stats_t& st,
+                       const std::chrono::steady_clock::time_point& t_begin) {
+  EvalOut h = {};
+  if (es->nsel > 0) {
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
+    HIP_TRY(hipEventRecord(es->ev1, stream));
+    HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
+    if (es->hist_entries > 0 && W.nnz > 0) queue_streamed_entries(stream, R.num_cus, H, W, &d_out->streamed);
+    const size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncut;
+    HIP_TRY(hipMemcpyAsync(&h, d_out, down, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    st.d2h_bytes = (int64_t)down;
+  }
+  for (int32_t k = 0; k < ncut; ++k) {
+    const EvalSums& s = h.sums[k];
+    out[k].nvalid = s.n[0]; out[k].nvalid_head = s.n[1]; out[k].nvalid_tail = s.n[2];
+    out[k].hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0; out[k].arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
+    out[k].hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0; out[k].hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
+  }
+  st.w_bytes = 8.0 * (double)h.streamed;
+  close_stats(es, ranked, st, t_begin);
+}
+}  // namespace
+
+slimgpu_eval_stats_t& last_eval_stats() { return g_eval_stats; }
+double last_rank_prepass_ms() { return g_rank_prepass_ms; }
+
+slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                  int32_t fm_ncols, int32_t ncutoffs, const int32_t* cutoffs, int32_t nusers,
+                                  const int32_t* users, int32_t* status) {
+  return evalset_create_impl(mat, tst, fmarker, fm_ncols, ncutoffs, cutoffs, nusers, users, status, /*ranked=*/false);
+}
+
+slimgpu_evalset_t* evalset_create_ranked(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
+                                         int32_t fm_ncols, int32_t nusers, const int32_t* users, int32_t* status) {
+  return evalset_create_impl(mat, tst, fmarker, fm_ncols, 0, nullptr, nusers, users, status, /*ranked=*/true);
+}
+
+int64_t evalset_entries(const slimgpu_evalset_t* es) { return es ? es->entries : -1; }
+void evalset_free(slimgpu_evalset_t* es) { delete es; }
+int32_t evalset_cutoffs(const slimgpu_evalset_t* es) { return es ? es->cut.n : 0; }
+
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out) {
+  const char* who = "SLIMGPU_ModelEvaluate";
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (const int32_t rc = check_evaluation(who, out != nullptr, es, model, &ncutoffs, W, R); rc != SLIM_OK) return rc;
+  const int32_t ncut = es->cut.n;
+  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    es->ws.allocs = 0;
+    const HistoryView H = history_of(R, es);
+    if (es->nsel > 0) {
+      const ScorerRequest rq =
+          EvalTargets{es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get(), es->cut};
+      HIP_TRY(hipEventRecord(es->ev0, stream));
+      st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws).path;
+      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+    }
+    finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure(who, e);
+  }
+}
+
+// ---- the rank of every held-out item (slim_gpu_rank.h) ------------------------------------------
+namespace {
+// the checks both ranked calls share, then the scorer in rank mode on the matrix's stream: ranks and scores of
+// the eval set's test entries are in es->ws.rank / rscore when the stream has run.  SLIM_OK or a refusal.
+int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, DeviceRowView& W,
+                    DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st) {
+  if (const int32_t rc = check_evaluation(who, true, es, model, nullptr, W, R); rc != SLIM_OK) return rc;
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(R.device));
+  hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  es->ws.allocs = 0;
+  g_rank_prepass_ms = 0;
+  st.path = kRank;
+  if (es->nsel <= 0) return SLIM_OK;
+  H = history_of(R, es);
+  const ScorerRequest rq = RankTargets{es->tst.ptr.get(), es->tst.ind.get(), es->tbase(),
+                                       es->entries,       es->max_test,      es->evk0,    es->evk1};
+  HIP_TRY(hipEventRecord(es->ev0, stream));
+  if (queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws).path != kRank)
+    return refuse(std::string(who) + ": " + last_error());
+  return SLIM_OK;
+}
+}  // namespace
+
+int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    DeviceRowView W;
+    DeviceCsrView R;
+    HistoryView H;
+    if (const int32_t rc = queue_ranks("SLIMGPU_ModelRanks", es, model, W, R, H, st); rc != SLIM_OK) return rc;
+    if (es->nsel > 0) {
+      hipStream_t stream = static_cast<hipStream_t>(R.stream);
+      HIP_TRY(hipEventRecord(es->ev1, stream));
+      const size_t n = (size_t)es->entries;
+      if (ranks && n) {
+        HIP_TRY(hipMemcpyAsync(ranks, es->ws.rank.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+        st.d2h_bytes += (int64_t)(sizeof(int32_t) * n);
+      }
+      if (scores && n) {
+        HIP_TRY(hipMemcpyAsync(scores, es->ws.rscore.get(), sizeof(float) * n, hipMemcpyDeviceToHost, stream));
+        st.d2h_bytes += (int64_t)(sizeof(float) * n);
+      }
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    close_stats(es, /*ranked=*/true, st, t_begin);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_ModelRanks", e);
+  }
+}
+
+int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs,
+                              const int32_t* cutoffs, EvalResult* out) {
+  if (!cutoffs || !out || ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_RANK_CUTOFFS)
+    return refuse("SLIMGPU_ModelEvaluateRanked: between 1 and " + std::to_string(SLIMGPU_MAX_RANK_CUTOFFS) +
+              " cutoffs, not " + std::to_string(ncutoffs));
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    if (cutoffs[k] < 1)
+      return refuse("SLIMGPU_ModelEvaluateRanked: a cutoff must be at least 1, not " + std::to_string(cutoffs[k]));
+    if (k > 0 && cutoffs[k] <= cutoffs[k - 1])
+      return refuse("SLIMGPU_ModelEvaluateRanked: the cutoffs must ascend strictly");
+    out[k] = EvalResult();
+  }
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    DeviceRowView W;
+    DeviceCsrView R;
+    HistoryView H;
+    if (const int32_t rc = queue_ranks("SLIMGPU_ModelEvaluateRanked", es, model, W, R, H, st); rc != SLIM_OK) return rc;
+    if (es->nsel > 0) {
+      hipStream_t stream = static_cast<hipStream_t>(R.stream);
+      const size_t nterms = (size_t)SLIMGPU_MAX_CUTOFFS * (size_t)es->nsel;
+      if (es->d_rterms.bytes() < sizeof(UserTerms) * nterms) ++es->ws.allocs;
+      UserTerms* d_terms = es->d_rterms.reserve(nterms);
+      EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
+      // the terms workspace holds 8 records per position: the cutoffs in slices of SLIMGPU_MAX_CUTOFFS
+      for (int32_t k0 = 0; k0 < ncutoffs; k0 += SLIMGPU_MAX_CUTOFFS) {
+        Cutoffs cut = {};
+        cut.n = std::min<int32_t>(SLIMGPU_MAX_CUTOFFS, ncutoffs - k0);
+        for (int32_t k = 0; k < cut.n; ++k) cut.c[k] = cutoffs[k0 + k];
+        launch_rank_terms(stream, R.num_cus, es->nsel, H.users, cut, es->ws.rank.get(), es->tbase(), es->tst.ptr.get(),
+                          es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, d_terms);
+        launch_sum_in_user_order(stream, es->nsel, cut.n, d_terms, d_out->sums + k0);
+      }
+    }
+    finish_evaluation(es, R, W, H, ncutoffs, out, /*ranked=*/true, st, t_begin);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure("SLIMGPU_ModelEvaluateRanked", e);
+  }
+}
+
+namespace {
+// SLIMGPU_MatrixPredict (every row, lists of up to 128) and SLIMGPU_MatrixPredictLists (who names the caller)
+int32_t matrix_predict_impl(const char* who, int32_t max_n, int32_t nrcmds, const slimgpu_model* model,
+                            slimgpu_matrix_t* mat, int32_t nusers, const int32_t* users, int32_t* output,
+                            float* scores, int32_t* counts) {
+  DeviceRowView W;
+  DeviceCsrView R;
+  const bool long_ok = max_n > 128;
+  if (!model || !mat || !output || !scores || nrcmds < 1 || nrcmds > max_n || model_row_view(model, &W) != SLIM_OK ||
+      matrix_csr_view(mat, &R) != SLIM_OK)
+    return refuse(std::string(who) + ": bad arguments (a resident model, a staged matrix, 1 <= nrcmds <= " +
+              std::to_string(max_n) + ")");
+  if (const int32_t rc = check_user_list(who, nusers, users, R.nrows); rc != SLIM_OK) return rc;
+  if (const int32_t rc = check_pair(who, R, W); rc != SLIM_OK) return rc;
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int32_t rc = SLIM_OK;
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    const int32_t nu = users ? nusers : R.nrows;
+    if (nu > 0) {
+      ScorerWorkspace ws;
+      DeviceBuffer<int32_t> d_users;
+      ++ws.allocs;  // (the longest history's length)
+      if (users) {  // (pageable source: the copy has left the caller's array before the scorer is queued)
+        d_users = DeviceBuffer<int32_t>((size_t)nu);
+        ++ws.allocs;
+        HIP_TRY(hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)nu, hipMemcpyHostToDevice, stream));
+      }
+      const HistoryView H = resident_history(R, nu, d_users.get(),
+                                             longest_history(stream, R.num_cus, nu, d_users.get(), R.d_ptr, nullptr));
+      const ScorerRequest rq = long_ok ? ScorerRequest(LongListsRequest{nrcmds}) : ScorerRequest(ListsRequest{nrcmds});
+      const ScorerChoice C = choose_scorer(W, H, rq);
+      HIP_TRY(hipEventCreate(&ev0));
+      HIP_TRY(hipEventCreate(&ev1));
+      HIP_TRY(hipEventRecord(ev0, stream));
+      size_t down = 0;  // only the lists come down (and the longest history's length before them)
+      if (long_ok) {    // (kernel_ms then spans the slices and their copies)
+        st.path = score_lists(W, H, C, R.num_cus, stream, ws, output, scores, counts, &down);
+        if (st.path == kRefused) {
+          set_error(std::string(who) + ": " + std::string(last_error()));
+          rc = SLIM_ERROR_INPUT;
+        }
+        HIP_TRY(hipEventRecord(ev1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+      } else {
+        st.path = queue_scorer(W, H, C, rq, R.num_cus, stream, ws).path;
+        HIP_TRY(hipEventRecord(ev1, stream));
+        down = fetch_lists(ws, nu, nrcmds, stream, output, scores, nullptr);
+      }
+      st.d2h_bytes = (int64_t)(down + sizeof(int32_t));
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+      st.kernel_ms = ms;
+      st.device_allocs = ws.allocs;
+      st.w_rows_read = R.nnz;
+    }
+    st.total_ms = ms_since(t_begin);
+    if (rc == SLIM_OK) g_eval_stats = st;
+    if (rc == SLIM_OK && long_ok && nu <= 0) last_list_stats() = slimgpu_list_stats_t{};
+  } catch (const HipFail& e) {
+    rc = hip_failure(who, e);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    rc = SLIM_ERROR_MEMORY;
+  }
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  return rc;
+}
+}  // namespace
+
+int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
+                       float* scores) {
+  return matrix_predict_impl("SLIMGPU_MatrixPredict", 128, nrcmds, model, mat, 0, nullptr, output, scores, nullptr);
+}
+
+int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t nusers,
+                             const int32_t* users, int32_t* output, float* scores, int32_t* counts) {
+  return matrix_predict_impl("SLIMGPU_MatrixPredictLists", SLIMGPU_MAX_LIST, nrcmds, model, mat, nusers, users, output,
+                             scores, counts);
+}
+}  // namespace slimamd

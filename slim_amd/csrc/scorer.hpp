@@ -1,0 +1,129 @@
+// scorer.hpp -- the top-N scorer as its host code sees it (internal; topn.hip implements it).  A caller describes
+// the model (DeviceRowView) and the histories (HistoryView), says what it wants (ScorerRequest), lets
+// choose_scorer decide once per call and queues through queue_scorer.
+#pragma once
+
+#include <chrono>
+#include <string>
+#include <variant>
+
+#include "engine.hpp"
+#include "eval_terms.hpp"
+#include "hip_check.hpp"
+
+namespace slimamd {
+// Device buffers of the scorers, grow-only: a second run of the same shape allocates nothing.
+struct ScorerWorkspace {
+  DeviceBuffer<uint32_t> split;            // chunk kernel: where every chunk starts in every model row
+  DeviceBuffer<int32_t> queue, oid, ocnt;  // work queue; lists and their lengths (when they are wanted)
+  DeviceBuffer<float> osc, score;          // list scores; wave kernel: score vectors
+  DeviceBuffer<unsigned long long> disc;   // wave kernel: discovery vectors
+  // rank mode: (key, score) of every test entry from the pre-pass, (rank, score) out
+  DeviceBuffer<unsigned long long> tkey;
+  DeviceBuffer<float> tscore, rscore;
+  DeviceBuffer<int32_t> rank;
+  // long lists: one slab of ncols (image, key, id) records per workgroup; the counters of slimgpu_list_stats_t
+  DeviceBuffer<uint4> slab;
+  DeviceBuffer<unsigned long long> lstats;
+  int allocs = 0;                          // device allocations since the caller last cleared it
+  template <class T>
+  T* need(DeviceBuffer<T>& b, size_t n) {
+    if (b.bytes() < sizeof(T) * (n ? n : 1)) ++allocs;
+    return b.reserve(n);
+  }
+};
+
+struct HistoryView {
+  int32_t nusers = 0;               // positions
+  const int32_t* users = nullptr;   // the user of every position; nullptr: position q is user q
+  const int64_t* ptr = nullptr; const int32_t* ind = nullptr; const float* val = nullptr;
+  int64_t max_hist = 0;
+  int32_t user0 = 0;                // long lists without a user list: position q is user user0 + q (a slice)
+};
+// the rows of a staged matrix as histories: `nsel` positions, d_users their users (nullptr: the first rows)
+inline HistoryView resident_history(const DeviceCsrView& R, int32_t nsel, const int32_t* d_users, int64_t max_hist) {
+  HistoryView H;
+  H.nusers = nsel; H.users = d_users; H.max_hist = max_hist;
+  H.ptr = R.d_ptr; H.ind = R.d_ind; H.val = R.d_val;
+  return H;
+}
+
+// What a caller wants, one of four.  Lists of up to 128 into ws.oid / osc / ocnt; the same of up to
+// SLIMGPU_MAX_LIST (ws.lstats is the caller's to provide and to clear: it adds up over the slices of one call);
+struct ListsRequest { int32_t nrcmds; };
+struct LongListsRequest { int32_t nrcmds; };
+struct EvalTargets {  // the users' terms of lists of cut.c[cut.n - 1]: the fused epilogue's inputs and output
+  const int64_t* tptr; const int32_t* tind; const int32_t* fmarker;
+  int32_t fm_ncols;
+  UserTerms* terms;  // [cut.n][positions]
+  Cutoffs cut;
+};
+struct RankTargets {  // ranks and scores of the positions' test entries into ws.rank / ws.rscore
+  const int64_t* tptr; const int32_t* tind;
+  const int64_t* tbase;    // [positions + 1]: where a position's test entries start
+  int64_t entries;         // test entries of all positions
+  int64_t max_test;        // the longest test row among them
+  hipEvent_t pre0, pre1;   // around the pre-pass (k_test_keys)
+};
+using ScorerRequest = std::variant<ListsRequest, LongListsRequest, EvalTargets, RankTargets>;
+
+// Which kernel serves.  The values are those of slimgpu_eval_stats_t::path and slimgpu_list_stats_t::path.
+enum ScorerPath : int {
+  kRefused = 0,  // nothing on the device serves
+  kChunk = 1,    // the chunk kernel: lists of up to 64, with or without the fused evaluation
+  kWave = 2,     // the wave kernel (k_user_terms behind it for an evaluation)
+  kRank = 3,     // the chunk kernel in rank mode
+  kLong = 4,     // the chunk kernel's long-list form
+};
+struct ChunkPlan {  // geometry of the chunk kernel for a model / history pair: key width, chunk width, LDS
+  bool key32 = false;
+  int pos_bits = 32, item_bytes = 12, t2w = 8, cw = 64, nchunks = 1;
+  size_t lds = 0;
+};
+struct ScorerChoice {
+  ScorerPath path = kRefused;
+  ChunkPlan plan;
+  int32_t nrcmds = 1;      // the list length scored (1 for ranks)
+  std::string refusal;     // kRefused: why
+  bool chunk_pin_missed = false;  // SLIM_TOPN_KERNEL=chunk is set and the path is another
+};
+// Decides once per call; reads the SLIM_TOPN_* switches.  Of H only max_hist counts.  force_key64: the worst
+// case of a model not seen yet (the smallest chunks, hence the largest split table).
+ScorerChoice choose_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerRequest& rq,
+                           bool force_key64 = false);
+struct ScorerLaunch {  // how queue_scorer served a call
+  ScorerPath path = kRefused;  // the choice's; kRefused: set_error says why
+  int groups = 0;  // workgroups of the chunk kernel, wavefronts of the wave kernel
+  ChunkPlan plan;  // the chunk kernel's geometry
+  std::chrono::steady_clock::time_point launched;  // host time at which the scorer kernel itself was first queued
+};
+// Queues on `stream` what `rq` asks for, on the path of `choice` (choose_scorer's for this W, H and rq).
+ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice,
+                          const ScorerRequest& rq, int num_cus, hipStream_t stream, ScorerWorkspace& ws);
+// the buffers of a choice's path ahead of time (lists: ws.oid / osc / ocnt too)
+void reserve_scorer(ScorerWorkspace& ws, const ScorerChoice& choice, int32_t wrows, int32_t ncols, int32_t nusers,
+                    int num_cus, bool lists);
+// Brings the lists of a scorer queued on `stream` down and copies the counts[u] entries of every user's list; the
+// slots beyond a list stay as the caller filled them.  counts is optional.  Returns the bytes that came down.
+size_t fetch_lists(const ScorerWorkspace& ws, int32_t nusers, int32_t nrcmds, hipStream_t stream, int32_t* output,
+                   float* scores, int32_t* counts);
+// The lists of every position of H, of any length up to SLIMGPU_MAX_LIST (choice: choose_scorer's for a
+// LongListsRequest), brought down like fetch_lists does.  Up to 128 this is one launch.  On the long-list path the
+// users go through in slices, each brought down before the next is queued, and the slab counters of all slices are
+// added into last_list_stats().  Returns the path (kRefused: set_error says why); *down: the bytes that came down.
+ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice, int num_cus,
+                       hipStream_t stream, ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts,
+                       size_t* down);
+// The entries of the longest row among the rows at `nsel` positions of a CSR (d_users == nullptr: rows [0, nsel))
+// and, when `entries` is given, of all of them: one kernel on `stream`, 4 (16) bytes down, the stream drained.
+int64_t longest_history(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* d_users, const int64_t* d_ptr,
+                        int64_t* entries);
+// queued on `stream`: the entries of the model rows that the histories of H stream (the scorer's byte model)
+// into *d_out, which is preset to 0
+void queue_streamed_entries(hipStream_t stream, int num_cus, const HistoryView& H, const DeviceRowView& W,
+                            unsigned long long* d_out);
+
+inline double ms_since(const std::chrono::steady_clock::time_point& t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+}  // namespace slimamd

@@ -316,6 +316,24 @@ def test_steady_state_slices_and_refusals(cases):
         c.mat.model_from_scipy(W)
 
 
+def test_ranks_are_refused_where_the_chunk_scorer_cannot_serve(cases, monkeypatch):
+    """Only the chunk kernel has a rank form: with the wave kernel pinned both ranked calls are refused and say
+    why; without the pin the same eval set gives the reference ranks again.  (The pin is the only way to this
+    refusal: a resident model with rows that do not ascend is refused when it is made.)"""
+    c = cases("floats")
+    ev = c.mat.evaluator(c.T, fmarker=c.fm, ranked=True)
+    monkeypatch.setenv("SLIM_TOPN_KERNEL", "wave")
+    why = r": ranks of the held-out items need the chunk scorer: .*\(SLIM_TOPN_KERNEL is set\)"
+    with pytest.raises(RuntimeError, match="SLIMGPU_ModelRanks" + why):
+        ev.ranks(c.model)
+    with pytest.raises(RuntimeError, match="SLIMGPU_ModelEvaluateRanked" + why):
+        ev.evaluate_ranked(c.model, (10,))
+    monkeypatch.delenv("SLIM_TOPN_KERNEL")
+    ranks, _ = ev.ranks(c.model)
+    assert np.array_equal(ranks, c.rank) and ev.stats()["path"] == 3
+    ev.close()
+
+
 # ---- 4. an uploaded model is the learned model ---------------------------------------------------------------------------
 def test_uploaded_model_gives_the_learned_models_ranks(learned):
     R, T, mat, model = learned
