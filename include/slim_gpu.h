@@ -311,5 +311,7 @@ const char *SLIMGPU_LastError(void);
 /* The rank of every held-out item: evaluation of resident models at any list length. */
 #include "slim_gpu_rank.h"
 #include "slim_gpu_lists.h"
+/* Candidate filters for those lists: item allow / block sets, per-user exclusions. */
+#include "slim_gpu_filter.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

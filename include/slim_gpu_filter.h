@@ -1,0 +1,62 @@
+/*
+ * slim_gpu_filter.h -- engine extensions of libslim.so: candidate filters for the top-N lists of
+ * slim_gpu_lists.h.  Included by slim_gpu.h; plain C types only.
+ *
+ * A filter narrows what may be recommended: a set of items that may (or may not) be shown to anybody, and a
+ * list per user of items that may not be shown to that user.  With a filter, the candidates of a user are the
+ * items touched by the history, not in the history, allowed by the item set and not in the user's exclusion
+ * row.  Everything else is slim_gpu_lists.h: the total order (score descending, then discovery order), the
+ * float additions in history order, output / scores / counts, the slots beyond a list, the limits and refusals
+ * of the three paths, SLIMGPU_LastListStats.  The order is total and a candidate's score and discovery key do
+ * not depend on the other candidates, so the filtered list of length N is the first N survivors of the
+ * unfiltered full ranking, bit for bit; a filter that allows everything and excludes nothing gives the
+ * unfiltered call's output.
+ *
+ * The exclusion row of a position is that of its USER ID: users[q] on the matrix call, the row of trn on the
+ * calls that take host histories -- never the position in the call or in a slice of the long-list form.
+ *
+ * The object validates once and holds its host description (one bit per item, the exclusion CSR).  The device
+ * copy is made on the first call that scores on a device and kept until SLIMGPU_FilterFree: a second call of
+ * the same shape allocates nothing for it.  A filter is not tied to a model, only to a number of items; a call
+ * whose model has another ncols is SLIM_ERROR_INPUT and writes nothing.  filter == NULL in a call: no filter.
+ *
+ * Not built: evaluation and ranks under a filter (SLIMGPU_EvalSet*, SLIMGPU_ModelRanks take none);
+ * recommending history items; skipping the history walk of chunks in which nothing is allowed.
+ */
+#ifndef SLIM_AMD_SLIM_GPU_FILTER_H_
+#define SLIM_AMD_SLIM_GPU_FILTER_H_
+
+#include "slim_gpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct slimgpu_filter slimgpu_filter_t;
+/* items: nitems ids in any order, repeats allowed.  blocked == 0: only these may be recommended
+   (items == NULL: every item may);  blocked != 0: these may not.
+   xptr/xind: per-user exclusions as a CSR over user ids, xusers rows (xptr == NULL: none).
+   A user id >= xusers has no exclusions.  ids outside [0, ncols), a non-monotone xptr or
+   xptr[0] != 0 are SLIM_ERROR_INPUT with a SLIMGPU_LastError text. */
+int32_t SLIMGPU_FilterCreate(int32_t ncols, int32_t nitems, const int32_t *items, int32_t blocked,
+                             int32_t xusers, const int64_t *xptr, const int32_t *xind,
+                             slimgpu_filter_t **out);
+void SLIMGPU_FilterFree(slimgpu_filter_t *f);
+/* SLIMGPU_PredictLists / SLIMGPU_ModelPredictLists / SLIMGPU_MatrixPredictLists under a filter */
+int32_t SLIMGPU_PredictListsFiltered(int32_t nrcmds, slim_t *model, slim_t *trn, slimgpu_filter_t *filter,
+                                     int32_t *output, float *scores, int32_t *counts);
+int32_t SLIMGPU_ModelPredictListsFiltered(int32_t nrcmds, const slimgpu_model_t *model, slim_t *trn,
+                                          slimgpu_filter_t *filter, int32_t *output, float *scores,
+                                          int32_t *counts);
+int32_t SLIMGPU_MatrixPredictListsFiltered(int32_t nrcmds, const slimgpu_model_t *model, slimgpu_matrix_t *mat,
+                                           int32_t nusers, const int32_t *users, slimgpu_filter_t *filter,
+                                           int32_t *output, float *scores, int32_t *counts);
+/* Py_SLIM_Predict under a filter: the same SLIM_PREDICT=gpu|cpu|auto policy (the device scorer at
+   1 <= nrcmds <= SLIMGPU_MAX_LIST, the host scorer otherwise and, under auto, on a device refusal) */
+int32_t Py_SLIM_PredictFiltered(int32_t nrcmds, slim_t *slimhandle, slim_t *trnhandle,
+                                slimgpu_filter_t *filter, int32_t *output, float *scores);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SLIM_AMD_SLIM_GPU_FILTER_H_ */

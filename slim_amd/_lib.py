@@ -202,6 +202,22 @@ _LIST_SIGNATURES = {
 LIST_SYMBOLS = tuple(_LIST_SIGNATURES)
 MAX_LIST = 4096         # SLIMGPU_MAX_LIST
 
+# candidate filters for those lists (include/slim_gpu_filter.h): item allow / block sets, per-user exclusions
+_FILTER_SIGNATURES = {
+    "SLIMGPU_FilterCreate": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.POINTER(C.c_void_p)]),
+    "SLIMGPU_FilterFree": (None, [C.c_void_p]),
+    "SLIMGPU_PredictListsFiltered": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+    "SLIMGPU_ModelPredictListsFiltered": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]),
+    "SLIMGPU_MatrixPredictListsFiltered": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "Py_SLIM_PredictFiltered": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, i32_1d, f32_1d]),
+}
+
+FILTER_SYMBOLS = tuple(_FILTER_SIGNATURES)
+
 _lib = None
 
 
@@ -217,7 +233,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
                               list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
-                              list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items())):
+                              list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
+                              list(_FILTER_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

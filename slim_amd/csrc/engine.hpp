@@ -135,10 +135,20 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
                             int32_t* output, float* scores, int32_t* counts);
 // slim_gpu_lists.h: lists of up to SLIMGPU_MAX_LIST (up to 128 on the paths of the calls above, beyond on the
 // chunk kernel's long-list form); SLIM_ERROR_INPUT with the outputs untouched where nothing on the device serves
+// filter (slim_gpu_filter.h; nullptr: none) narrows the candidates; one made for another ncols is refused
 int32_t predict_lists(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
-                      int32_t* output, float* scores, int32_t* counts);
+                      int32_t* output, float* scores, int32_t* counts, slimgpu_filter* filter = nullptr);
 int32_t predict_lists_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
-                           int32_t* output, float* scores, int32_t* counts);
+                           int32_t* output, float* scores, int32_t* counts, slimgpu_filter* filter = nullptr);
+// filter.hip: the filter object -- validated once, its host description (host_csr.hpp: HostFilter) and the
+// device copy that filter_on_device (scorer.hpp) makes on first use
+struct HostFilter;
+slimgpu_filter* filter_create(int32_t ncols, int32_t nitems, const int32_t* items, int32_t blocked, int32_t xusers,
+                              const int64_t* xptr, const int32_t* xind, int32_t* status);
+void filter_free(slimgpu_filter* f);
+HostFilter filter_host(const slimgpu_filter* f);
+// SLIM_OK, or SLIM_ERROR_INPUT with "<who>: ..." as the error text when f was made for another number of items
+int32_t filter_check(const char* who, const slimgpu_filter* f, int32_t model_ncols);
 slimgpu_list_stats_t& last_list_stats();
 int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out);
 // the CSR of a staged matrix where it lies (the history of the resident scorer)
@@ -177,7 +187,8 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
                        float* scores);
 // users[nusers]: the rows scored, ascending (nullptr and 0: every row); counts may be null
 int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t nusers,
-                             const int32_t* users, int32_t* output, float* scores, int32_t* counts);
+                             const int32_t* users, int32_t* output, float* scores, int32_t* counts,
+                             slimgpu_filter* filter = nullptr);
 slimgpu_eval_stats_t& last_eval_stats();
 // facts of a row view, for the scorers: d_facts[0] = entries of its longest row, d_facts[1] = 1 when the
 // ids of some row do not ascend strictly (both preset to 0 by the caller).  Queues one kernel on

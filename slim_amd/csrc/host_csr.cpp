@@ -210,6 +210,55 @@ int32_t top_n(const slim_csr_t* W, int32_t nratings, const int32_t* itemids,
   return n;
 }
 
+// top_n is the yardstick the filtered scorers are tested against and stays as it is: this is its loop with the
+// filter's marks.  The exclusion row is marked like the history (-2) before the walk; an id the bitmap does not
+// allow is marked -2 when the walk first meets it (a user touches far fewer than ncols ids) and remembered, so
+// that the marker leaves as it came: all -1.
+int32_t top_n_filtered(const slim_csr_t* W, int32_t nratings, const int32_t* itemids,
+                       const float* ratings, int32_t nrcmds, int32_t* rids, float* rscores,
+                       TopNScratch& ws, const HostFilter& F, int32_t user) {
+  const int32_t ncols = W->ncols, nrows = W->nrows;
+  auto in_cols = [&](int32_t i) { return i >= 0 && i < ncols; };
+  const int64_t x0 = F.xptr && user >= 0 && user < F.xusers ? F.xptr[user] : 0;
+  const int64_t x1 = F.xptr && user >= 0 && user < F.xusers ? F.xptr[user + 1] : 0;
+  for (int32_t r = 0; r < nratings; ++r)
+    if (in_cols(itemids[r])) ws.marker[itemids[r]] = -2;  // history: never recommended
+  for (int64_t x = x0; x < x1; ++x)
+    if (in_cols(F.xind[x])) ws.marker[F.xind[x]] = -2;    // nor the user's exclusions
+
+  int32_t ncand = 0;
+  std::vector<int32_t> barred;  // ids the bitmap turned away
+  for (int32_t r = 0; r < nratings; ++r) {
+    const int32_t i = itemids[r];
+    if (i < 0 || i >= nrows) continue;
+    const float rating = ratings ? ratings[r] : 1.0f;
+    for (ssize_t j = W->rowptr[i]; j < W->rowptr[i + 1]; ++j) {
+      const int32_t k = W->rowind[j];
+      int32_t& slot = ws.marker[k];
+      if (slot == -2) continue;
+      if (slot == -1) {
+        if (F.bits && !((F.bits[k >> 5] >> (k & 31)) & 1u)) {
+          slot = -2;
+          barred.push_back(k);
+          continue;
+        }
+        ws.val[ncand] = k;
+        ws.key[ncand] = 0.0f;
+        slot = ncand++;
+      }
+      ws.key[slot] += rating * W->rowval[j];
+    }
+  }
+  const int32_t n = emit_best(ncand, nrcmds, ws.key, ws.val, rids, rscores);
+  for (int32_t c = 0; c < ncand; ++c) ws.marker[ws.val[c]] = -1;
+  for (const int32_t k : barred) ws.marker[k] = -1;
+  for (int64_t x = x0; x < x1; ++x)
+    if (in_cols(F.xind[x])) ws.marker[F.xind[x]] = -1;
+  for (int32_t r = 0; r < nratings; ++r)
+    if (in_cols(itemids[r])) ws.marker[itemids[r]] = -1;
+  return n;
+}
+
 int32_t top_n_1vsk(const slim_csr_t* W, int32_t nratings, const int32_t* itemids,
                    const float* ratings, int32_t nrcmds, int32_t* rids,
                    float* rscores, int32_t nnegs, const int32_t* negitems) {

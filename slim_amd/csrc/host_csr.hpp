@@ -56,6 +56,19 @@ struct TopNScratch {
 int32_t top_n(const slim_csr_t* W, int32_t nratings, const int32_t* itemids,
               const float* ratings, int32_t nrcmds, int32_t* rids, float* rscores,
               TopNScratch& ws);
+// A candidate filter (slim_gpu_filter.h) as the host scorer reads it.  bits: one bit per item, set = may be
+// recommended (nullptr: every item may); xptr / xind: exclusion rows over user ids (nullptr: none).
+struct HostFilter {
+  int32_t ncols = 0, xusers = 0;
+  const uint32_t* bits = nullptr;
+  const int64_t* xptr = nullptr;
+  const int32_t* xind = nullptr;
+};
+// top_n for user `user` under a filter: the candidates are those of top_n that F allows and the user's
+// exclusion row does not name; their scores and their order among themselves are top_n's.
+int32_t top_n_filtered(const slim_csr_t* W, int32_t nratings, const int32_t* itemids,
+                       const float* ratings, int32_t nrcmds, int32_t* rids, float* rscores,
+                       TopNScratch& ws, const HostFilter& F, int32_t user);
 // predict.c:77-133: rank a fixed negative-candidate list.
 int32_t top_n_1vsk(const slim_csr_t* W, int32_t nratings, const int32_t* itemids,
                    const float* ratings, int32_t nrcmds, int32_t* rids,

@@ -167,6 +167,18 @@ inline Csr read_matrix(const std::string& path, Fmt fmt) {
   return m;
 }
 
+// item ids, one per line (blank lines are skipped)
+inline std::vector<int32_t> read_ids(const std::string& path) {
+  FILE* f = std::fopen(path.c_str(), "r");
+  if (!f) die("Failed to open " + path);
+  std::vector<int32_t> ids;
+  long id;
+  while (std::fscanf(f, "%ld", &id) == 1) ids.push_back((int32_t)id);
+  if (!std::feof(f)) die("bad item id in " + path);
+  std::fclose(f);
+  return ids;
+}
+
 // row view of a model handle, in the same format as the input (slim_learn.c:83)
 inline void write_matrix(const slim_csr_t* m, const std::string& path, Fmt fmt) {
   FILE* f = std::fopen(path.c_str(), "w");

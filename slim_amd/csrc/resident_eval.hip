@@ -394,7 +394,7 @@ namespace {
 // SLIMGPU_MatrixPredict (every row, lists of up to 128) and SLIMGPU_MatrixPredictLists (who names the caller)
 int32_t matrix_predict_impl(const char* who, int32_t max_n, int32_t nrcmds, const slimgpu_model* model,
                             slimgpu_matrix_t* mat, int32_t nusers, const int32_t* users, int32_t* output,
-                            float* scores, int32_t* counts) {
+                            float* scores, int32_t* counts, slimgpu_filter* filter = nullptr) {
   DeviceRowView W;
   DeviceCsrView R;
   const bool long_ok = max_n > 128;
@@ -404,6 +404,7 @@ int32_t matrix_predict_impl(const char* who, int32_t max_n, int32_t nrcmds, cons
               std::to_string(max_n) + ")");
   if (const int32_t rc = check_user_list(who, nusers, users, R.nrows); rc != SLIM_OK) return rc;
   if (const int32_t rc = check_pair(who, R, W); rc != SLIM_OK) return rc;
+  if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -426,12 +427,13 @@ int32_t matrix_predict_impl(const char* who, int32_t max_n, int32_t nrcmds, cons
                                              longest_history(stream, R.num_cus, nu, d_users.get(), R.d_ptr, nullptr));
       const ScorerRequest rq = long_ok ? ScorerRequest(LongListsRequest{nrcmds}) : ScorerRequest(ListsRequest{nrcmds});
       const ScorerChoice C = choose_scorer(W, H, rq);
+      const CandidateFilter F = filter_on_device(filter, R.device, stream, &ws.allocs);
       HIP_TRY(hipEventCreate(&ev0));
       HIP_TRY(hipEventCreate(&ev1));
       HIP_TRY(hipEventRecord(ev0, stream));
       size_t down = 0;  // only the lists come down (and the longest history's length before them)
       if (long_ok) {    // (kernel_ms then spans the slices and their copies)
-        st.path = score_lists(W, H, C, R.num_cus, stream, ws, output, scores, counts, &down);
+        st.path = score_lists(W, H, C, R.num_cus, stream, ws, output, scores, counts, &down, F);
         if (st.path == kRefused) {
           set_error(std::string(who) + ": " + std::string(last_error()));
           rc = SLIM_ERROR_INPUT;
@@ -471,8 +473,9 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
 }
 
 int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t nusers,
-                             const int32_t* users, int32_t* output, float* scores, int32_t* counts) {
+                             const int32_t* users, int32_t* output, float* scores, int32_t* counts,
+                             slimgpu_filter* filter) {
   return matrix_predict_impl("SLIMGPU_MatrixPredictLists", SLIMGPU_MAX_LIST, nrcmds, model, mat, nusers, users, output,
-                             scores, counts);
+                             scores, counts, filter);
 }
 }  // namespace slimamd

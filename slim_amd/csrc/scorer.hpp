@@ -48,6 +48,18 @@ inline HistoryView resident_history(const DeviceCsrView& R, int32_t nsel, const 
   return H;
 }
 
+// A candidate filter (slim_gpu_filter.h) where the scorer runs; inert when its pointers are null.  bits: one bit
+// per item, set = may be recommended; xptr / xind: the exclusion rows, a CSR over user ids with xusers rows.
+struct CandidateFilter {
+  const uint32_t* bits = nullptr;
+  const int64_t* xptr = nullptr; const int32_t* xind = nullptr;
+  int32_t xusers = 0;
+};
+// The device copy of `f` (nullptr: no filter) on the current device, `device`: uploaded on `stream` on the
+// first use there (the stream is drained once, so that later calls may use another) and kept until the
+// filter is freed.  *allocs grows by the device allocations this made.
+CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stream, int* allocs);
+
 // What a caller wants, one of four.  Lists of up to 128 into ws.oid / osc / ocnt; the same of up to
 // SLIMGPU_MAX_LIST (ws.lstats is the caller's to provide and to clear: it adds up over the slices of one call);
 struct ListsRequest { int32_t nrcmds; };
@@ -98,8 +110,10 @@ struct ScorerLaunch {  // how queue_scorer served a call
   std::chrono::steady_clock::time_point launched;  // host time at which the scorer kernel itself was first queued
 };
 // Queues on `stream` what `rq` asks for, on the path of `choice` (choose_scorer's for this W, H and rq).
+// F narrows the candidates of the lists (the evaluation and the rank mode take none).
 ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice,
-                          const ScorerRequest& rq, int num_cus, hipStream_t stream, ScorerWorkspace& ws);
+                          const ScorerRequest& rq, int num_cus, hipStream_t stream, ScorerWorkspace& ws,
+                          const CandidateFilter& F = {});
 // the buffers of a choice's path ahead of time (lists: ws.oid / osc / ocnt too)
 void reserve_scorer(ScorerWorkspace& ws, const ScorerChoice& choice, int32_t wrows, int32_t ncols, int32_t nusers,
                     int num_cus, bool lists);
@@ -113,7 +127,7 @@ size_t fetch_lists(const ScorerWorkspace& ws, int32_t nusers, int32_t nrcmds, hi
 // added into last_list_stats().  Returns the path (kRefused: set_error says why); *down: the bytes that came down.
 ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice, int num_cus,
                        hipStream_t stream, ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts,
-                       size_t* down);
+                       size_t* down, const CandidateFilter& F = {});
 // The entries of the longest row among the rows at `nsel` positions of a CSR (d_users == nullptr: rows [0, nsel))
 // and, when `entries` is given, of all of them: one kernel on `stream`, 4 (16) bytes down, the stream drained.
 int64_t longest_history(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* d_users, const int64_t* d_ptr,

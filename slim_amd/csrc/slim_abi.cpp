@@ -736,6 +736,77 @@ int32_t SLIMGPU_MatrixPredictLists(int32_t nrcmds, const slimgpu_model_t* model,
   return matrix_predict_lists(nrcmds, model, mat, nusers, users, output, scores, counts);
 }
 
+// --------------------------------------------------- slim_gpu_filter.h ------
+
+int32_t SLIMGPU_FilterCreate(int32_t ncols, int32_t nitems, const int32_t* items, int32_t blocked, int32_t xusers,
+                             const int64_t* xptr, const int32_t* xind, slimgpu_filter_t** out) {
+  set_error("");
+  if (!out) {
+    set_error("SLIMGPU_FilterCreate: bad arguments (out is NULL)");
+    return SLIM_ERROR_INPUT;
+  }
+  int32_t status = SLIM_ERROR;
+  *out = filter_create(ncols, nitems, items, blocked, xusers, xptr, xind, &status);
+  return status;
+}
+
+void SLIMGPU_FilterFree(slimgpu_filter_t* f) { filter_free(f); }
+
+int32_t SLIMGPU_PredictListsFiltered(int32_t nrcmds, slim_t* model, slim_t* trn, slimgpu_filter_t* filter,
+                                     int32_t* output, float* scores, int32_t* counts) {
+  set_error("");
+  return predict_lists(as_csr(model), as_csr(trn), nrcmds, output, scores, counts, filter);
+}
+
+int32_t SLIMGPU_ModelPredictListsFiltered(int32_t nrcmds, const slimgpu_model_t* model, slim_t* trn,
+                                          slimgpu_filter_t* filter, int32_t* output, float* scores, int32_t* counts) {
+  set_error("");
+  DeviceRowView v;
+  if (!model || nrcmds < 1 || nrcmds > SLIMGPU_MAX_LIST || model_row_view(model, &v) != SLIM_OK) {
+    set_error("SLIMGPU_ModelPredictListsFiltered: bad arguments (a resident model with a row view, 1 <= nrcmds <= " +
+              std::to_string(SLIMGPU_MAX_LIST) + ")");
+    return SLIM_ERROR_INPUT;
+  }
+  return predict_lists_view(v, as_csr(trn), nrcmds, output, scores, counts, filter);
+}
+
+int32_t SLIMGPU_MatrixPredictListsFiltered(int32_t nrcmds, const slimgpu_model_t* model, slimgpu_matrix_t* mat,
+                                           int32_t nusers, const int32_t* users, slimgpu_filter_t* filter,
+                                           int32_t* output, float* scores, int32_t* counts) {
+  set_error("");
+  return matrix_predict_lists(nrcmds, model, mat, nusers, users, output, scores, counts, filter);
+}
+
+// Py_SLIM_Predict under a filter: the same policy, the device scorer at every length it serves
+int32_t Py_SLIM_PredictFiltered(int32_t nrcmds, slim_t* slimhandle, slim_t* trnhandle, slimgpu_filter_t* filter,
+                                int32_t* output, float* scores) {
+  const slim_csr_t* W = as_csr(slimhandle);
+  const slim_csr_t* trn = as_csr(trnhandle);
+  if (!W || !trn || !W->rowptr || !trn->rowptr || nrcmds < 0) return SLIM_ERROR;
+  set_error("");
+  if (const int32_t rc = filter_check("Py_SLIM_PredictFiltered", filter, W->ncols); rc != SLIM_OK) return rc;
+  const int policy = predict_policy();
+  if (policy == 2 || (policy == 1 && nrcmds >= 1 && nrcmds <= SLIMGPU_MAX_LIST && trn->nrows > 0 &&
+                      device_count() > 0)) {
+    const int32_t rc = predict_lists(W, trn, nrcmds, output, scores, nullptr, filter);
+    if (rc == SLIM_OK || policy == 2) return rc;
+  }
+  const HostFilter F = filter_host(filter);
+  TopNScratch ws(W->ncols > W->nrows ? W->ncols : W->nrows);
+  std::vector<int32_t> rids(nrcmds);
+  std::vector<float> rsc(nrcmds);
+  for (int32_t u = 0; u < trn->nrows; ++u) {
+    const ssize_t lo = trn->rowptr[u], hi = trn->rowptr[u + 1];
+    const int32_t n = top_n_filtered(W, (int32_t)(hi - lo), trn->rowind + lo, trn->rowval ? trn->rowval + lo : nullptr,
+                                     nrcmds, rids.data(), rsc.data(), ws, F, u);
+    for (int32_t r = 0; r < n; ++r) {
+      output[(ssize_t)u * nrcmds + r] = rids[r];
+      scores[(ssize_t)u * nrcmds + r] = rsc[r];
+    }
+  }
+  return trn->nrows > 0 ? SLIM_OK : SLIM_ERROR;
+}
+
 int32_t SLIMGPU_LastListStats(slimgpu_list_stats_t* out) {
   if (!out) return SLIM_ERROR_INPUT;
   *out = last_list_stats();

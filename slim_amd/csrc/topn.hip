@@ -208,6 +208,10 @@ void fill_common(ChunkArgs& T, const DeviceRowView& W, const HistoryView& H, con
   T.cw = C.plan.cw; T.nchunks = C.plan.nchunks; T.pos_bits = C.plan.pos_bits; T.wsplit = ws.split.get();
   T.wlast = W.nnz > 0 ? (uint32_t)(W.nnz - 1) : 0u;
 }
+// the filter of a lists call into the wave kernel's or a chunk kernel's arguments
+void fill_filter(FilterArgs& A, const CandidateFilter& F) {
+  A.bits = F.bits; A.xptr = F.xptr; A.xind = F.xind; A.xusers = F.xusers;
+}
 void fill_lists(TopN2Args& T, const ScorerWorkspace& ws) {
   T.out_ids = ws.oid.get(); T.out_scores = ws.osc.get(); T.out_cnt = ws.ocnt.get();
 }
@@ -229,7 +233,7 @@ void reserve_scorer(ScorerWorkspace& ws, const ScorerChoice& C, int32_t wrows, i
 }
 
 ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& C, const ScorerRequest& rq,
-                          int num_cus, hipStream_t stream, ScorerWorkspace& ws) {
+                          int num_cus, hipStream_t stream, ScorerWorkspace& ws, const CandidateFilter& F) {
   ScorerLaunch L;
   L.path = C.path;
   L.plan = C.plan;
@@ -263,6 +267,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
         TopN2Args A{};
         fill_common(A, W, H, C, ws);
         fill_lists(A, ws);
+        fill_filter(A.flt, F);
         launch_scorer(pick_kernel<TopN2Args>(P), L, 64 * P.t2w, P.lds, stream, A);
       }
       break;
@@ -270,6 +275,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
       TopNLongArgs A{};
       fill_common(A, W, H, C, ws);
       fill_lists(A, ws);
+      fill_filter(A.flt, F);
       A.sort_cap = long_sort_cap();
       A.area = (int32_t)long_area_bytes(P, nrcmds, A.sort_cap);
       const size_t lds = long_lds_bytes((size_t)A.area);
@@ -317,6 +323,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
       fill_views(T, W, H, C, ws);
       T.score = ws.score.get(); T.disc = ws.disc.get();
       T.out_ids = ws.oid.get(); T.out_scores = ws.osc.get(); T.out_cnt = ws.ocnt.get();
+      if (lists) fill_filter(T.flt, F);
       launch_scorer(&topn_kernel, L, 64, lds, stream, T);
       if (ev)
         launch_user_terms(stream, num_cus, H.nusers, H.users, nrcmds, ev->cut, ws.oid.get(), ws.ocnt.get(), ev->tptr,
@@ -366,13 +373,13 @@ slimgpu_list_stats_t& last_list_stats() { return g_list_stats; }
 
 ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& C, int num_cus,
                        hipStream_t stream, ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts,
-                       size_t* down) {
+                       size_t* down, const CandidateFilter& F) {
   slimgpu_list_stats_t ls = {};
   const int32_t nrcmds = C.nrcmds;
   const ScorerRequest rq = LongListsRequest{nrcmds};
   size_t bytes = 0;
   if (C.path != kLong) {
-    const ScorerLaunch L = queue_scorer(W, H, C, rq, num_cus, stream, ws);
+    const ScorerLaunch L = queue_scorer(W, H, C, rq, num_cus, stream, ws, F);
     if (L.path == kRefused) return kRefused;
     bytes = fetch_lists(ws, H.nusers, nrcmds, stream, output, scores, counts);
     ls.slices = 1;
@@ -384,7 +391,7 @@ ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const Score
       HistoryView S = H;
       S.nusers = std::min(step, H.nusers - s0);
       if (H.users) S.users = H.users + s0; else S.user0 = H.user0 + s0;
-      queue_scorer(W, S, C, rq, num_cus, stream, ws);
+      queue_scorer(W, S, C, rq, num_cus, stream, ws, F);  // (the exclusion rows go by user id: S names the users)
       bytes += fetch_lists(ws, S.nusers, nrcmds, stream, output + (int64_t)s0 * nrcmds, scores + (int64_t)s0 * nrcmds,
                            counts ? counts + s0 : nullptr);
       ++ls.slices;
@@ -425,8 +432,9 @@ bool host_model_ok(const slim_csr_t* W) { return W && W->rowptr && (W->rowval ||
 
 // predict_device_view (long_ok false) and predict_lists_view
 int32_t predict_view_impl(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds, int32_t* output,
-                          float* scores, int32_t* counts, bool long_ok) {
+                          float* scores, int32_t* counts, bool long_ok, slimgpu_filter* filter = nullptr) {
   const int32_t nusers = hist->nrows;
+  if (const int32_t rc = filter_check("SLIMGPU_PredictLists", filter, W.ncols); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   try {
     (void)hipGetLastError();  // a failure of an earlier call must not be reported by this one
@@ -447,7 +455,10 @@ int32_t predict_view_impl(const DeviceRowView& W, const slim_csr_t* hist, int32_
       return refuse("SLIMGPU_Predict: SLIM_TOPN_KERNEL=chunk needs nrcmds <= 64 and model rows sorted by id");
     ScorerWorkspace ws;
     if (long_ok) {
-      if (score_lists(V, H, C, num_cus, /*stream=*/nullptr, ws, output, scores, counts, nullptr) == kRefused)
+      int device = 0;
+      HIP_TRY(hipGetDevice(&device));
+      const CandidateFilter F = filter_on_device(filter, device, /*stream=*/nullptr, &ws.allocs);
+      if (score_lists(V, H, C, num_cus, /*stream=*/nullptr, ws, output, scores, counts, nullptr, F) == kRefused)
         return refuse("SLIMGPU_PredictLists: " + std::string(last_error()));
       return SLIM_OK;
     }
@@ -470,7 +481,8 @@ int32_t predict_view_impl(const DeviceRowView& W, const slim_csr_t* hist, int32_
 
 // predict_device (long_ok false) and predict_lists: the model staged, then as above
 int32_t predict_impl(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds, int32_t* output, float* scores,
-                     int32_t* counts, bool long_ok) {
+                     int32_t* counts, bool long_ok, slimgpu_filter* filter = nullptr) {
+  if (const int32_t rc = filter_check("SLIMGPU_PredictLists", filter, W->ncols); rc != SLIM_OK) return rc;
   try {
     (void)hipGetLastError();
     int ndev = 0;
@@ -480,7 +492,7 @@ int32_t predict_impl(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds
     DeviceRowView v;
     v.nrows = W->nrows; v.ncols = W->ncols; v.nnz = w.nnz; v.max_row = w.max_row;
     v.d_ptr = w.ptr.get(); v.d_ind = w.ind.get(); v.d_val = w.val.get();
-    return predict_view_impl(v, hist, nrcmds, output, scores, counts, long_ok);
+    return predict_view_impl(v, hist, nrcmds, output, scores, counts, long_ok, filter);
   } catch (const HipFail& e) {
     return hip_failure(predict_name(long_ok), e);
   }
@@ -493,9 +505,9 @@ int32_t predict_device_view(const DeviceRowView& W, const slim_csr_t* hist, int3
   return rc != SLIM_OK ? rc : predict_view_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/false);
 }
 int32_t predict_lists_view(const DeviceRowView& W, const slim_csr_t* hist, int32_t nrcmds,
-                           int32_t* output, float* scores, int32_t* counts) {
+                           int32_t* output, float* scores, int32_t* counts, slimgpu_filter* filter) {
   const int32_t rc = check_predict_args(true, W.d_ptr != nullptr, hist, nrcmds, output, scores);
-  return rc != SLIM_OK ? rc : predict_view_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/true);
+  return rc != SLIM_OK ? rc : predict_view_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/true, filter);
 }
 int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
                        int32_t* output, float* scores, int32_t* counts) {
@@ -503,8 +515,8 @@ int32_t predict_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcm
   return rc != SLIM_OK ? rc : predict_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/false);
 }
 int32_t predict_lists(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
-                      int32_t* output, float* scores, int32_t* counts) {
+                      int32_t* output, float* scores, int32_t* counts, slimgpu_filter* filter) {
   const int32_t rc = check_predict_args(true, host_model_ok(W), hist, nrcmds, output, scores);
-  return rc != SLIM_OK ? rc : predict_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/true);
+  return rc != SLIM_OK ? rc : predict_impl(W, hist, nrcmds, output, scores, counts, /*long_ok=*/true, filter);
 }
 }  // namespace slimamd

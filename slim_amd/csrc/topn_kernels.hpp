@@ -34,9 +34,22 @@ namespace {
 constexpr unsigned long long kUntouched = ~0ull;
 constexpr unsigned long long kExcluded = ~0ull - 1ull;
 
+// A candidate filter (slim_gpu_filter.h) as the kernels read it; inert when its pointers are null.  bits: one bit per
+// item, set = may be recommended (nullptr: every item may).  xptr / xind: the exclusion rows, a CSR over USER ids
+// with xusers rows (nullptr: none; a user >= xusers has none).
+struct FilterArgs {
+  const uint32_t* bits = nullptr;
+  const int64_t* xptr = nullptr; const int32_t* xind = nullptr;
+  int32_t xusers = 0;
+};
+__device__ __forceinline__ bool filter_allows(const uint32_t* __restrict__ bits, const int id) {
+  return (bits[id >> 5] >> (id & 31)) & 1u;
+}
+
 struct TopNArgs {
   int32_t nusers, nitems_rows, ncols, nrcmds;  // nusers: positions
   const int32_t* users = nullptr;  // the user of every position; nullptr: position q is user q
+  FilterArgs flt;
   const int64_t* wptr; const int32_t* wind; const float* wval;
   const int64_t* hptr; const int32_t* hind;
   const float* hval;  // nullptr: implicit ratings of 1
@@ -57,6 +70,11 @@ __device__ __forceinline__ int64_t uni64(int64_t v) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
+// the exclusion row of user u (wave-uniform): [x0, x1) in xind, empty without a filter
+__device__ __forceinline__ void exclusion_row(const FilterArgs& F, const int u, int64_t& x0, int64_t& x1) {
+  x0 = x1 = 0;
+  if (F.xptr != nullptr && u < F.xusers) x0 = uni64(F.xptr[u]), x1 = uni64(F.xptr[u + 1]);
+}
 
 // Control flow is wave-uniform wherever the data allows it: positions are strided statically
 // over the wavefronts (outputs are indexed by the position, history by its user), loop bounds over history rows and output ranks are scalars, and the
@@ -76,12 +94,22 @@ __global__ __launch_bounds__(64) void topn_kernel(const TopNArgs T) {
   for (int q = (int)blockIdx.x; q < T.nusers; q += (int)gridDim.x) {
     const int u = T.users ? __builtin_amdgcn_readfirstlane(T.users[q]) : q;
     const int64_t h0 = uni64(T.hptr[u]), h1 = uni64(T.hptr[u + 1]);
+    int64_t x0, x1;
+    exclusion_row(T.flt, u, x0, x1);
 
-    for (int k = lane; k < T.ncols; k += 64) disc[k] = kUntouched;
+    // an item the filter does not allow is excluded before anything touches it
+    if (T.flt.bits == nullptr)
+      for (int k = lane; k < T.ncols; k += 64) disc[k] = kUntouched;
+    else
+      for (int k = lane; k < T.ncols; k += 64) disc[k] = filter_allows(T.flt.bits, k) ? kUntouched : kExcluded;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    // history items are never recommended (predict.c:35-38)
+    // history items are never recommended (predict.c:35-38), nor is the user's exclusion row
     for (int64_t h = h0 + lane; h < h1; h += 64) {
       const int i = T.hind[h];
+      if (i >= 0 && i < T.ncols) disc[i] = kExcluded;
+    }
+    for (int64_t x = x0 + lane; x < x1; x += 64) {
+      const int i = T.flt.xind[x];
       if (i >= 0 && i < T.ncols) disc[i] = kExcluded;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -208,6 +236,7 @@ struct ChunkArgs {
   const uint32_t* wsplit;  // [nitems_rows][nchunks + 1]: offset in row i of the first id >= c * cw
   const int64_t* hptr; const int32_t* hind; const float* hval;
   int32_t* queue;
+  FilterArgs flt;  // (the evaluation and the rank mode pass none)
 };
 struct TopN2Args : ChunkArgs {  // lists of up to 64 (topn_chunk_kernel)
   int32_t* out_ids = nullptr; float* out_scores = nullptr; int32_t* out_cnt = nullptr;
@@ -628,14 +657,32 @@ __device__ __forceinline__ int draw_user(const Args& T, int& pos, const int tid)
   return u;
 }
 
+// Candidacy is decided here and nowhere else: a slot that leaves as kExc is no candidate whatever the history
+// walk adds to it, and nothing behind the walk looks at such a slot.  Without a filter the history's items are
+// excluded; with one (FilterArgs) so are the ids its bitmap does not allow -- the 64 lanes of a step read the two
+// words of their 64 ids, any `base`, and the short last chunk never reads past word (ncols - 1) / 32 -- and the
+// ids of the exclusion row of user `u` (the body's, after Mode::begin has settled which user the position is),
+// under the history's range guard.  The row's bounds are two scalar loads per chunk: held across the walk they
+// would take four scalar registers it has not got.  The branches are on kernel arguments: wave-uniform.
 template <class Args, class Lds>
 __device__ __forceinline__ void prepare_chunk(const Args& T, const Lds& L, const int base, const int width,
-                                              const int64_t h0, const int64_t h1) {
-  for (int k = L.lane; k < width; k += 64) L.disc[k] = Lds::kUnt;
+                                              const int64_t h0, const int64_t h1, const int u) {
+  if (T.flt.bits == nullptr)
+    for (int k = L.lane; k < width; k += 64) L.disc[k] = Lds::kUnt;
+  else
+    for (int k = L.lane; k < width; k += 64) L.disc[k] = filter_allows(T.flt.bits, base + k) ? Lds::kUnt : Lds::kExc;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   for (int64_t h = h0 + L.lane; h < h1; h += 64) {  // history items are never recommended
     const int i = T.hind[h];
     if (i >= base && i < base + width) L.disc[i - base] = Lds::kExc;
+  }
+  if (T.flt.xptr != nullptr) {  // nor are the user's exclusions
+    int64_t x0, x1;
+    exclusion_row(T.flt, u, x0, x1);
+    for (int64_t x = x0 + L.lane; x < x1; x += 64) {
+      const int i = T.flt.xind[x];
+      if (i >= base && i < base + width) L.disc[i - base] = Lds::kExc;
+    }
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 }
@@ -1024,7 +1071,7 @@ __device__ __forceinline__ void topn_chunk_body(const typename Mode::Args& T) {
       for (int c = L.wave; c < T.nchunks; c += NW) {
         const int base = c * T.cw;
         const int width = (T.ncols - base) < T.cw ? (T.ncols - base) : T.cw;
-        prepare_chunk(T, L, base, width, h0, h1);
+        prepare_chunk(T, L, base, width, h0, h1, u);
         walk_history<KeyT>(T, L, c, base, h0, h1);
         M.chunk(T, L, base, width);
       }

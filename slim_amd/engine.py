@@ -109,11 +109,12 @@ class ResidentModel(object):
             raise RuntimeError("SLIMGPU_ModelFetch failed (%d): %s" % (st.value, _lib.last_error()))
         return h if return_handle else model_to_scipy(self._lib, h)
 
-    def predict(self, device_matrix, nrcmds=10, users=None, return_counts=False):
+    def predict(self, device_matrix, nrcmds=10, users=None, return_counts=False, filter=None):
         """SLIMGPU_MatrixPredictLists: top-N (1 <= nrcmds <= 4096) of every row of the staged matrix, or of
         the rows in `users` (strictly ascending ids), scored in HBM (only the lists come down).  Returns
         (ids, scores) of shape [rows, nrcmds], and the list lengths with return_counts; ids are -1 and
-        scores 0 beyond a user's list."""
+        scores 0 beyond a user's list.  filter: an ItemFilter (DeviceMatrix.item_filter) that narrows the
+        candidates (SLIMGPU_MatrixPredictListsFiltered); its exclusion rows go by user id."""
         nrcmds = int(nrcmds)
         if users is not None:
             users = np.ascontiguousarray(users, np.int32)
@@ -121,12 +122,16 @@ class ResidentModel(object):
         ids = np.full(n * nrcmds, -1, np.int32)
         scores = np.zeros(n * nrcmds, np.float32)
         counts = np.zeros(n, np.int32)
-        st = self._lib.SLIMGPU_MatrixPredictLists(
-            nrcmds, self.handle, device_matrix.handle, 0 if users is None else users.size,
-            None if users is None else users.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
-            scores.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p))
+        who = (0 if users is None else users.size, None if users is None else users.ctypes.data_as(C.c_void_p))
+        out = (ids.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p))
+        if filter is None:
+            st = self._lib.SLIMGPU_MatrixPredictLists(nrcmds, self.handle, device_matrix.handle, *(who + out))
+        else:
+            st = self._lib.SLIMGPU_MatrixPredictListsFiltered(nrcmds, self.handle, device_matrix.handle,
+                                                              *(who + (filter.handle,) + out))
         if st != SLIM_OK:
-            raise RuntimeError("SLIMGPU_MatrixPredictLists failed (%d): %s" % (st, _lib.last_error()))
+            raise RuntimeError("SLIMGPU_MatrixPredictLists%s failed (%d): %s"
+                               % ("" if filter is None else "Filtered", st, _lib.last_error()))
         out = (ids.reshape(n, nrcmds), scores.reshape(n, nrcmds))
         return out + (counts,) if return_counts else out
 
@@ -138,6 +143,47 @@ class ResidentModel(object):
     def __del__(self):
         try:
             self.free()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+class ItemFilter(object):
+    """A candidate filter of the top-N lists (SLIMGPU_FilterCreate, include/slim_gpu_filter.h) over `ncols`
+    items; owns the handle.  allowed / blocked: item ids (at most one of the two; allowed=[] allows nothing);
+    exclusions: a scipy matrix whose row u holds the items never shown to user u."""
+
+    def __init__(self, ncols, allowed=None, blocked=None, exclusions=None, lib=None):
+        if allowed is not None and blocked is not None:
+            raise ValueError("item filter: pass at most one of allowed / blocked")
+        self._lib = lib or _lib.load()
+        self.handle = C.c_void_p()
+        self.ncols = int(ncols)
+        items = allowed if blocked is None else blocked
+        if items is not None:   # (one spare element: an empty set still has an address)
+            ids = np.ascontiguousarray(items, dtype=np.int32).ravel()
+            buf = np.concatenate((ids, np.zeros(1, np.int32)))
+        xusers, xptr, xind = 0, None, None
+        if exclusions is not None:
+            X = sp.csr_matrix(exclusions)
+            xusers = X.shape[0]
+            xptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+            xind = np.concatenate((np.asarray(X.indices, dtype=np.int32), np.zeros(1, np.int32)))
+        st = self._lib.SLIMGPU_FilterCreate(
+            self.ncols, 0 if items is None else ids.size, None if items is None else buf.ctypes.data_as(C.c_void_p),
+            0 if blocked is None else 1, xusers, None if xptr is None else xptr.ctypes.data_as(C.c_void_p),
+            None if xind is None else xind.ctypes.data_as(C.c_void_p), C.byref(self.handle))
+        if st != SLIM_OK:
+            self.handle = C.c_void_p()
+            raise ValueError("SLIMGPU_FilterCreate failed (%d): %s" % (st, _lib.last_error()))
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            self._lib.SLIMGPU_FilterFree(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:   # noqa: BLE001 -- interpreter shutdown
             pass
 
@@ -438,6 +484,11 @@ class DeviceMatrix(object):
         lens = np.diff(T.indptr)[:nall] if sel is None else np.diff(T.indptr)[sel]
         indptr = np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
         return Evaluator(self._lib, h, self, () if ranked else cut.tolist(), indptr)
+
+    def item_filter(self, allowed=None, blocked=None, exclusions=None):
+        """SLIMGPU_FilterCreate over this matrix's items: an ItemFilter for ResidentModel.predict(filter=...).
+        Pass at most one of allowed / blocked (item ids); exclusions: a scipy CSR over user rows."""
+        return ItemFilter(self.ncols, allowed, blocked, exclusions, lib=self._lib)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)

@@ -304,11 +304,67 @@ class SLIM(object):
         self.mselect_result = dict(bestHR=(l1hr, l2hr, hrhr, arhr), bestAR=(l1ar, l2ar, hrar, arar))
 
     # -- prediction ----------------------------------------------------------
-    def predict(self, data, nrcmds=10, outfile=None, negitems=None, nnegs=0, returnscores=False):
+    def _known_items(self, items, ncols):
+        """Dense ids (below ncols) of the original item ids the model knows; the others are dropped."""
+        known = []
+        is_dict = isinstance(self.item2id, dict)
+        for it in items:
+            if is_dict:
+                j = self.item2id.get(it, -1)
+            else:
+                j = int(it) if isinstance(it, numbers.Integral) and 0 <= it < len(self.item2id) else -1
+            if 0 <= j < ncols:
+                known.append(j)
+        return np.asarray(known, dtype=np.int32)
+
+    def _candidate_filter(self, data, allowed_items, blocked_items, exclude):
+        """The ItemFilter of predict(): original ids through the model's item map, the rows of `exclude` put in
+        the order of data's users."""
+        from .engine import ItemFilter
+        if allowed_items is not None and blocked_items is not None:
+            raise TypeError("Please provide at most one of allowed_items and blocked_items.")
+        ncols = int(C.cast(self.handle, C.POINTER(_lib.CsrView)).contents.ncols)
+        allowed = None if allowed_items is None else self._known_items(allowed_items, ncols)
+        blocked = None if blocked_items is None else self._known_items(blocked_items, ncols)
+        rows = None
+        if exclude is not None:
+            assert type(exclude) == SLIMatrix, "exclude must be a SLIMatrix object."
+            assert exclude.nItems == self.nItems, "The shape of exclude should match the model."
+            nnz = C.c_int(0)
+            self._lib.Py_csr_stat(exclude.handle, C.byref(nnz))
+            ptr = np.zeros(exclude.nUsers + 1, dtype=np.int32)
+            ind = np.zeros(max(nnz.value, 1), dtype=np.int32)
+            val = np.ones(max(nnz.value, 1), dtype=np.float32)
+            self._lib.Py_csr_export(exclude.handle, ptr, ind, val)
+            if isinstance(data.user2id, dict):
+                xdict = isinstance(exclude.user2id, dict)
+                src = [exclude.user2id.get(k, -1) if xdict else (k if 0 <= k < exclude.nUsers else -1)
+                       for k in data.user2id]   # (dense ids ascend in insertion order)
+            else:
+                src = [u if u < exclude.nUsers else -1 for u in range(data.nUsers)]
+            xptr, xind = [0], []
+            for r in src:
+                if r >= 0:
+                    row = ind[ptr[r]:ptr[r + 1]]
+                    xind.extend(row[row < ncols].tolist())
+                xptr.append(len(xind))
+            rows = sp.csr_matrix((np.ones(len(xind), np.float32), np.asarray(xind, np.int32),
+                                  np.asarray(xptr, np.int64)), shape=(len(src), max(ncols, 1)))
+        return ItemFilter(ncols, allowed, blocked, rows, lib=self._lib)
+
+    def predict(self, data, nrcmds=10, outfile=None, negitems=None, nnegs=0, returnscores=False,
+                allowed_items=None, blocked_items=None, exclude=None):
+        """allowed_items / blocked_items (at most one): ORIGINAL item ids that alone may / may not be
+        recommended; exclude: a SLIMatrix built against the same maps whose row of a user holds the items never
+        shown to that user.  Ids the model does not know are ignored.  (An engine extension: the reference's
+        predict has no filters.)"""
         if self.ismodel != SLIM_OK:
             raise TypeError("Model not found. Please train a model.")
         assert self.nItems == data.nItems, \
             "The shape of the input matrix should match the model."
+        filtered = not (allowed_items is None and blocked_items is None and exclude is None)
+        if filtered and negitems is not None:
+            raise TypeError("Item filters do not apply to the prediction over negative items.")
         res = np.full(data.nUsers * nrcmds, -1, dtype=np.int32)
         scores = np.zeros(data.nUsers * nrcmds, dtype=np.float32)
         user_is_dict = isinstance(data.user2id, dict)
@@ -336,6 +392,12 @@ class SLIM(object):
                 print("%d negative items not in the training set." % unknown)
             rc = self._lib.Py_SLIM_Predict_1vsk(nrcmds, nnegs, self.handle, data.handle, cand,
                                                 res, scores)
+        elif filtered:
+            flt = self._candidate_filter(data, allowed_items, blocked_items, exclude)
+            try:
+                rc = self._lib.Py_SLIM_PredictFiltered(nrcmds, self.handle, data.handle, flt.handle, res, scores)
+            finally:
+                flt.close()
         else:
             rc = self._lib.Py_SLIM_Predict(nrcmds, self.handle, data.handle, res, scores)
         if rc != SLIM_OK:
