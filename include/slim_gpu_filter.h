@@ -1,6 +1,7 @@
 /*
  * slim_gpu_filter.h -- engine extensions of libslim.so: candidate filters for the top-N lists of
- * slim_gpu_lists.h.  Included by slim_gpu.h; plain C types only.
+ * slim_gpu_lists.h, and for the evaluation and the ranks of slim_gpu_eval.h / slim_gpu_rank.h.  Included by
+ * slim_gpu.h; plain C types only.
  *
  * A filter narrows what may be recommended: a set of items that may (or may not) be shown to anybody, and a
  * list per user of items that may not be shown to that user.  With a filter, the candidates of a user are the
@@ -20,8 +21,9 @@
  * the same shape allocates nothing for it.  A filter is not tied to a model, only to a number of items; a call
  * whose model has another ncols is SLIM_ERROR_INPUT and writes nothing.  filter == NULL in a call: no filter.
  *
- * Not built: evaluation and ranks under a filter (SLIMGPU_EvalSet*, SLIMGPU_ModelRanks take none);
- * recommending history items; skipping the history walk of chunks in which nothing is allowed.
+ * Evaluation, ranks and the model-selection grid under a filter: slim_gpu_filter_eval.h (included below).
+ *
+ * Not built: recommending history items; skipping the history walk of chunks in which nothing is allowed.
  */
 #ifndef SLIM_AMD_SLIM_GPU_FILTER_H_
 #define SLIM_AMD_SLIM_GPU_FILTER_H_
@@ -59,4 +61,7 @@ int32_t Py_SLIM_PredictFiltered(int32_t nrcmds, slim_t *slimhandle, slim_t *trnh
 #ifdef __cplusplus
 }
 #endif
+
+#include "slim_gpu_filter_eval.h"
+
 #endif /* SLIM_AMD_SLIM_GPU_FILTER_H_ */

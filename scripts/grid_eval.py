@@ -26,6 +26,11 @@ times each: (A) SLIMGPU_ModelEvaluate at --nrcmds from the build at --parent-lib
 a matrix handle, a model and an eval set of its own over the same device arrays; skipped without it), (B) the same
 call from this build, (C) SLIMGPU_ModelEvaluateRanked at the cutoff --nrcmds, (D) the same at --ranked-cutoffs.
 C and D report the pre-pass (k_test_keys) from its own events; B and C must give the same figures.
+With --filtered the variants are instead A, A2 (the parent build's SLIMGPU_ModelEvaluateRanked), B, C, and E / F: B's and
+C's calls of this build under a candidate filter (SLIMGPU_ModelEvaluateAtFiltered, SLIMGPU_ModelEvaluateRankedFiltered)
+that allows --allow-fraction of the items and excludes --exclusions random items per user.  The bound on B (C) is A's
+(A2's) slowest run plus the spread of A's (A2's) runs, all in this one job; every run has --run-limit-s seconds, after
+which the process is killed (SIGALRM, no handler).
 
 --pairs 0 (default): the short grid -- the cold pair, three l2 steps and one l1 change; N > 0: the first
 N pairs of the file; -1: all of them (each warm-started from the one before it in the list).  The run stops adding pairs when --budget-s is used up and says so.
@@ -79,7 +84,7 @@ class ParentBuild(object):
         from slim_amd import _lib as _l
         from slim_amd.engine import _wrap_rows, make_options
         self.lib = lib = C.CDLL(path)
-        for table in (_l._SIGNATURES, _l._EVAL_SIGNATURES):
+        for table in (_l._SIGNATURES, _l._EVAL_SIGNATURES, _l._RANK_SIGNATURES):
             for name, (res, argt) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = res, argt
@@ -100,21 +105,30 @@ class ParentBuild(object):
         self.es = C.c_void_p(lib.SLIMGPU_EvalSetCreate(self.mat, ht, fm, fm.size, 10, C.byref(st)))
         lib.Py_csr_free(ht)
         assert self.es, lib.SLIMGPU_LastError()
+        ht = _wrap_rows(lib, T)
+        self.esr = C.c_void_p(lib.SLIMGPU_EvalSetCreateRanked(self.mat, ht, fm, fm.size, 0, None, C.byref(st)))
+        lib.Py_csr_free(ht)
+        assert self.esr, lib.SLIMGPU_LastError()
 
-    def evaluate(self):
+    def evaluate(self, ranked=False):
         import numpy as np
         from slim_amd import _lib as _l
         from slim_amd.constants import SLIM_OK
         met, nv = np.zeros(4), np.zeros(3, np.int32)
+        cut = np.array([10], np.int32)
         t0 = time.time()
-        rc = self.lib.SLIMGPU_ModelEvaluate(self.es, self.model, met, nv)
+        if ranked:
+            rc = self.lib.SLIMGPU_ModelEvaluateRanked(self.esr, self.model, 1, cut.ctypes.data_as(C.c_void_p), met, nv)
+        else:
+            rc = self.lib.SLIMGPU_ModelEvaluate(self.es, self.model, met, nv)
         s = time.time() - t0
         assert rc == SLIM_OK, (rc, self.lib.SLIMGPU_LastError())
         st = _l.EvalStats()
         self.lib.SLIMGPU_LastEvalStats(C.byref(st))
-        return s, (met.tolist(), nv.tolist()), st.as_dict()
+        return s, (met.tolist(), nv.tolist()), st.as_dict(), float(self.lib.SLIMGPU_LastRankPrepassMs()) if ranked else 0.0
 
     def close(self):
+        self.lib.SLIMGPU_EvalSetFree(C.byref(self.esr))
         self.lib.SLIMGPU_EvalSetFree(C.byref(self.es))
         self.lib.SLIMGPU_ModelFree(C.byref(self.model))
         self.lib.SLIMGPU_MatrixFree(C.byref(self.mat))
@@ -136,7 +150,7 @@ def ranked_comparison(args, mat, T, fm, shape, say):
     many = [int(v) for v in args.ranked_cutoffs.split(",") if v]
     KEYS = ("hr", "hr_head", "hr_tail", "arhr")
     NK = ("nvalid", "nvalid_head", "nvalid_tail")
-    fig = lambda d: ([d[k] for k in KEYS], [d[k] for k in NK])
+    fig = lambda d: ([float(d[k]) for k in KEYS], [int(d[k]) for k in NK])
 
     def run_b():
         t0 = time.time()
@@ -154,10 +168,53 @@ def ranked_comparison(args, mat, T, fm, shape, say):
         return time.time() - t0, [(r["nrcmds"], r["hr"], r["arhr"]) for r in g], evr.stats(), evr.prepass_ms()
 
     def run_a():
-        s, f, st = parent.evaluate()
-        return s, f, st, 0.0
+        return parent.evaluate()
+
+    def run_a2():
+        return parent.evaluate(ranked=True)
 
     variants = ([("A", run_a)] if parent else []) + [("B", run_b), ("C", run_c), ("D", run_d)]
+    flt = None
+    if args.filtered:
+        import numpy as np
+        import scipy.sparse as sp
+        t0 = time.time()
+        rng = np.random.default_rng(args.seed + 7)
+        nrows, ncols = shape[0], shape[1]
+        allowed = np.flatnonzero(rng.random(ncols) < args.allow_fraction)
+        X = sp.csr_matrix((nrows, ncols), dtype=np.float32)      # (by hand: no sort, no merge of repeats)
+        X.indices = rng.integers(0, ncols, size=nrows * args.exclusions, dtype=np.int32)
+        X.indptr = np.arange(nrows + 1, dtype=np.int64) * args.exclusions
+        X.data = np.ones(X.indices.size, np.float32)
+        flt = mat.item_filter(allowed=allowed, exclusions=X)
+        say("# filter: %d of %d items allowed, %d exclusions per user (%d entries), made in %.1f s"
+            % (allowed.size, ncols, args.exclusions, X.indices.size, time.time() - t0))
+        del X
+
+        def run_e():
+            t0 = time.time()
+            g = ev.evaluate(model, filter=flt)
+            return time.time() - t0, fig(g), ev.stats(), 0.0
+
+        def run_f():
+            t0 = time.time()
+            g = evr.evaluate_ranked(model, [args.nrcmds], filter=flt)
+            return time.time() - t0, fig(g[0]), evr.stats(), evr.prepass_ms()
+
+        variants = ([("A", run_a), ("A2", run_a2)] if parent else []) + [("B", run_b), ("C", run_c), ("E", run_e),
+                                                                        ("F", run_f)]
+    if args.run_limit_s > 0:     # every run under its own limit: SIGALRM without a handler ends the process
+        import signal
+
+        def limited(f):
+            def g():
+                signal.alarm(int(args.run_limit_s))
+                try:
+                    return f()
+                finally:
+                    signal.alarm(0)
+            return g
+        variants = [(n, limited(f)) for n, f in variants]
     for name, fn in variants:            # a warm-up of each: workspaces made, code objects loaded
         fn()
     say("# %-3s %-3s %9s %10s %11s %5s %6s %6s %9s | figures" % ("run", "var", "eval_s", "kernel_ms", "prepass_ms", "path",
@@ -177,8 +234,24 @@ def ranked_comparison(args, mat, T, fm, shape, say):
     for name, _ in variants:
         k = [x[0] for x in res[name]]
         p = [x[1] for x in res[name]]
-        say("# %s: kernel_ms %.1f .. %.1f%s" % (name, min(k), max(k),
-                                               "" if name in "AB" else ", pre-pass %.1f .. %.1f ms" % (min(p), max(p))))
+        say("# %s: kernel_ms %.1f .. %.1f%s" % (name, min(k), max(k), "" if name in ("A", "B", "E") else
+                                               ", pre-pass %.1f .. %.1f ms" % (min(p), max(p))))
+    if args.filtered:
+        assert figs["E"] == figs["F"], "E and F disagree: %r vs %r" % (figs["E"], figs["F"])
+        say("# E and F gave equal figures; filtered hr %.6f against %.6f unfiltered" % (figs["E"][0][0], figs["B"][0][0]))
+        for mine, theirs in (("B", "A"), ("C", "A2")) if parent else ():
+            km, kt = [x[0] for x in res[mine]], [x[0] for x in res[theirs]]
+            bound = max(kt) + (max(kt) - min(kt))
+            say("# %s against %s: the parent's slowest run %.1f ms + its spread %.1f ms = %.1f ms; this build's slowest "
+                "%.1f ms, median %.1f ms: %s" % (mine, theirs, max(kt), max(kt) - min(kt), bound, max(km),
+                                                 sorted(km)[len(km) // 2], "inside" if max(km) <= bound else "EXCEEDS"))
+        if parent:
+            parent.close()
+        flt.close()
+        ev.close()
+        evr.close()
+        model.free()
+        return
     kb = [x[0] for x in res["B"]]
     kc, pc = [x[0] for x in res["C"]], [x[1] for x in res["C"]]
     say("# C against B: slowest C %.1f ms; B's slowest run plus the pre-pass = %.1f ms: %s"
@@ -208,6 +281,10 @@ def main():
     ap.add_argument("--parent-lib", default="", help="--ranked: libslim.so of the parent commit (run A)")
     ap.add_argument("--runs", type=int, default=4, help="--ranked: runs of each variant")
     ap.add_argument("--ranked-cutoffs", default="5,10,20,50,100,200,500", help="--ranked: the cutoffs of run D")
+    ap.add_argument("--filtered", action="store_true", help="--ranked: what a filter costs, and what carrying it costs")
+    ap.add_argument("--allow-fraction", type=float, default=0.5, help="--filtered: the allow set's share of the items")
+    ap.add_argument("--exclusions", type=int, default=20, help="--filtered: exclusion entries per user")
+    ap.add_argument("--run-limit-s", type=float, default=0, help="--ranked: seconds every single run may take (0: no limit)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_eval_c5.txt"))
     args = ap.parse_args()
     import numpy as np

@@ -218,6 +218,19 @@ _FILTER_SIGNATURES = {
 
 FILTER_SYMBOLS = tuple(_FILTER_SIGNATURES)
 
+# evaluation, ranks and the model-selection grid under a filter (include/slim_gpu_filter_eval.h): the unfiltered
+# calls' arguments with the filter handle behind the model (the grid: as its last argument)
+_FILTERED_EVAL_SIGNATURES = {
+    "SLIMGPU_ModelEvaluateAtFiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, f64_1d, i32_1d]),
+    "SLIMGPU_ModelRanksFiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_ModelEvaluateRankedFiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                        f64_1d, i32_1d]),
+    "Py_SLIM_MselectFiltered": (C.c_int32, [C.c_void_p, C.c_void_p, i32_1d, f64_1d, f64_1d, f64_1d,
+                                            C.c_int32, C.c_int32] + [C.c_void_p] * 9),
+}
+
+FILTERED_EVAL_SYMBOLS = tuple(_FILTERED_EVAL_SIGNATURES)
+
 _lib = None
 
 
@@ -234,7 +247,7 @@ def load():
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
                               list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
                               list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
-                              list(_FILTER_SIGNATURES.items())):
+                              list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

@@ -176,13 +176,18 @@ slimgpu_evalset_t* evalset_create(slimgpu_matrix_t* mat, const slim_csr_t* tst, 
 slimgpu_evalset_t* evalset_create_ranked(slimgpu_matrix_t* mat, const slim_csr_t* tst, const int32_t* fmarker,
                                          int32_t fm_ncols, int32_t nusers, const int32_t* users, int32_t* status);
 int64_t evalset_entries(const slimgpu_evalset_t* es);
-int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores);
+// filter (slim_gpu_filter.h; nullptr: none) narrows the candidates of the three calls below: a test entry it
+// removes stays in every denominator, is a miss at every cutoff and has rank 0 and score 0; a filter made for
+// another ncols than the model's is refused before anything is queued
+int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores,
+                    slimgpu_filter* filter = nullptr);
 int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs,
-                              const int32_t* cutoffs, EvalResult* out);
+                              const int32_t* cutoffs, EvalResult* out, slimgpu_filter* filter = nullptr);
 double last_rank_prepass_ms();
 void evalset_free(slimgpu_evalset_t* es);
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es);
-int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out);
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out,
+                       slimgpu_filter* filter = nullptr);
 int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
                        float* scores);
 // users[nusers]: the rows scored, ascending (nullptr and 0: every row); counts may be null

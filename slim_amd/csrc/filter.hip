@@ -96,7 +96,7 @@ int32_t filter_check(const char* who, const slimgpu_filter* f, int32_t model_nco
                 std::to_string(model_ncols));
 }
 
-CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stream, int* allocs) {
+CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stream, int* allocs, int64_t* h2d) {
   CandidateFilter F;
   if (!f || (!f->has_bits && !f->has_rows)) return F;
   if (f->device != device) {  // first use here: the copy of another device goes
@@ -106,8 +106,10 @@ CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stre
       using T = std::remove_reference_t<decltype(host[0])>;
       buf.reserve(host.size());
       if (allocs) ++*allocs;
-      if (!host.empty())
+      if (!host.empty()) {
         HIP_TRY(hipMemcpyAsync(buf.get(), host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice, stream));
+        if (h2d) *h2d += (int64_t)(sizeof(T) * host.size());
+      }
     };
     if (f->has_bits) put(f->d_bits, f->bits);
     if (f->has_rows) {

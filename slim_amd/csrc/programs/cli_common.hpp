@@ -179,6 +179,59 @@ inline std::vector<int32_t> read_ids(const std::string& path) {
   return ids;
 }
 
+// ---- candidate filters: -allowfile | -blockfile, -exclfile (slim_predict, slim_mselect) --------------
+constexpr OptSpec kFilterSpecs[] = {{"allowfile", true}, {"blockfile", true}, {"exclfile", true}};
+constexpr const char* kFilterUsage =
+    "   -allowfile=file | -blockfile=file  (item ids, one per line: only these / none of these are\n"
+    "   recommended)  -exclfile=file  (a matrix in -ifmt: row u holds items never shown to user u)\n";
+
+// whether a filter is asked for; the two item sets exclude each other
+inline bool filter_options(const Args& a) {
+  if (a.has("allowfile") && a.has("blockfile")) die("The -allowfile and -blockfile options cannot be used together.");
+  return a.has("allowfile") || a.has("blockfile") || a.has("exclfile");
+}
+inline void filter_files_exist(const Args& a) {
+  for (const auto& s : kFilterSpecs)
+    if (a.has(s.name) && !file_exists(a.str(s.name, ""))) die("Input file " + a.str(s.name, "") + " does not exist.");
+}
+// The filter of the options over `ncols` items (free with SLIMGPU_FilterFree).  Ids outside [0, ncols) cannot be
+// recommended anyway: they are dropped.  allowed / excluded: what is left, for a header line.
+struct CliFilter {
+  slimgpu_filter_t* handle = nullptr;
+  int64_t allowed = 0, excluded = 0;
+};
+inline CliFilter read_filter(const Args& a, int32_t ncols, Fmt fmt) {
+  CliFilter F;
+  const bool blocked = a.has("blockfile"), set = a.has("allowfile") || blocked;
+  std::vector<int32_t> items;
+  if (set)
+    for (const int32_t id : read_ids(a.str(blocked ? "blockfile" : "allowfile", "")))
+      if (id >= 0 && id < ncols) items.push_back(id);
+  std::vector<char> named(std::max(ncols, 0), 0);
+  for (const int32_t id : items) named[id] = 1;
+  const int64_t nnamed = std::count(named.begin(), named.end(), 1);
+  F.allowed = !set ? ncols : (blocked ? ncols - nnamed : nnamed);
+  items.push_back(0);  // (a spare element: an empty allow set still has an address)
+  std::vector<int64_t> xptr;
+  std::vector<int32_t> xind;
+  if (a.has("exclfile")) {
+    const Csr excl = read_matrix(a.str("exclfile", ""), fmt);
+    xptr.push_back(0);
+    for (int32_t u = 0; u < excl.nrows; ++u) {
+      for (ssize_t z = excl.ptr[u]; z < excl.ptr[u + 1]; ++z)
+        if (excl.ind[z] >= 0 && excl.ind[z] < ncols) xind.push_back(excl.ind[z]);
+      xptr.push_back((int64_t)xind.size());
+    }
+    F.excluded = (int64_t)xind.size();
+    xind.push_back(0);
+  }
+  if (SLIMGPU_FilterCreate(ncols, (int32_t)items.size() - 1, set ? items.data() : nullptr, blocked,
+                           xptr.empty() ? 0 : (int32_t)xptr.size() - 1, xptr.empty() ? nullptr : xptr.data(),
+                           xptr.empty() ? nullptr : xind.data(), &F.handle) != SLIM_OK)
+    die(std::string("cannot make the item filter: ") + SLIMGPU_LastError());
+  return F;
+}
+
 // row view of a model handle, in the same format as the input (slim_learn.c:83)
 inline void write_matrix(const slim_csr_t* m, const std::string& path, Fmt fmt) {
   FILE* f = std::fopen(path.c_str(), "w");

@@ -6,11 +6,12 @@
 using namespace slimcli;
 
 int main(int argc, char** argv) {
-  const std::vector<OptSpec> specs = {
+  std::vector<OptSpec> specs = {
       {"ifmt", true},    {"binarize", false}, {"optTol", true},  {"niters", true},
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
       {"evalstride", true}, {"gpukernel", true}, {"help", false}};
+  specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() != 3) {
     std::printf("\n Usage: slim_mselect [options] train-file test-file l12-file\n"
@@ -19,7 +20,10 @@ int main(int argc, char** argv) {
                 "   -ngpus=i   (engine extension: R replicated on i GPUs, every model sharded over them)\n"
                 "   -evalstride=i  (engine extension: evaluate users 0, i, 2i, ... only; needs the evaluation in HBM)\n"
                 "   (-nrcmds above 128 is evaluated in HBM from the ranks of the held-out items: no lists are formed)\n"
-                "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n\n");
+                "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n"
+                "%s   (engine extension: every pair is evaluated under the filter; a held-out item it removes is a miss;\n"
+                "   needs the evaluation in HBM)\n\n",
+                kFilterUsage);
     return 0;
   }
   const Fmt fmt = parse_fmt(a.str("ifmt", "csr"));
@@ -28,6 +32,8 @@ int main(int argc, char** argv) {
   const int nrcmds = a.integer("nrcmds", 10);
   const int stride = a.integer("evalstride", 1);
   if (stride < 1) die("Invalid -evalstride of " + a.str("evalstride", "") + ".");
+  const bool filtered = filter_options(a);
+  filter_files_exist(a);
   Csr trn = read_matrix(a.pos[0], fmt), tst = read_matrix(a.pos[1], fmt);
   if (a.has("binarize")) trn.has_val = false;
   const std::string sim = a.str("simtype", "cos");
@@ -102,7 +108,24 @@ int main(int argc, char** argv) {
     die(std::string("-evalstride needs the evaluation in HBM (one GPU, nrcmds >= 1, SLIM_GPU_RESIDENT and "
                     "SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ") +
         (nrcmds < 1 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
+  // nor is there an evaluation under a filter outside HBM: no silent evaluation on the raw catalogue
+  CliFilter flt;
+  int32_t rrows = 0, rcols = 0;  // the resident models are as wide as the staged matrix
+  int64_t rnnz = 0;
+  if (filtered) {
+    if (!evalset)
+      die(std::string("the item filters need the evaluation in HBM (one GPU, nrcmds >= 1, SLIM_GPU_RESIDENT and "
+                      "SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ") +
+          (!resident ? std::string("the models of this grid do not stay in HBM")
+           : evr_env && std::atoi(evr_env) == 0 ? std::string("SLIM_GPU_EVAL_RESIDENT=0")
+           : nrcmds < 1 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
+    SLIMGPU_MatrixInfo(R, &rrows, &rcols, &rnnz);
+    flt = read_filter(a, rcols, fmt);
+  }
   if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
+  if (filtered)
+    std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)flt.allowed, rcols,
+                (long long)flt.excluded);
   std::printf("\nEstimating & evaluating models...\n\n");
   double best_hr = 0, best_ar = 0, bh_l1 = 0, bh_l2 = 0, ba_l1 = 0, ba_l2 = 0;
   while (std::fgets(line, sizeof line, lf)) {
@@ -144,9 +167,11 @@ int main(int argc, char** argv) {
     Eval e;
     double em[4];
     int32_t env[3];
-    const bool evaluated = evalset && (ranked ? SLIMGPU_ModelEvaluateRanked(evalset, dmodel, 1, &cutoff, em, env)
-                                              : SLIMGPU_ModelEvaluate(evalset, dmodel, em, env)) == SLIM_OK;
-    if (!evaluated && stride > 1) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
+    // (one list length: the filtered call's only row is SLIMGPU_ModelEvaluate's; a null filter is no filter)
+    const bool evaluated =
+        evalset && (ranked ? SLIMGPU_ModelEvaluateRankedFiltered(evalset, dmodel, flt.handle, 1, &cutoff, em, env)
+                           : SLIMGPU_ModelEvaluateAtFiltered(evalset, dmodel, flt.handle, 1, em, env)) == SLIM_OK;
+    if (!evaluated && (stride > 1 || filtered)) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
     if (evaluated) {
       e.hr = em[0]; e.hr_head = em[1]; e.hr_tail = em[2]; e.arhr = em[3];
       e.nvalid = env[0]; e.nvalid_head = env[1]; e.nvalid_tail = env[2];
@@ -175,6 +200,7 @@ int main(int argc, char** argv) {
   SLIM_FreeModel(&model);
   SLIMGPU_ModelFree(&dmodel);
   SLIMGPU_EvalSetFree(&evalset);
+  SLIMGPU_FilterFree(flt.handle);
   std::free(fmarker);
   Py_csr_free(hold);
   SLIMGPU_MatrixFree(&R);

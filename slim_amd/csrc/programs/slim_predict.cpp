@@ -7,15 +7,14 @@
 using namespace slimcli;
 
 int main(int argc, char** argv) {
-  const std::vector<OptSpec> specs = {{"ifmt", true},      {"binarize", false}, {"outfile", true},
-                                      {"nrcmds", true},    {"dbglvl", true},    {"help", false},
-                                      {"allowfile", true}, {"blockfile", true}, {"exclfile", true}};
+  std::vector<OptSpec> specs = {{"ifmt", true},   {"binarize", false}, {"outfile", true},
+                                {"nrcmds", true}, {"dbglvl", true},    {"help", false}};
+  specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() < 2 || a.pos.size() > 4) {
     std::printf("\n Usage: slim_predict [options] model-file old-file [test-file] [neg-file]\n"
-                "   -ifmt=csr|csrnv|cluto|ijv  -binarize  -outfile=file  -nrcmds=i  -dbglvl=i\n"
-                "   -allowfile=file | -blockfile=file  (item ids, one per line: only these / none of these are\n"
-                "   recommended)  -exclfile=file  (a matrix in -ifmt: row u holds items never shown to user u)\n\n");
+                "   -ifmt=csr|csrnv|cluto|ijv  -binarize  -outfile=file  -nrcmds=i  -dbglvl=i\n%s\n",
+                kFilterUsage);
     return 0;
   }
   const Fmt fmt = parse_fmt(a.str("ifmt", "csr"));
@@ -23,11 +22,9 @@ int main(int argc, char** argv) {
   if (nrcmds < 1) die("The -nrcmds parameter should be positive.");
   for (const auto& p : a.pos)
     if (!file_exists(p)) die("Input file " + p + " does not exist.");
-  if (a.has("allowfile") && a.has("blockfile")) die("The -allowfile and -blockfile options cannot be used together.");
-  const bool filtered = a.has("allowfile") || a.has("blockfile") || a.has("exclfile");
+  const bool filtered = filter_options(a);
   if (filtered && a.pos.size() > 3) die("The item filters do not apply to a prediction over a neg-file.");
-  for (const char* k : {"allowfile", "blockfile", "exclfile"})
-    if (a.has(k) && !file_exists(a.str(k, ""))) die("Input file " + a.str(k, "") + " does not exist.");
+  filter_files_exist(a);
 
   slim_t* model = read_model(a.pos[0], fmt == Fmt::csrnv ? Fmt::csr : fmt);
   const slim_csr_t* W = static_cast<slim_csr_t*>(model);
@@ -53,31 +50,7 @@ int main(int argc, char** argv) {
   if (!has_neg) {
     // all users at once (GPU scorer when a device is present, identical lists otherwise)
     slim_t* hold = to_handle(old);
-    slimgpu_filter_t* flt = nullptr;
-    if (filtered) {  // ids the model does not have cannot be recommended anyway: they are dropped
-      const bool blocked = a.has("blockfile");
-      std::vector<int32_t> items;
-      if (a.has("allowfile") || blocked)
-        for (const int32_t id : read_ids(a.str(blocked ? "blockfile" : "allowfile", "")))
-          if (id >= 0 && id < W->ncols) items.push_back(id);
-      items.push_back(0);  // (a spare element: an empty allow set still has an address)
-      std::vector<int64_t> xptr;
-      std::vector<int32_t> xind;
-      if (a.has("exclfile")) {
-        const Csr excl = read_matrix(a.str("exclfile", ""), fmt);
-        xptr.push_back(0);
-        for (int32_t u = 0; u < excl.nrows; ++u) {
-          for (ssize_t z = excl.ptr[u]; z < excl.ptr[u + 1]; ++z)
-            if (excl.ind[z] >= 0 && excl.ind[z] < W->ncols) xind.push_back(excl.ind[z]);
-          xptr.push_back((int64_t)xind.size());
-        }
-        xind.push_back(0);
-      }
-      if (SLIMGPU_FilterCreate(W->ncols, (int32_t)items.size() - 1, a.has("allowfile") || blocked ? items.data() : nullptr,
-                               blocked, xptr.empty() ? 0 : (int32_t)xptr.size() - 1, xptr.empty() ? nullptr : xptr.data(),
-                               xptr.empty() ? nullptr : xind.data(), &flt) != SLIM_OK)
-        die(std::string("cannot make the item filter: ") + SLIMGPU_LastError());
-    }
+    slimgpu_filter_t* flt = filtered ? read_filter(a, W->ncols, fmt).handle : nullptr;
     const int32_t rc = filtered ? Py_SLIM_PredictFiltered(nrcmds, model, hold, flt, lists.data(), scores.data())
                                 : Py_SLIM_Predict(nrcmds, model, hold, lists.data(), scores.data());
     if (rc != SLIM_OK) die(std::string("prediction failed: ") + SLIMGPU_LastError());

@@ -266,11 +266,13 @@ int64_t evalset_entries(const slimgpu_evalset_t* es) { return es ? es->entries :
 void evalset_free(slimgpu_evalset_t* es) { delete es; }
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es) { return es ? es->cut.n : 0; }
 
-int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out) {
-  const char* who = "SLIMGPU_ModelEvaluate";
+int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out,
+                       slimgpu_filter* filter) {
+  const char* who = filter ? "SLIMGPU_ModelEvaluateAtFiltered" : "SLIMGPU_ModelEvaluate";
   DeviceRowView W;
   DeviceCsrView R;
   if (const int32_t rc = check_evaluation(who, out != nullptr, es, model, &ncutoffs, W, R); rc != SLIM_OK) return rc;
+  if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   const int32_t ncut = es->cut.n;
   for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
   const auto t_begin = std::chrono::steady_clock::now();
@@ -284,8 +286,10 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
     if (es->nsel > 0) {
       const ScorerRequest rq =
           EvalTargets{es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get(), es->cut};
+      // (the filter's device copy is made by its first call on this device; later ones allocate and send nothing)
+      const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
       HIP_TRY(hipEventRecord(es->ev0, stream));
-      st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws).path;
+      st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
       launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
     }
     finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
@@ -299,9 +303,10 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
 namespace {
 // the checks both ranked calls share, then the scorer in rank mode on the matrix's stream: ranks and scores of
 // the eval set's test entries are in es->ws.rank / rscore when the stream has run.  SLIM_OK or a refusal.
-int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, DeviceRowView& W,
-                    DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st) {
+int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
+                    DeviceRowView& W, DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st) {
   if (const int32_t rc = check_evaluation(who, true, es, model, nullptr, W, R); rc != SLIM_OK) return rc;
+  if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   (void)hipGetLastError();
   HIP_TRY(hipSetDevice(R.device));
   hipStream_t stream = static_cast<hipStream_t>(R.stream);
@@ -312,21 +317,24 @@ int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model*
   H = history_of(R, es);
   const ScorerRequest rq = RankTargets{es->tst.ptr.get(), es->tst.ind.get(), es->tbase(),
                                        es->entries,       es->max_test,      es->evk0,    es->evk1};
+  const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
   HIP_TRY(hipEventRecord(es->ev0, stream));
-  if (queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws).path != kRank)
+  if (queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path != kRank)
     return refuse(std::string(who) + ": " + last_error());
   return SLIM_OK;
 }
 }  // namespace
 
-int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores) {
+int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores,
+                    slimgpu_filter* filter) {
+  const char* who = filter ? "SLIMGPU_ModelRanksFiltered" : "SLIMGPU_ModelRanks";
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
   try {
     DeviceRowView W;
     DeviceCsrView R;
     HistoryView H;
-    if (const int32_t rc = queue_ranks("SLIMGPU_ModelRanks", es, model, W, R, H, st); rc != SLIM_OK) return rc;
+    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st); rc != SLIM_OK) return rc;
     if (es->nsel > 0) {
       hipStream_t stream = static_cast<hipStream_t>(R.stream);
       HIP_TRY(hipEventRecord(es->ev1, stream));
@@ -349,7 +357,7 @@ int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* 
 }
 
 int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs,
-                              const int32_t* cutoffs, EvalResult* out) {
+                              const int32_t* cutoffs, EvalResult* out, slimgpu_filter* filter) {
   if (!cutoffs || !out || ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_RANK_CUTOFFS)
     return refuse("SLIMGPU_ModelEvaluateRanked: between 1 and " + std::to_string(SLIMGPU_MAX_RANK_CUTOFFS) +
               " cutoffs, not " + std::to_string(ncutoffs));
@@ -366,7 +374,8 @@ int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model,
     DeviceRowView W;
     DeviceCsrView R;
     HistoryView H;
-    if (const int32_t rc = queue_ranks("SLIMGPU_ModelEvaluateRanked", es, model, W, R, H, st); rc != SLIM_OK) return rc;
+    const char* who = filter ? "SLIMGPU_ModelEvaluateRankedFiltered" : "SLIMGPU_ModelEvaluateRanked";
+    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st); rc != SLIM_OK) return rc;
     if (es->nsel > 0) {
       hipStream_t stream = static_cast<hipStream_t>(R.stream);
       const size_t nterms = (size_t)SLIMGPU_MAX_CUTOFFS * (size_t)es->nsel;

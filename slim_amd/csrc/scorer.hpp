@@ -57,8 +57,9 @@ struct CandidateFilter {
 };
 // The device copy of `f` (nullptr: no filter) on the current device, `device`: uploaded on `stream` on the
 // first use there (the stream is drained once, so that later calls may use another) and kept until the
-// filter is freed.  *allocs grows by the device allocations this made.
-CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stream, int* allocs);
+// filter is freed.  *allocs grows by the device allocations this made, *h2d (optional) by the bytes it sent.
+CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stream, int* allocs,
+                                 int64_t* h2d = nullptr);
 
 // What a caller wants, one of four.  Lists of up to 128 into ws.oid / osc / ocnt; the same of up to
 // SLIMGPU_MAX_LIST (ws.lstats is the caller's to provide and to clear: it adds up over the slices of one call);
@@ -110,7 +111,8 @@ struct ScorerLaunch {  // how queue_scorer served a call
   std::chrono::steady_clock::time_point launched;  // host time at which the scorer kernel itself was first queued
 };
 // Queues on `stream` what `rq` asks for, on the path of `choice` (choose_scorer's for this W, H and rq).
-// F narrows the candidates of the lists (the evaluation and the rank mode take none).
+// F narrows the candidates in every mode: those of the lists, of the lists behind an evaluation (both paths) and,
+// in the rank mode, of the pre-pass and the rank kernel alike.
 ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice,
                           const ScorerRequest& rq, int num_cus, hipStream_t stream, ScorerWorkspace& ws,
                           const CandidateFilter& F = {});

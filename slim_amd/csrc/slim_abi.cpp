@@ -176,11 +176,13 @@ int32_t Py_SLIM_Learn(slim_t* trnhandle, int32_t* ioptions, double* doptions,
   return SLIM_OK;
 }
 
-int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
-                        double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
-                        int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
-                        double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
-                        double* bestARAR) {
+// Py_SLIM_Mselect is this with no filter.  With one (slim_gpu_filter.h) every pair is evaluated under it, which
+// only the evaluation in HBM can do: where that is not to be had the call fails before the first solve.
+int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
+                                double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
+                                int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
+                                double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
+                                double* bestARAR, slimgpu_filter_t* filter) {
   const slim_csr_t* trn = as_csr(trnhandle);
   const slim_csr_t* tst = as_csr(tsthandle);
   if (!trn || !tst || !trn->rowptr || !tst->rowptr) return SLIM_ERROR_INPUT;
@@ -240,12 +242,12 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   if (resident && !(evr_env && std::atoi(evr_env) == 0)) {
     evalset = evalset_create(mat, tst, fmarker, ncols, 1, &nrcmds, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
                              &status);
-    if (!evalset && stride == 1) set_error("");
+    if (!evalset && stride == 1 && !filter) set_error("");
   } else if (may_reside && nrcmds > 128 && !(evr_env && std::atoi(evr_env) == 0)) {
     evalset = evalset_create_ranked(mat, tst, fmarker, ncols, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
                                     &status);
     ranked = resident = evalset != nullptr;
-    if (!evalset && stride == 1) set_error("");
+    if (!evalset && stride == 1 && !filter) set_error("");
   }
   if (stride > 1 && !evalset) {
     const std::string why = SLIMGPU_LastError();
@@ -258,6 +260,35 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
     matrix_free(mat);
     return SLIM_ERROR_INPUT;
   }
+  const HostFilter hflt = filter_host(filter);
+  if (filter) {  // (no silent evaluation on the raw catalogue)
+    const bool several = base.ngpus > 1 || (mat && !matrix_replicas(mat).empty());
+    int32_t mrows = 0, mcols = 0;
+    int64_t mnnz = 0;
+    if (mat) matrix_info(mat, &mrows, &mcols, &mnnz);
+    std::string why;
+    if (admm) why = "the ADMM solver leaves no model in HBM";
+    else if (several) why = "the grid runs on several GPUs";
+    else if (res_env && std::atoi(res_env) == 0) why = "SLIM_GPU_RESIDENT=0 keeps the models on the host";
+    else if (evr_env && std::atoi(evr_env) == 0) why = "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host";
+    else if (nrcmds < 1) why = "nrcmds is " + std::to_string(nrcmds);
+    else if (!evalset) {  // (a matrix with merged duplicates, ...)
+      why = SLIMGPU_LastError();
+      if (why.empty()) why = "the eval set could not be made";
+    }
+    else if (hflt.ncols != mcols)
+      why = "the filter was made for " + std::to_string(hflt.ncols) + " items, the resident models have " +
+            std::to_string(mcols);
+    if (!why.empty()) {
+      set_error("Py_SLIM_MselectFiltered: a filter needs the evaluation in HBM (cd on one GPU, SLIM_GPU_RESIDENT "
+                "and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs, a filter of the "
+                "models' width): " + why);
+      evalset_free(evalset);
+      std::free(fmarker);
+      matrix_free(mat);
+      return SLIM_ERROR_INPUT;
+    }
+  }
 
   std::printf("------------------------------------------------------------------\n");
   std::printf("SLIM, version %s (MI355X engine)\n", SLIM_VERSION);
@@ -268,6 +299,15 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
               tst->rowptr[tst->nrows]);
   std::printf("  optTol: %.2le, niters: %d\n", base.optTol, base.maxniters);
   if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
+  if (filter) {
+    int64_t allowed = hflt.ncols;
+    if (hflt.bits) {
+      allowed = 0;
+      for (int32_t k = 0; k < hflt.ncols; ++k) allowed += (hflt.bits[k >> 5] >> (k & 31)) & 1u;
+    }
+    std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)allowed, hflt.ncols,
+                (long long)(hflt.xptr ? hflt.xptr[hflt.xusers] : 0));
+  }
   std::printf("\nEstimating & evaluating models...\n\n");
 
   *bestHRHR = *bestARHR = *bestHRAR = *bestARAR = 0.0;
@@ -302,9 +342,9 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
           break;
         }
         model_nnz_now = (ssize_t)model_nnz(dmodel);
-        evaluated = evalset && (ranked ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev)
-                                       : model_evaluate(evalset, dmodel, 1, &ev)) == SLIM_OK;
-        if (!evaluated && stride > 1) {  // (no silent evaluation of everybody)
+        evaluated = evalset && (ranked ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev, filter)
+                                       : model_evaluate(evalset, dmodel, 1, &ev, filter)) == SLIM_OK;
+        if (!evaluated && (stride > 1 || filter)) {  // (no silent evaluation of everybody, or without the filter)
           rc = SLIM_ERROR;
           break;
         }
@@ -384,6 +424,15 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
   std::free(fmarker);
   matrix_free(mat);
   return rc;
+}
+
+int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
+                        double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
+                        int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
+                        double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
+                        double* bestARAR) {
+  return Py_SLIM_MselectFiltered(trnhandle, tsthandle, ioptions, doptions, arrayl1, arrayl2, nl1, nl2, bestl1HR,
+                                 bestl2HR, bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR, bestARAR, nullptr);
 }
 
 int32_t Py_SLIM_GetTopN(slim_t* model, int32_t nratings, int32_t* itemids, float* ratings,
@@ -625,6 +674,11 @@ void SLIMGPU_EvalSetFree(slimgpu_evalset_t** es) {
 
 int32_t SLIMGPU_ModelEvaluateAt(slimgpu_evalset_t* es, const slimgpu_model_t* model, int32_t ncutoffs,
                                 double* metrics, int32_t* nvalid) {
+  return SLIMGPU_ModelEvaluateAtFiltered(es, model, nullptr, ncutoffs, metrics, nvalid);
+}
+
+int32_t SLIMGPU_ModelEvaluateAtFiltered(slimgpu_evalset_t* es, const slimgpu_model_t* model, slimgpu_filter_t* filter,
+                                        int32_t ncutoffs, double* metrics, int32_t* nvalid) {
   set_error("");
   if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
   EvalResult ev[SLIMGPU_MAX_CUTOFFS];
@@ -632,7 +686,7 @@ int32_t SLIMGPU_ModelEvaluateAt(slimgpu_evalset_t* es, const slimgpu_model_t* mo
     set_error("SLIMGPU_ModelEvaluateAt: ncutoffs must be the eval set's number of list lengths");
     return SLIM_ERROR_INPUT;
   }
-  const int32_t rc = model_evaluate(es, model, ncutoffs, ev);
+  const int32_t rc = model_evaluate(es, model, ncutoffs, ev, filter);
   if (rc != SLIM_OK) return rc;
   for (int32_t k = 0; k < ncutoffs; ++k) {
     double* m = metrics + 4 * k;
@@ -677,12 +731,24 @@ int32_t SLIMGPU_ModelRanks(slimgpu_evalset_t* es, const slimgpu_model_t* model, 
   return model_ranks(es, model, ranks, scores);
 }
 
+int32_t SLIMGPU_ModelRanksFiltered(slimgpu_evalset_t* es, const slimgpu_model_t* model, slimgpu_filter_t* filter,
+                                   int32_t* ranks, float* scores) {
+  set_error("");
+  return model_ranks(es, model, ranks, scores, filter);
+}
+
 int32_t SLIMGPU_ModelEvaluateRanked(slimgpu_evalset_t* es, const slimgpu_model_t* model, int32_t ncutoffs,
                                     const int32_t* cutoffs, double* metrics, int32_t* nvalid) {
+  return SLIMGPU_ModelEvaluateRankedFiltered(es, model, nullptr, ncutoffs, cutoffs, metrics, nvalid);
+}
+
+int32_t SLIMGPU_ModelEvaluateRankedFiltered(slimgpu_evalset_t* es, const slimgpu_model_t* model,
+                                            slimgpu_filter_t* filter, int32_t ncutoffs, const int32_t* cutoffs,
+                                            double* metrics, int32_t* nvalid) {
   set_error("");
   if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
   EvalResult ev[SLIMGPU_MAX_RANK_CUTOFFS];
-  const int32_t rc = model_evaluate_ranked(es, model, ncutoffs, cutoffs, ev);
+  const int32_t rc = model_evaluate_ranked(es, model, ncutoffs, cutoffs, ev, filter);
   if (rc != SLIM_OK) return rc;
   for (int32_t k = 0; k < ncutoffs; ++k) {
     double* m = metrics + 4 * k;

@@ -208,7 +208,7 @@ void fill_common(ChunkArgs& T, const DeviceRowView& W, const HistoryView& H, con
   T.cw = C.plan.cw; T.nchunks = C.plan.nchunks; T.pos_bits = C.plan.pos_bits; T.wsplit = ws.split.get();
   T.wlast = W.nnz > 0 ? (uint32_t)(W.nnz - 1) : 0u;
 }
-// the filter of a lists call into the wave kernel's or a chunk kernel's arguments
+// the filter of a call into the wave kernel's, a chunk kernel's or the pre-pass's arguments
 void fill_filter(FilterArgs& A, const CandidateFilter& F) {
   A.bits = F.bits; A.xptr = F.xptr; A.xind = F.xind; A.xusers = F.xusers;
 }
@@ -262,6 +262,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
         fill_common(A, W, H, C, ws);
         A.tptr = ev->tptr; A.tind = ev->tind; A.fmarker = ev->fmarker; A.fm_ncols = ev->fm_ncols; A.terms = ev->terms;
         A.cut = ev->cut;
+        fill_filter(A.flt, F);
         launch_scorer(pick_kernel<TopNEvalArgs>(P), L, 64 * P.t2w, P.lds, stream, A);
       } else {
         TopN2Args A{};
@@ -294,15 +295,18 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
       if (rk.entries <= 0) break;  // (no test entry: nothing to rank)
       HIP_TRY(hipEventRecord(rk.pre0, stream));
       const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)H.nusers + 3) / 4, (int64_t)num_cus * 16));
+      FilterArgs FA;  // the pre-pass and the chunks decide candidacy by the same filter
+      fill_filter(FA, F);
       hipLaunchKernelGGL(k_test_keys, dim3(blocks), dim3(256), 0, stream, H.nusers, H.users, W.nrows, ncols, P.pos_bits,
                          W.d_ptr, W.d_ind, W.d_val, H.ptr, H.ind, H.val, rk.tptr, rk.tind, rk.tbase, ws.tkey.get(),
-                         ws.tscore.get());
+                         ws.tscore.get(), FA);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipEventRecord(rk.pre1, stream));
       TopNRankArgs A{};
       fill_common(A, W, H, C, ws);
       A.tptr = rk.tptr; A.tbase = rk.tbase;
       A.tkey = ws.tkey.get(); A.tscore = ws.tscore.get(); A.rank = ws.rank.get(); A.rscore = ws.rscore.get();
+      A.flt = FA;
       // a test row longer than the merge area holds keys for: one scoring pass per group of entries
       A.gsize = P.t2w * kT2MaxN;
       if (const char* e = std::getenv("SLIM_TOPN_RANK_GROUP")) {
@@ -323,7 +327,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
       fill_views(T, W, H, C, ws);
       T.score = ws.score.get(); T.disc = ws.disc.get();
       T.out_ids = ws.oid.get(); T.out_scores = ws.osc.get(); T.out_cnt = ws.ocnt.get();
-      if (lists) fill_filter(T.flt, F);
+      fill_filter(T.flt, F);
       launch_scorer(&topn_kernel, L, 64, lds, stream, T);
       if (ev)
         launch_user_terms(stream, num_cus, H.nusers, H.users, nrcmds, ev->cut, ws.oid.get(), ws.ocnt.get(), ev->tptr,

@@ -236,7 +236,7 @@ struct ChunkArgs {
   const uint32_t* wsplit;  // [nitems_rows][nchunks + 1]: offset in row i of the first id >= c * cw
   const int64_t* hptr; const int32_t* hind; const float* hval;
   int32_t* queue;
-  FilterArgs flt;  // (the evaluation and the rank mode pass none)
+  FilterArgs flt;  // every mode takes one: lists, the fused evaluation, ranks (with k_test_keys), long lists
 };
 struct TopN2Args : ChunkArgs {  // lists of up to 64 (topn_chunk_kernel)
   int32_t* out_ids = nullptr; float* out_scores = nullptr; int32_t* out_cnt = nullptr;
@@ -332,6 +332,12 @@ __global__ void k_row_split(int32_t nrows, int32_t nchunks, int32_t cw,
 // order, starting from 0.0f + the first, products and sums rounded separately -- the additions of `update`
 // in the same order.  The first history index that has t, and t's position in that row, form the key.  An
 // entry equal to a history item, outside [0, ncols) or never touched is no candidate (kNoCandidate, score 0).
+// Under a filter (F; inert when its pointers are null) so is an entry whose bit is clear in the bitmap or whose
+// id stands in the exclusion row of user u.  The row is taken as it is given -- no order, repeats -- so it is
+// walked lane-strided, one ballot per 64 entries; an id outside [0, ncols) never reaches the walk, and a user
+// >= xusers has no row (exclusion_row).  The filter is asked BEFORE the searches: a removed entry costs none,
+// and a surviving one receives exactly the additions it receives without a filter.  Both filter branches are
+// on kernel arguments.
 __global__ __launch_bounds__(256) void k_test_keys(int32_t nsel, const int32_t* __restrict__ users, int32_t wrows,
                                                    int32_t ncols, int32_t pos_bits, const int64_t* __restrict__ wptr,
                                                    const int32_t* __restrict__ wind, const float* __restrict__ wval,
@@ -339,7 +345,7 @@ __global__ __launch_bounds__(256) void k_test_keys(int32_t nsel, const int32_t* 
                                                    const float* __restrict__ hval, const int64_t* __restrict__ tptr,
                                                    const int32_t* __restrict__ tind, const int64_t* __restrict__ tbase,
                                                    unsigned long long* __restrict__ tkey,
-                                                   float* __restrict__ tscore) {
+                                                   float* __restrict__ tscore, const FilterArgs F) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -348,12 +354,20 @@ __global__ __launch_bounds__(256) void k_test_keys(int32_t nsel, const int32_t* 
     const int64_t h0 = hptr[u], h1 = hptr[u + 1];
     const int64_t t0 = tptr[u], t1 = tptr[u + 1];
     const int64_t out = tbase[q];
+    int64_t x0, x1;
+    exclusion_row(F, u, x0, x1);
     for (int64_t z = t0; z < t1; ++z) {
       const int32_t t = tind[z];
       unsigned long long key = kNoCandidate;
       float acc = 0.0f;
-      bool in_hist = false, touched = false;
+      bool in_hist = false, touched = false;  // in_hist: in the history, or removed by the filter
       if (t >= 0 && t < ncols) {
+        if (F.bits != nullptr) in_hist = !filter_allows(F.bits, t);
+        if (F.xptr != nullptr)
+          for (int64_t xb = x0; xb < x1 && !in_hist; xb += 64) {
+            const int64_t x = xb + lane;
+            in_hist = __ballot(x < x1 && F.xind[x] == t) != 0;
+          }
         for (int64_t hb = h0; hb < h1 && !in_hist; hb += 64) {
           const int64_t h = hb + lane;
           bool found = false, same = false;

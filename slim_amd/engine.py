@@ -218,7 +218,9 @@ def _wrap_rows(lib, M):
 class Evaluator(object):
     """The test set of a grid staged in HBM (SLIMGPU_EvalSetCreateAt): `evaluate(resident_model)` scores
     the model against the staged training matrix and brings down HR / ARHR only -- of the longest
-    lists; `evaluate_at(resident_model)` gives the figures of every list length, from the same pass."""
+    lists; `evaluate_at(resident_model)` gives the figures of every list length, from the same pass.
+    Every call takes filter=<ItemFilter> (DeviceMatrix.item_filter): the candidates are then the filter's, a
+    test entry it removes stays in the denominators and is a miss (rank 0, score 0); exclusion rows go by user id."""
 
     def __init__(self, lib, handle, matrix, cutoffs=(10,), indptr=None):
         self._lib = lib
@@ -227,7 +229,9 @@ class Evaluator(object):
         self.cutoffs = tuple(int(c) for c in cutoffs)
         self.indptr = indptr       # ranks(): where every position's test entries start
 
-    def evaluate(self, model):
+    def evaluate(self, model, filter=None):
+        if filter is not None:  # (the last row of the filtered call: the longest lists)
+            return {k: v for k, v in self.evaluate_at(model, filter=filter)[-1].items() if k != "nrcmds"}
         met = np.zeros(4, np.float64)
         nv = np.zeros(3, np.int32)
         st = self._lib.SLIMGPU_ModelEvaluate(self.handle, model.handle, met, nv)
@@ -236,42 +240,55 @@ class Evaluator(object):
         return {"hr": met[0], "hr_head": met[1], "hr_tail": met[2], "arhr": met[3],
                 "nvalid": int(nv[0]), "nvalid_head": int(nv[1]), "nvalid_tail": int(nv[2])}
 
-    def evaluate_at(self, model):
-        """SLIMGPU_ModelEvaluateAt: one dict per list length (evaluate()'s keys and "nrcmds")."""
+    def evaluate_at(self, model, filter=None):
+        """SLIMGPU_ModelEvaluateAt(Filtered): one dict per list length (evaluate()'s keys and "nrcmds")."""
         n = len(self.cutoffs)
         met = np.zeros(4 * n, np.float64)
         nv = np.zeros(3 * n, np.int32)
-        st = self._lib.SLIMGPU_ModelEvaluateAt(self.handle, model.handle, n, met, nv)
+        if filter is None:
+            st = self._lib.SLIMGPU_ModelEvaluateAt(self.handle, model.handle, n, met, nv)
+        else:
+            st = self._lib.SLIMGPU_ModelEvaluateAtFiltered(self.handle, model.handle, filter.handle, n, met, nv)
         if st != SLIM_OK:
-            raise RuntimeError("SLIMGPU_ModelEvaluateAt failed (%d): %s" % (st, _lib.last_error()))
+            raise RuntimeError("SLIMGPU_ModelEvaluateAt%s failed (%d): %s"
+                               % ("" if filter is None else "Filtered", st, _lib.last_error()))
         return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
 
-    def ranks(self, model, scores=False):
-        """SLIMGPU_ModelRanks: the rank of every test entry of the evaluated users among the user's candidates
+    def ranks(self, model, scores=False, filter=None):
+        """SLIMGPU_ModelRanks(Filtered): the rank of every test entry of the evaluated users among the user's candidates
         (1 = the head of every list; 0 = in no list of any length).  Returns (ranks, indptr[, scores]): the
         entries of position q are ranks[indptr[q]:indptr[q + 1]], in the order of the user's test row."""
         n = int(self._lib.SLIMGPU_EvalSetEntries(self.handle))
         rk = np.zeros(max(n, 1), np.int32)
         sc = np.zeros(max(n, 1), np.float32) if scores else None
-        st = self._lib.SLIMGPU_ModelRanks(self.handle, model.handle, rk.ctypes.data_as(C.c_void_p),
-                                          None if sc is None else sc.ctypes.data_as(C.c_void_p))
+        out = (rk.ctypes.data_as(C.c_void_p), None if sc is None else sc.ctypes.data_as(C.c_void_p))
+        if filter is None:
+            st = self._lib.SLIMGPU_ModelRanks(self.handle, model.handle, *out)
+        else:
+            st = self._lib.SLIMGPU_ModelRanksFiltered(self.handle, model.handle, filter.handle, *out)
         if st != SLIM_OK:
-            raise RuntimeError("SLIMGPU_ModelRanks failed (%d): %s" % (st, _lib.last_error()))
+            raise RuntimeError("SLIMGPU_ModelRanks%s failed (%d): %s"
+                               % ("" if filter is None else "Filtered", st, _lib.last_error()))
         return (rk[:n], self.indptr, sc[:n]) if scores else (rk[:n], self.indptr)
 
-    def evaluate_ranked(self, model, cutoffs):
-        """SLIMGPU_ModelEvaluateRanked: one dict per cutoff (evaluate_at()'s keys), at ANY list lengths
+    def evaluate_ranked(self, model, cutoffs, filter=None):
+        """SLIMGPU_ModelEvaluateRanked(Filtered): one dict per cutoff (evaluate_at()'s keys), at ANY list lengths
         (ascending, at most 32), from the ranks of the held-out items -- no list is formed."""
         cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
         n = cut.size
         met = np.zeros(4 * max(n, 1), np.float64)
         nv = np.zeros(3 * max(n, 1), np.int32)
-        st = self._lib.SLIMGPU_ModelEvaluateRanked(self.handle, model.handle, n, cut.ctypes.data_as(C.c_void_p),
-                                                   met, nv)
+        if filter is None:
+            st = self._lib.SLIMGPU_ModelEvaluateRanked(self.handle, model.handle, n, cut.ctypes.data_as(C.c_void_p),
+                                                       met, nv)
+        else:
+            st = self._lib.SLIMGPU_ModelEvaluateRankedFiltered(self.handle, model.handle, filter.handle, n,
+                                                               cut.ctypes.data_as(C.c_void_p), met, nv)
         if st != SLIM_OK:
-            raise RuntimeError("SLIMGPU_ModelEvaluateRanked failed (%d): %s" % (st, _lib.last_error()))
+            raise RuntimeError("SLIMGPU_ModelEvaluateRanked%s failed (%d): %s"
+                               % ("" if filter is None else "Filtered", st, _lib.last_error()))
         return [{"nrcmds": int(c), "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(cut)]
@@ -486,7 +503,8 @@ class DeviceMatrix(object):
         return Evaluator(self._lib, h, self, () if ranked else cut.tolist(), indptr)
 
     def item_filter(self, allowed=None, blocked=None, exclusions=None):
-        """SLIMGPU_FilterCreate over this matrix's items: an ItemFilter for ResidentModel.predict(filter=...).
+        """SLIMGPU_FilterCreate over this matrix's items: an ItemFilter for ResidentModel.predict(filter=...) and
+        for the Evaluator's calls.
         Pass at most one of allowed / blocked (item ids); exclusions: a scipy CSR over user rows."""
         return ItemFilter(self.ncols, allowed, blocked, exclusions, lib=self._lib)
 

@@ -233,6 +233,58 @@ class SLIMatrix(object):
 
 
 # ---------------------------------------------------------------------------
+# candidate filters (SLIM.predict, SLIM.mselect)
+# ---------------------------------------------------------------------------
+def _known_items(item2id, items, ncols):
+    """Dense ids (below ncols) of the original item ids that item2id knows; the others are dropped."""
+    known = []
+    is_dict = isinstance(item2id, dict)
+    for it in items:
+        if is_dict:
+            j = item2id.get(it, -1)
+        else:
+            j = int(it) if isinstance(it, numbers.Integral) and 0 <= it < len(item2id) else -1
+        if 0 <= j < ncols:
+            known.append(j)
+    return np.asarray(known, dtype=np.int32)
+
+
+def _candidate_filter(lib, item2id, nitems, ncols, data, allowed_items, blocked_items, exclude):
+    """An ItemFilter over `ncols` items: original ids through item2id (a model's map in predict, the training
+    matrix's in mselect), the rows of `exclude` put in the order of data's users."""
+    from .engine import ItemFilter
+    if allowed_items is not None and blocked_items is not None:
+        raise TypeError("Please provide at most one of allowed_items and blocked_items.")
+    allowed = None if allowed_items is None else _known_items(item2id, allowed_items, ncols)
+    blocked = None if blocked_items is None else _known_items(item2id, blocked_items, ncols)
+    rows = None
+    if exclude is not None:
+        assert type(exclude) == SLIMatrix, "exclude must be a SLIMatrix object."
+        assert exclude.nItems == nitems, "The shape of exclude should match the model."
+        nnz = C.c_int(0)
+        lib.Py_csr_stat(exclude.handle, C.byref(nnz))
+        ptr = np.zeros(exclude.nUsers + 1, dtype=np.int32)
+        ind = np.zeros(max(nnz.value, 1), dtype=np.int32)
+        val = np.ones(max(nnz.value, 1), dtype=np.float32)
+        lib.Py_csr_export(exclude.handle, ptr, ind, val)
+        if isinstance(data.user2id, dict):
+            xdict = isinstance(exclude.user2id, dict)
+            src = [exclude.user2id.get(k, -1) if xdict else (k if 0 <= k < exclude.nUsers else -1)
+                   for k in data.user2id]   # (dense ids ascend in insertion order)
+        else:
+            src = [u if u < exclude.nUsers else -1 for u in range(data.nUsers)]
+        xptr, xind = [0], []
+        for r in src:
+            if r >= 0:
+                row = ind[ptr[r]:ptr[r + 1]]
+                xind.extend(row[row < ncols].tolist())
+            xptr.append(len(xind))
+        rows = sp.csr_matrix((np.ones(len(xind), np.float32), np.asarray(xind, np.int32),
+                              np.asarray(xptr, np.int64)), shape=(len(src), max(ncols, 1)))
+    return ItemFilter(ncols, allowed, blocked, rows, lib=lib)
+
+
+# ---------------------------------------------------------------------------
 # SLIM
 # ---------------------------------------------------------------------------
 class SLIM(object):
@@ -271,9 +323,16 @@ class SLIM(object):
                                % _lib.last_error())
         print("Learning takes %.3f secs." % elapsed)
 
-    def mselect(self, params, trndata, tstdata, arrayl1, arrayl2, nrcmds):
+    def mselect(self, params, trndata, tstdata, arrayl1, arrayl2, nrcmds, allowed_items=None, blocked_items=None,
+                exclude=None):
+        """allowed_items / blocked_items / exclude: evaluate every pair under a candidate filter, with the rules
+        of predict() -- ORIGINAL item ids through trndata's maps, at most one of allowed and blocked, unknown ids
+        ignored, exclude a SLIMatrix whose rows are put in the order of trndata's users.  A held-out item the
+        filter removes counts as a miss.  (An engine extension; it needs the evaluation in HBM.)"""
         assert type(trndata) == SLIMatrix, "trndata must be a SLIMatrix object."
         assert type(tstdata) == SLIMatrix, "tstdata must be a SLIMatrix object."
+        if allowed_items is not None and blocked_items is not None:
+            raise TypeError("Please provide at most one of allowed_items and blocked_items.")
         assert type(arrayl1) in [list, np.ndarray], "Please provide a list of l1 values."
         assert type(arrayl2) in [list, np.ndarray], "Please provide a list of l2 values."
         view = _prepare(params)
@@ -284,12 +343,21 @@ class SLIM(object):
         if len(arrayl2) < 1:
             raise TypeError("The l2 array must not be empty.")
         best = [C.c_double(0.0) for _ in range(8)]
+        grid = (trndata.handle, tstdata.handle, iopt, dopt,
+                np.ascontiguousarray(np.sort(arrayl1), dtype=np.float64),
+                np.ascontiguousarray(np.sort(arrayl2), dtype=np.float64),
+                len(arrayl1), len(arrayl2)) + tuple(C.byref(b) for b in best)
         t0 = time.time()
-        rc = self._lib.Py_SLIM_Mselect(
-            trndata.handle, tstdata.handle, iopt, dopt,
-            np.ascontiguousarray(np.sort(arrayl1), dtype=np.float64),
-            np.ascontiguousarray(np.sort(arrayl2), dtype=np.float64),
-            len(arrayl1), len(arrayl2), *[C.byref(b) for b in best])
+        if allowed_items is None and blocked_items is None and exclude is None:
+            rc = self._lib.Py_SLIM_Mselect(*grid)
+        else:   # the models of the grid are as wide as the staged training matrix: its largest item id + 1
+            ncols = max(int(C.cast(trndata.handle, C.POINTER(_lib.CsrView)).contents.ncols), 1)
+            flt = _candidate_filter(self._lib, trndata.item2id, trndata.nItems, ncols, trndata, allowed_items,
+                                    blocked_items, exclude)
+            try:
+                rc = self._lib.Py_SLIM_MselectFiltered(*(grid + (flt.handle,)))
+            finally:
+                flt.close()
         elapsed = time.time() - t0
         l1hr, l2hr, hrhr, arhr, l1ar, l2ar, hrar, arar = [b.value for b in best]
         if rc != SLIM_OK:
@@ -304,53 +372,12 @@ class SLIM(object):
         self.mselect_result = dict(bestHR=(l1hr, l2hr, hrhr, arhr), bestAR=(l1ar, l2ar, hrar, arar))
 
     # -- prediction ----------------------------------------------------------
-    def _known_items(self, items, ncols):
-        """Dense ids (below ncols) of the original item ids the model knows; the others are dropped."""
-        known = []
-        is_dict = isinstance(self.item2id, dict)
-        for it in items:
-            if is_dict:
-                j = self.item2id.get(it, -1)
-            else:
-                j = int(it) if isinstance(it, numbers.Integral) and 0 <= it < len(self.item2id) else -1
-            if 0 <= j < ncols:
-                known.append(j)
-        return np.asarray(known, dtype=np.int32)
-
     def _candidate_filter(self, data, allowed_items, blocked_items, exclude):
         """The ItemFilter of predict(): original ids through the model's item map, the rows of `exclude` put in
         the order of data's users."""
-        from .engine import ItemFilter
-        if allowed_items is not None and blocked_items is not None:
-            raise TypeError("Please provide at most one of allowed_items and blocked_items.")
         ncols = int(C.cast(self.handle, C.POINTER(_lib.CsrView)).contents.ncols)
-        allowed = None if allowed_items is None else self._known_items(allowed_items, ncols)
-        blocked = None if blocked_items is None else self._known_items(blocked_items, ncols)
-        rows = None
-        if exclude is not None:
-            assert type(exclude) == SLIMatrix, "exclude must be a SLIMatrix object."
-            assert exclude.nItems == self.nItems, "The shape of exclude should match the model."
-            nnz = C.c_int(0)
-            self._lib.Py_csr_stat(exclude.handle, C.byref(nnz))
-            ptr = np.zeros(exclude.nUsers + 1, dtype=np.int32)
-            ind = np.zeros(max(nnz.value, 1), dtype=np.int32)
-            val = np.ones(max(nnz.value, 1), dtype=np.float32)
-            self._lib.Py_csr_export(exclude.handle, ptr, ind, val)
-            if isinstance(data.user2id, dict):
-                xdict = isinstance(exclude.user2id, dict)
-                src = [exclude.user2id.get(k, -1) if xdict else (k if 0 <= k < exclude.nUsers else -1)
-                       for k in data.user2id]   # (dense ids ascend in insertion order)
-            else:
-                src = [u if u < exclude.nUsers else -1 for u in range(data.nUsers)]
-            xptr, xind = [0], []
-            for r in src:
-                if r >= 0:
-                    row = ind[ptr[r]:ptr[r + 1]]
-                    xind.extend(row[row < ncols].tolist())
-                xptr.append(len(xind))
-            rows = sp.csr_matrix((np.ones(len(xind), np.float32), np.asarray(xind, np.int32),
-                                  np.asarray(xptr, np.int64)), shape=(len(src), max(ncols, 1)))
-        return ItemFilter(ncols, allowed, blocked, rows, lib=self._lib)
+        return _candidate_filter(self._lib, self.item2id, self.nItems, ncols, data, allowed_items, blocked_items,
+                                 exclude)
 
     def predict(self, data, nrcmds=10, outfile=None, negitems=None, nnegs=0, returnscores=False,
                 allowed_items=None, blocked_items=None, exclude=None):
