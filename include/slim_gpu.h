@@ -313,5 +313,7 @@ const char *SLIMGPU_LastError(void);
 #include "slim_gpu_lists.h"
 /* Candidate filters for those lists: item allow / block sets, per-user exclusions. */
 #include "slim_gpu_filter.h"
+/* Per-user candidate sets scored and ordered on the device: the 1-vs-k protocol at any k. */
+#include "slim_gpu_cand.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

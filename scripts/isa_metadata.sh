@@ -3,8 +3,8 @@
 # dominant one (cross-compiled here, no GPU needed):  bash scripts/isa_metadata.sh > profiles/rNN/isa_metadata.txt
 #
 # bash scripts/isa_metadata.sh topn [path/to/topn.hip]: the same figures of every instantiation of the top-N
-# scorers (topn_chunk_kernel / topn_chunk_eval_kernel / topn_chunk_rank_kernel / topn_chunk_long_kernel <NW, KeyT>; y = 32-bit keys,
-# j = 64-bit keys) -- of this tree's topn.hip (which instantiates the kernels of topn_kernels.hpp), or of another
+# scorers (topn_chunk_kernel / topn_chunk_eval_kernel / topn_chunk_rank_kernel / topn_chunk_long_kernel /
+# topn_chunk_cand_kernel <NW, KeyT>; y = 32-bit keys, j = 64-bit keys; and topn_kernel, k_test_keys, k_cand_lists) -- of this tree's topn.hip (which instantiates the kernels of topn_kernels.hpp), or of another
 # revision's copied into slim_amd/csrc under another name (it needs the tree's headers)
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
@@ -14,7 +14,7 @@ if [ "$1" = "topn" ]; then
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics --cuda-device-only -I$R/slim_amd/csrc \
     -Rpass-analysis=kernel-resource-usage -c -o $T/x.o -x hip $SRC 2>&1 |
   grep -E "Function Name|VGPRs:|TotalSGPRs|VGPRs Spill|SGPRs Spill|ScratchSize|LDS Size" | sed 's/.*remark: *//;s/ \[-Rpass.*//' |
-  awk '/Function Name/{if (n) print n, v; n=$3; v=""; next} {v=v" | "$0} END{print n, v}' | grep "topn_" |
+  awk '/Function Name/{if (n) print n, v; n=$3; v=""; next} {v=v" | "$0} END{print n, v}' | grep -E "topn_|k_test_keys|k_cand_lists" |
   sed 's/_ZN7slimamd[0-9]*_GLOBAL__N_1[0-9]*//;s/_ZN7slimamd[0-9]*//;s/ILi\([0-9]*\)E\([yj]\)EEvNS[0-9_]*[A-Za-z0-9]*E/<\1,\2>/' | sort
   rm -rf $T
   exit 0

@@ -231,6 +231,22 @@ _FILTERED_EVAL_SIGNATURES = {
 
 FILTERED_EVAL_SYMBOLS = tuple(_FILTERED_EVAL_SIGNATURES)
 
+# per-user candidate sets scored and ordered on the device (include/slim_gpu_cand.h); slot_scores / output / scores /
+# counts / users are passed as pointers (any may be None)
+_CAND_SIGNATURES = {
+    "SLIMGPU_CandSetCreate": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "SLIMGPU_CandSetFree": (None, [C.c_void_p]),
+    "SLIMGPU_ScoreCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "SLIMGPU_MatrixScoreCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_ModelEvaluateCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, f64_1d, i32_1d]),
+    "Py_SLIM_ScoreCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+}
+
+CAND_SYMBOLS = tuple(_CAND_SIGNATURES)
+
 _lib = None
 
 
@@ -247,7 +263,8 @@ def load():
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EVAL_SIGNATURES.items()) +
                               list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
                               list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
-                              list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items())):
+                              list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
+                              list(_CAND_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

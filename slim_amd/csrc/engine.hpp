@@ -149,6 +149,25 @@ void filter_free(slimgpu_filter* f);
 HostFilter filter_host(const slimgpu_filter* f);
 // SLIM_OK, or SLIM_ERROR_INPUT with "<who>: ..." as the error text when f was made for another number of items
 int32_t filter_check(const char* who, const slimgpu_filter* f, int32_t model_ncols);
+// candidates.hip: the candidate set object (slim_gpu_cand.h) -- validated once, its host description (host_csr.hpp:
+// HostCandSet) and the device copy that candset_on_device (scorer.hpp) makes on first use -- and the calls that score
+// its rows on a device: host model and host histories (every row of trn), or a resident model and rows of the staged
+// matrix.  slot_scores may be null; nrcmds == 0: no lists.  SLIM_ERROR_INPUT with the outputs untouched where the
+// set does not fit the call or the chunk scorer cannot serve.
+struct HostCandSet;
+slimgpu_candset* candset_create(int32_t ncols, int32_t nusers, const int64_t* cptr, const int32_t* cind,
+                                int32_t* status);
+void candset_free(slimgpu_candset* cs);
+HostCandSet candset_host(const slimgpu_candset* cs);
+// what every call checks of its set before anything is written: the model's width, a row for every selected user
+// (users: ascending, nullptr: users [0, nsel)), the list arguments, and for lists rows of at most SLIMGPU_MAX_LIST
+int32_t candset_check(const char* who, const slimgpu_candset* cs, int32_t model_ncols, int32_t nsel,
+                      const int32_t* users, int32_t nrcmds, const int32_t* output, const float* scores);
+int32_t score_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_candset* cs, int32_t nrcmds,
+                         float* slot_scores, int32_t* output, float* scores, int32_t* counts);
+int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs, int32_t nusers,
+                                const int32_t* users, int32_t nrcmds, float* slot_scores, int32_t* output,
+                                float* scores, int32_t* counts);
 slimgpu_list_stats_t& last_list_stats();
 int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out);
 // the CSR of a staged matrix where it lies (the history of the resident scorer)
@@ -188,6 +207,10 @@ void evalset_free(slimgpu_evalset_t* es);
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es);
 int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out,
                        slimgpu_filter* filter = nullptr);
+// slim_gpu_cand.h: the figures of the candidate lists (score descending, then slot) of the eval set's users at its
+// cutoffs; a set of another ncols, with too few rows or with a selected row above SLIMGPU_MAX_LIST is refused
+int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_candset* cs,
+                                  int32_t ncutoffs, EvalResult* out);
 int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t* output,
                        float* scores);
 // users[nusers]: the rows scored, ascending (nullptr and 0: every row); counts may be null

@@ -280,6 +280,38 @@ int32_t top_n_1vsk(const slim_csr_t* W, int32_t nratings, const int32_t* itemids
   return emit_best(nnegs, nrcmds, key, val, rids, rscores);
 }
 
+void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nrcmds,
+                           float* slot_scores, int32_t* output, float* scores, int32_t* counts) {
+  const int32_t ncols = W->ncols, nrows = W->nrows;
+  std::vector<int32_t> slot_of(ncols, -2);  // -2: not a candidate
+  std::vector<float> key;
+  std::vector<int32_t> val;
+  for (int32_t u = 0; u < trn->nrows; ++u) {
+    const int32_t* cand = S.cind + S.cptr[u];
+    const int32_t len = (int32_t)(S.cptr[u + 1] - S.cptr[u]);
+    key.assign(len, 0.0f);
+    val.assign(cand, cand + len);
+    for (int32_t c = 0; c < len; ++c)
+      if (cand[c] >= 0 && cand[c] < ncols) slot_of[cand[c]] = c;  // (a repeated id: the last occurrence)
+    for (ssize_t h = trn->rowptr[u]; h < trn->rowptr[u + 1]; ++h) {
+      const int32_t i = trn->rowind[h];
+      if (i < 0 || i >= nrows) continue;
+      const float rating = trn->rowval ? trn->rowval[h] : 1.0f;
+      for (ssize_t j = W->rowptr[i]; j < W->rowptr[i + 1]; ++j) {
+        const int32_t s = slot_of[W->rowind[j]];
+        if (s >= 0) key[s] += rating * W->rowval[j];
+      }
+    }
+    for (int32_t c = 0; c < len; ++c)
+      if (cand[c] >= 0 && cand[c] < ncols) slot_of[cand[c]] = -2;
+    if (slot_scores) std::copy(key.begin(), key.end(), slot_scores + S.cptr[u]);
+    if (nrcmds > 0) {
+      const int32_t n = emit_best(len, nrcmds, key, val, output + (ssize_t)u * nrcmds, scores + (ssize_t)u * nrcmds);
+      if (counts) counts[u] = n;
+    }
+  }
+}
+
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,
                          const int32_t* rowind) {
   int32_t* mark = xmalloc<int32_t>(ncols);

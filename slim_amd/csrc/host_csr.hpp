@@ -74,6 +74,18 @@ int32_t top_n_1vsk(const slim_csr_t* W, int32_t nratings, const int32_t* itemids
                    const float* ratings, int32_t nrcmds, int32_t* rids,
                    float* rscores, int32_t nnegs, const int32_t* negitems);
 
+// A candidate set (slim_gpu_cand.h) as the host scorer reads it: a CSR over user ids, ids as given.
+struct HostCandSet {
+  int32_t ncols = 0, nusers = 0;
+  const int64_t* cptr = nullptr;
+  const int32_t* cind = nullptr;
+};
+// top_n_1vsk's loop over the candidate rows of the users [0, trn->nrows): slot_scores (optional) laid out like
+// the set, lists (nrcmds > 0) of min(nrcmds, row length) into output / scores [user][nrcmds], counts optional.
+// The ncols-long slot table is made once per call and restored after each user.
+void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nrcmds,
+                           float* slot_scores, int32_t* output, float* scores, int32_t* counts);
+
 // api.c:215-245.  malloc'd marker array (0 head / 1 tail).
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,
                          const int32_t* rowind);

@@ -29,6 +29,7 @@ struct slimgpu_evalset {
   int64_t max_hist = 0;      // the longest of those histories
   slimamd::StagedCsr tst;  // the test rows of the matrix's users (ids only)
   slimamd::DeviceBuffer<int32_t> d_fm, d_users;
+  std::vector<int32_t> h_users;  // the listed users on the host: a candidate set's rows are checked against them
   slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;  // [cut.n][nsel]
   slimamd::DeviceBuffer<unsigned long long> d_out;    // EvalOut
   slimamd::ScorerWorkspace ws;
@@ -58,6 +59,8 @@ struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoff
   EvalSums sums[SLIMGPU_MAX_RANK_CUTOFFS];
 };
 
+}  // namespace
+
 // the matrix and the model of one call: one device, one width, rows that are the caller's
 int32_t check_pair(const char* who, const DeviceCsrView& R, const DeviceRowView& W) {
   if (R.merged)
@@ -86,6 +89,7 @@ int32_t check_user_list(const char* who, int32_t nusers, const int32_t* users, i
   return SLIM_ERROR_INPUT;
 }
 
+namespace {
 HistoryView history_of(const DeviceCsrView& R, const slimgpu_evalset* es) {
   return resident_history(R, es->nsel, es->listed ? es->d_users.get() : nullptr, es->max_hist);
 }
@@ -141,6 +145,7 @@ slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* 
       HIP_TRY(hipMemcpyAsync(es->d_fm.get(), fmarker, sizeof(int32_t) * (size_t)fm_ncols, hipMemcpyHostToDevice, stream));
     if (users) {  // (pageable source: the copy has left the caller's array when the call returns)
       es->d_users = DeviceBuffer<int32_t>((size_t)nsel);
+      es->h_users.assign(users, users + nsel);
       HIP_TRY(hipMemcpyAsync(es->d_users.get(), users, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
     }
     // the test entries of the evaluated users, the longest of their test rows and, for listed users, where
@@ -292,6 +297,49 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
       st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
       launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
     }
+    finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure(who, e);
+  }
+}
+
+// The evaluation of candidate lists (slim_gpu_cand.h): the scorer writes the slot scores of the users' candidate
+// rows, k_cand_lists orders every row and keeps the first cut.c[cut.n - 1], and the wave path's epilogue -- k_user_terms
+// on lists and counts, then k_sum_in_user_order -- forms the figures.  A row shorter than a cutoff gives a list
+// of its own length.
+int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_candset* cs,
+                                  int32_t ncutoffs, EvalResult* out) {
+  const char* who = "SLIMGPU_ModelEvaluateCandidates";
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (const int32_t rc = check_evaluation(who, out != nullptr, es, model, &ncutoffs, W, R); rc != SLIM_OK) return rc;
+  const int32_t ncut = es->cut.n, nrcmds = es->cut.c[ncut - 1];
+  const int32_t* h_users = es->listed ? es->h_users.data() : nullptr;
+  static const int32_t lists_wanted = 0;  // (the lists stay on the device: any non-null address serves the check)
+  static const float scores_wanted = 0;
+  if (const int32_t rc = candset_check(who, cs, W.ncols, es->nsel, h_users, nrcmds, &lists_wanted, &scores_wanted);
+      rc != SLIM_OK)
+    return rc;
+  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    es->ws.allocs = 0;
+    const HistoryView H = history_of(R, es);
+    if (es->nsel > 0) {
+      const CandidateRows rows = candset_on_device(cs, R.device, R.num_cus, stream, &es->ws.allocs, &st.h2d_bytes);
+      HIP_TRY(hipEventRecord(es->ev0, stream));
+      st.path = queue_candidates(W, H, rows, nrcmds, R.num_cus, stream, es->ws);
+      if (st.path == kRefused) return refuse(std::string(who) + ": " + last_error());
+      launch_user_terms(stream, R.num_cus, es->nsel, H.users, nrcmds, es->cut, es->ws.oid.get(), es->ws.ocnt.get(),
+                        es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get());
+      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+    }
+    st.path = kCand;
     finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
     return SLIM_OK;
   } catch (const HipFail& e) {

@@ -25,6 +25,7 @@ struct ScorerWorkspace {
   // long lists: one slab of ncols (image, key, id) records per workgroup; the counters of slimgpu_list_stats_t
   DeviceBuffer<uint4> slab;
   DeviceBuffer<unsigned long long> lstats;
+  DeviceBuffer<float> cand;                // candidate rows: the slot scores, laid out like the set
   int allocs = 0;                          // device allocations since the caller last cleared it
   template <class T>
   T* need(DeviceBuffer<T>& b, size_t n) {
@@ -61,7 +62,7 @@ struct CandidateFilter {
 CandidateFilter filter_on_device(slimgpu_filter* f, int device, hipStream_t stream, int* allocs,
                                  int64_t* h2d = nullptr);
 
-// What a caller wants, one of four.  Lists of up to 128 into ws.oid / osc / ocnt; the same of up to
+// What a caller wants, one of five.  Lists of up to 128 into ws.oid / osc / ocnt; the same of up to
 // SLIMGPU_MAX_LIST (ws.lstats is the caller's to provide and to clear: it adds up over the slices of one call);
 struct ListsRequest { int32_t nrcmds; };
 struct LongListsRequest { int32_t nrcmds; };
@@ -78,7 +79,24 @@ struct RankTargets {  // ranks and scores of the positions' test entries into ws
   int64_t max_test;        // the longest test row among them
   hipEvent_t pre0, pre1;   // around the pre-pass (k_test_keys)
 };
-using ScorerRequest = std::variant<ListsRequest, LongListsRequest, EvalTargets, RankTargets>;
+// A candidate set (slim_gpu_cand.h) where the scorer runs.  cptr / cind: the rows as given, a CSR over user ids with
+// nrows rows and `entries` entries; lptr / pairs: per row the live entries -- inside [0, ncols), of a repeated id
+// the last -- ascending by id, as (id, slot in the row).
+struct CandidateRows {
+  const int64_t* cptr = nullptr; const int32_t* cind = nullptr;
+  const int64_t* lptr = nullptr; const int2* pairs = nullptr;
+  int32_t nrows = 0;
+  int64_t entries = 0;
+};
+// The device copy of `cs` on the current device, `device`: made on `stream` on the first use there (the rows
+// uploaded, the device form made by the stable radix sort; the stream is drained once) and kept until the set is
+// freed.  *allocs grows by the device allocations this made, *h2d (optional) by the bytes it sent.
+CandidateRows candset_on_device(slimgpu_candset* cs, int device, int num_cus, hipStream_t stream, int* allocs,
+                                int64_t* h2d = nullptr);
+struct CandTargets {  // the slot scores of the positions' candidate rows into ws.cand (cleared first, whole)
+  CandidateRows rows;
+};
+using ScorerRequest = std::variant<ListsRequest, LongListsRequest, EvalTargets, RankTargets, CandTargets>;
 
 // Which kernel serves.  The values are those of slimgpu_eval_stats_t::path and slimgpu_list_stats_t::path.
 enum ScorerPath : int {
@@ -87,6 +105,7 @@ enum ScorerPath : int {
   kWave = 2,     // the wave kernel (k_user_terms behind it for an evaluation)
   kRank = 3,     // the chunk kernel in rank mode
   kLong = 4,     // the chunk kernel's long-list form
+  kCand = 5,     // the chunk kernel scoring candidate rows (slim_gpu_cand.h)
 };
 struct ChunkPlan {  // geometry of the chunk kernel for a model / history pair: key width, chunk width, LDS
   bool key32 = false;
@@ -112,7 +131,7 @@ struct ScorerLaunch {  // how queue_scorer served a call
 };
 // Queues on `stream` what `rq` asks for, on the path of `choice` (choose_scorer's for this W, H and rq).
 // F narrows the candidates in every mode: those of the lists, of the lists behind an evaluation (both paths) and,
-// in the rank mode, of the pre-pass and the rank kernel alike.
+// in the rank mode, of the pre-pass and the rank kernel alike.  Candidate rows (CandTargets) take no filter.
 ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice,
                           const ScorerRequest& rq, int num_cus, hipStream_t stream, ScorerWorkspace& ws,
                           const CandidateFilter& F = {});
@@ -130,6 +149,21 @@ size_t fetch_lists(const ScorerWorkspace& ws, int32_t nusers, int32_t nrcmds, hi
 ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice, int num_cus,
                        hipStream_t stream, ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts,
                        size_t* down, const CandidateFilter& F = {});
+// resident_eval.hip: what the calls on a staged matrix check of their arguments.  The matrix and the model of one
+// call: one device, one width, rows that are the caller's.  A list of users: at least one, without a list nusers
+// is 0 (nrows < 0: no more); rows of [0, nrows), ascending.  SLIM_OK, or SLIM_ERROR_INPUT with "<who>: ...".
+int32_t check_pair(const char* who, const DeviceCsrView& R, const DeviceRowView& W);
+int32_t check_user_list(const char* who, int32_t nusers, const int32_t* users, int32_t nrows);
+// Brings down the slot scores (ws.cand) of the rows of the users at `nsel` positions (users: host, ascending;
+// nullptr: users [0, nsel)) into slot_scores, which is laid out like the set; drains `stream`.  Returns the bytes.
+size_t fetch_slot_scores(const ScorerWorkspace& ws, const slimgpu_candset* cs, int32_t nsel, const int32_t* users,
+                         hipStream_t stream, float* slot_scores);
+// Candidate rows (slim_gpu_cand.h): queues on `stream` the slot scores of the rows of H's users into ws.cand and,
+// for nrcmds > 0, their lists (score descending, then slot ascending) into ws.oid / osc / ocnt -- every selected
+// row is then at most SLIMGPU_MAX_LIST long, the caller has checked.  Returns kCand, or kRefused (set_error says
+// why) with nothing queued.
+ScorerPath queue_candidates(const DeviceRowView& W, const HistoryView& H, const CandidateRows& rows, int32_t nrcmds,
+                            int num_cus, hipStream_t stream, ScorerWorkspace& ws);
 // The entries of the longest row among the rows at `nsel` positions of a CSR (d_users == nullptr: rows [0, nsel))
 // and, when `entries` is given, of all of them: one kernel on `stream`, 4 (16) bytes down, the stream drained.
 int64_t longest_history(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* d_users, const int64_t* d_ptr,

@@ -501,9 +501,24 @@ int32_t Py_SLIM_Predict_1vsk(int32_t nrcmds, int32_t nnegs, slim_t* slimhandle,
   const slim_csr_t* trn = as_csr(trnhandle);
   if (!W || !trn || !W->rowptr || !trn->rowptr || nrcmds < 0 || nnegs < 0) return SLIM_ERROR;
   const int policy = predict_policy();
-  if (policy == 2 || (policy == 1 && nrcmds >= 1 && nnegs >= 1 && nnegs <= 1024 &&
+  // up to 1024 candidates the 1-vs-k kernel serves; above that, and at every nnegs under SLIM_1VSK_KERNEL=chunk,
+  // the chunk scorer does through a candidate set with an implicit row pointer (slim_gpu_cand.h): the same
+  // results bit for bit
+  const char* kenv = std::getenv("SLIM_1VSK_KERNEL");
+  const bool chunk = nrcmds >= 1 && nnegs >= 1 && negitems && (nnegs > 1024 || (kenv && std::strcmp(kenv, "chunk") == 0));
+  if (policy == 2 || (policy == 1 && nrcmds >= 1 && nnegs >= 1 && (nnegs <= 1024 || chunk) &&
                       trn->nrows > 0 && device_count() > 0)) {
-    const int32_t rc = predict_1vsk_device(W, trn, nrcmds, nnegs, negitems, output, scores);
+    int32_t rc;
+    if (chunk) {
+      set_error("");
+      std::vector<int64_t> cptr((size_t)std::max(trn->nrows, 0) + 1);
+      for (size_t u = 0; u < cptr.size(); ++u) cptr[u] = (int64_t)u * nnegs;
+      slimgpu_candset_t* cs = candset_create(W->ncols, std::max(trn->nrows, 0), cptr.data(), negitems, &rc);
+      if (cs) rc = score_candidates(W, trn, cs, nrcmds, nullptr, output, scores, nullptr);
+      candset_free(cs);
+    } else {
+      rc = predict_1vsk_device(W, trn, nrcmds, nnegs, negitems, output, scores);
+    }
     if (rc == SLIM_OK || policy == 2) return rc;  // (unsorted model rows etc.: host scorer)
   }
   std::vector<int32_t> rids(nrcmds);
@@ -871,6 +886,77 @@ int32_t Py_SLIM_PredictFiltered(int32_t nrcmds, slim_t* slimhandle, slim_t* trnh
     }
   }
   return trn->nrows > 0 ? SLIM_OK : SLIM_ERROR;
+}
+
+// ----------------------------------------------------- slim_gpu_cand.h ------
+
+int32_t SLIMGPU_CandSetCreate(int32_t ncols, int32_t nusers, const int64_t* cptr, const int32_t* cind,
+                              slimgpu_candset_t** out) {
+  set_error("");
+  if (!out) {
+    set_error("SLIMGPU_CandSetCreate: bad arguments (out is NULL)");
+    return SLIM_ERROR_INPUT;
+  }
+  int32_t status = SLIM_ERROR;
+  *out = candset_create(ncols, nusers, cptr, cind, &status);
+  return status;
+}
+
+void SLIMGPU_CandSetFree(slimgpu_candset_t* cs) { candset_free(cs); }
+
+int32_t SLIMGPU_ScoreCandidates(slim_t* model, slim_t* trn, slimgpu_candset_t* cs, int32_t nrcmds, float* slot_scores,
+                                int32_t* output, float* scores, int32_t* counts) {
+  set_error("");
+  return score_candidates(as_csr(model), as_csr(trn), cs, nrcmds, slot_scores, output, scores, counts);
+}
+
+int32_t SLIMGPU_MatrixScoreCandidates(const slimgpu_model_t* model, slimgpu_matrix_t* mat, slimgpu_candset_t* cs,
+                                      int32_t nusers, const int32_t* users, int32_t nrcmds, float* slot_scores,
+                                      int32_t* output, float* scores, int32_t* counts) {
+  set_error("");
+  return matrix_score_candidates(model, mat, cs, nusers, users, nrcmds, slot_scores, output, scores, counts);
+}
+
+int32_t SLIMGPU_ModelEvaluateCandidates(slimgpu_evalset_t* es, const slimgpu_model_t* model, slimgpu_candset_t* cs,
+                                        int32_t ncutoffs, double* metrics, int32_t* nvalid) {
+  set_error("");
+  if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
+  EvalResult ev[SLIMGPU_MAX_CUTOFFS];
+  if (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS) {
+    set_error("SLIMGPU_ModelEvaluateCandidates: ncutoffs must be the eval set's number of list lengths");
+    return SLIM_ERROR_INPUT;
+  }
+  const int32_t rc = model_evaluate_candidates(es, model, cs, ncutoffs, ev);
+  if (rc != SLIM_OK) return rc;
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    double* m = metrics + 4 * k;
+    int32_t* n = nvalid + 3 * k;
+    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
+    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
+  }
+  return SLIM_OK;
+}
+
+// the policy of Py_SLIM_Predict: the device scorer under gpu and, with a device, under auto; the host loop under
+// cpu and, under auto, where the device refuses.  Both give the same scores and lists.
+int32_t Py_SLIM_ScoreCandidates(slim_t* model, slim_t* trnhandle, slimgpu_candset_t* cs, int32_t nrcmds,
+                                float* slot_scores, int32_t* output, float* scores, int32_t* counts) {
+  const slim_csr_t* W = as_csr(model);
+  const slim_csr_t* trn = as_csr(trnhandle);
+  if (!W || !trn || !W->rowptr || !trn->rowptr) return SLIM_ERROR;
+  set_error("");
+  if (const int32_t rc = candset_check("Py_SLIM_ScoreCandidates", cs, W->ncols, trn->nrows, nullptr, nrcmds, output,
+                                       scores);
+      rc != SLIM_OK)
+    return rc;
+  const int policy = predict_policy();
+  if (policy == 2 || (policy == 1 && trn->nrows > 0 && device_count() > 0)) {
+    const int32_t rc = score_candidates(W, trn, cs, nrcmds, slot_scores, output, scores, counts);
+    if (rc == SLIM_OK || policy == 2) return rc;
+  }
+  if (W->rowptr[W->nrows] > 0 && !W->rowval) return SLIM_ERROR;
+  score_candidates_host(W, trn, candset_host(cs), nrcmds, slot_scores, output, scores, counts);
+  return SLIM_OK;
 }
 
 int32_t SLIMGPU_LastListStats(slimgpu_list_stats_t* out) {

@@ -97,13 +97,14 @@ struct ListLength {  // the list length a request is scored with
   int32_t operator()(const LongListsRequest& r) const { return r.nrcmds; }
   int32_t operator()(const EvalTargets& e) const { return e.cut.c[e.cut.n - 1]; }
   int32_t operator()(const RankTargets&) const { return 1; }
+  int32_t operator()(const CandTargets&) const { return 1; }
 };
 }  // namespace
 
 // The chunk kernel serves lists of up to 64 from a model whose rows ascend, with fewer than 2^31 entries and a
 // split table of at most 2 GB; its long-list form (only for a call that may have lists of any length) serves
-// above 128, and at any length under SLIM_TOPN_KERNEL=long; only the chunk kernel has a rank form.  The wave
-// kernel serves the rest up to 128 (and everything under SLIM_TOPN_KERNEL=wave).
+// above 128, and at any length under SLIM_TOPN_KERNEL=long; only the chunk kernel has a rank form and a form for
+// candidate rows.  The wave kernel serves the rest up to 128 (and everything under SLIM_TOPN_KERNEL=wave).
 ScorerChoice choose_scorer(const DeviceRowView& W, const HistoryView& H, const ScorerRequest& rq, bool force_key64) {
   ScorerChoice C;
   C.plan = plan_chunks(std::max(W.ncols, 1), W.max_row, H.max_hist, force_key64);
@@ -114,7 +115,14 @@ ScorerChoice choose_scorer(const DeviceRowView& W, const HistoryView& H, const S
   const bool sorted = W.rows_sorted || W.nnz == 0;
   const bool chunk_ok = W.nnz < (int64_t(1) << 31) && sorted &&
                         (size_t)std::max(W.nrows, 1) * ((size_t)C.plan.nchunks + 1) * sizeof(uint32_t) <= kSplitLimit;
-  if (any_length && chunk_ok && (C.nrcmds > 128 || pinned("long"))) {
+  if (std::holds_alternative<CandTargets>(rq)) {  // only the chunk kernel scores candidate rows
+    if (chunk_ok)
+      C.path = kCand;
+    else
+      C.refusal = !sorted ? "candidate rows need the chunk scorer: the model's rows do not ascend by id (row order)"
+                          : "candidate rows need the chunk scorer: fewer than 2^31 model entries, a split table of at "
+                            "most 2 GB";
+  } else if (any_length && chunk_ok && (C.nrcmds > 128 || pinned("long"))) {
     C.path = kLong;
   } else if (C.nrcmds > 128) {
     C.refusal = !sorted
@@ -165,7 +173,7 @@ size_t long_area_bytes(const ChunkPlan& P, int32_t nrcmds, int sort_cap) {
   return (std::max(chunks, select) + 15) / 16 * 16;
 }
 size_t long_lds_bytes(size_t area) { return area + kLongBins * sizeof(uint32_t) + kLcWords * sizeof(int); }
-bool uses_split_table(ScorerPath path) { return path == kChunk || path == kRank || path == kLong; }
+bool uses_split_table(ScorerPath path) { return path == kChunk || path == kRank || path == kLong || path == kCand; }
 
 // the chunk kernel that takes Args, for the plan's workgroup and key width
 template <class Args, int NW, typename KeyT>
@@ -173,6 +181,7 @@ constexpr auto chunk_kernel() {
   if constexpr (std::is_same_v<Args, TopN2Args>) return &topn_chunk_kernel<NW, KeyT>;
   else if constexpr (std::is_same_v<Args, TopNEvalArgs>) return &topn_chunk_eval_kernel<NW, KeyT>;
   else if constexpr (std::is_same_v<Args, TopNRankArgs>) return &topn_chunk_rank_kernel<NW, KeyT>;
+  else if constexpr (std::is_same_v<Args, TopNCandArgs>) return &topn_chunk_cand_kernel<NW, KeyT>;
   else return &topn_chunk_long_kernel<NW, KeyT>;
 }
 template <class Args>
@@ -320,6 +329,24 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
       }
       break;
     }
+    case kCand: {
+      const CandidateRows& cr = std::get<CandTargets>(rq).rows;
+      L.groups = chunk_groups(P.lds, P.t2w, H.nusers, num_cus);
+      ws.need(ws.cand, (size_t)cr.entries);
+      // what dead entries, empty histories and out-of-range ids keep
+      HIP_TRY(hipMemsetAsync(ws.cand.get(), 0, sizeof(float) * (size_t)std::max<int64_t>(cr.entries, 1), stream));
+      if (cr.entries <= 0) break;
+      TopNCandArgs A{};
+      fill_common(A, W, H, C, ws);
+      A.cptr = cr.cptr; A.lptr = cr.lptr; A.pairs = cr.pairs; A.out = ws.cand.get();
+      // a row's chunk bounds go to the merge area (plan_chunks: the bytes behind the chunks) where they fit;
+      // SLIM_CAND_BOUNDS=search takes the search per chunk that serves when they do not
+      const char* benv = std::getenv("SLIM_CAND_BOUNDS");
+      A.bounds_table = ((size_t)P.nchunks + 1) * sizeof(int) <= (size_t)P.t2w * kT2MaxN * 16 + P.t2w * sizeof(int) &&
+                       !(benv && std::strcmp(benv, "search") == 0);
+      launch_scorer(pick_kernel<TopNCandArgs>(P), L, 64 * P.t2w, P.lds, stream, A);
+      break;
+    }
     default: {  // kWave
       size_t lds = 0;
       L.groups = wave_kernel_waves(H.nusers, nrcmds, num_cus, &lds);
@@ -335,6 +362,22 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
     }
   }
   return L;
+}
+
+ScorerPath queue_candidates(const DeviceRowView& W, const HistoryView& H, const CandidateRows& rows, int32_t nrcmds,
+                            int num_cus, hipStream_t stream, ScorerWorkspace& ws) {
+  const ScorerRequest rq = CandTargets{rows};
+  if (queue_scorer(W, H, choose_scorer(W, H, rq), rq, num_cus, stream, ws).path != kCand) return kRefused;
+  if (nrcmds > 0 && H.nusers > 0) {
+    ws.need(ws.oid, (size_t)H.nusers * nrcmds); ws.need(ws.osc, (size_t)H.nusers * nrcmds);
+    ws.need(ws.ocnt, (size_t)H.nusers);
+    const size_t lds = (size_t)kLongMaxN * sizeof(uint4);  // the longest row a list is made of
+    hipLaunchKernelGGL(k_cand_lists, dim3(std::max(1, std::min<int>(H.nusers, num_cus * 8))),
+                       dim3(64 * kCandListWaves), lds, stream, H.nusers, H.users, nrcmds, rows.cptr, rows.cind,
+                       ws.cand.get(), ws.oid.get(), ws.osc.get(), ws.ocnt.get());
+    HIP_TRY(hipGetLastError());
+  }
+  return kCand;
 }
 
 size_t fetch_lists(const ScorerWorkspace& ws, int32_t nusers, int32_t nrcmds, hipStream_t stream, int32_t* output,

@@ -276,6 +276,16 @@ struct TopNLongArgs : TopN2Args {
   int32_t area = 0;                    // bytes of the chunk / selection area; the histogram lies behind it
 };
 
+// candidate rows (slim_gpu_cand.h, topn_chunk_cand_kernel): no selection; after a chunk the scores of the ids the
+// user's candidate row names inside it go to the row's slots.  The rows go by USER id, like the exclusion rows.
+struct TopNCandArgs : ChunkArgs {
+  const int64_t* cptr = nullptr;  // the set as given: where a user's slots start in `out`
+  const int64_t* lptr = nullptr;  // the live entries of every row, ascending by id ...
+  const int2* pairs = nullptr;    // ... as (id, slot in the row); ids inside [0, ncols)
+  float* out = nullptr;           // slot scores, laid out like the set; cleared before the launch
+  int32_t bounds_table = 0;       // the nchunks + 1 chunk bounds of a row fit the merge area
+};
+
 __device__ __forceinline__ unsigned long long readlane_key(unsigned long long v, int l) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
@@ -678,9 +688,16 @@ __device__ __forceinline__ int draw_user(const Args& T, int& pos, const int tid)
 // ids of the exclusion row of user `u` (the body's, after Mode::begin has settled which user the position is),
 // under the history's range guard.  The row's bounds are two scalar loads per chunk: held across the walk they
 // would take four scalar registers it has not got.  The branches are on kernel arguments: wave-uniform.
-template <class Args, class Lds>
+// MARK false (a mode that scores given candidates, CandMode): nobody is excluded, not the history either -- every
+// slot leaves as kUnt and none is ever kExc.
+template <bool MARK = true, class Args, class Lds>
 __device__ __forceinline__ void prepare_chunk(const Args& T, const Lds& L, const int base, const int width,
                                               const int64_t h0, const int64_t h1, const int u) {
+  if constexpr (!MARK) {
+    for (int k = L.lane; k < width; k += 64) L.disc[k] = Lds::kUnt;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    return;
+  }
   if (T.flt.bits == nullptr)
     for (int k = L.lane; k < width; k += 64) L.disc[k] = Lds::kUnt;
   else
@@ -815,6 +832,7 @@ template <int NW, typename KeyT, bool EVAL>
 struct ListsMode {
   using Args = std::conditional_t<EVAL, TopNEvalArgs, TopN2Args>;
   using Lds = ChunkLds<NW, KeyT>;
+  static constexpr bool kMarkHistory = true;
   // this wavefront's N best so far: lane t holds rank t
   float ls = 0.0f;
   KeyT ld = Lds::kUnt;
@@ -954,6 +972,7 @@ template <int NW, typename KeyT>
 struct RankMode {
   using Args = TopNRankArgs;
   using Lds = ChunkLds<NW, KeyT>;
+  static constexpr bool kMarkHistory = true;
   float* r_s = nullptr;  // the user's test keys of this pass in the merge area, and their counts
   KeyT* r_d = nullptr;
   int* r_c = nullptr;
@@ -1030,6 +1049,7 @@ template <int NW, typename KeyT>
 struct LongMode {
   using Args = TopNLongArgs;
   using Lds = ChunkLds<NW, KeyT>;
+  static constexpr bool kMarkHistory = true;
   uint32_t* l_hist = nullptr;  // the histogram and the control words, behind the chunk / selection area
   int* l_ctl = nullptr;
 
@@ -1071,6 +1091,72 @@ struct LongMode {
   }
 };
 
+// Candidate rows: the scores of the ids a caller names per user (slim_gpu_cand.h), history items included, so
+// prepare_chunk marks nothing (kMarkHistory false).  The device form of the set holds a row's live entries
+// ascending by id, so the entries of chunk c are one stretch of the row.  begin finds the nchunks + 1 stretch
+// bounds ONCE per user -- thread c searches bound c * cw, the offsets (from the row's start) go to the merge
+// area, which this mode has no other use for; a table that does not fit there is replaced by a wave-uniform
+// search per chunk.  chunk: lanes stride over the stretch, read (key, score) of slot id - base and write the
+// score -- 0 for a slot nothing touched -- to the entry's slot of the output.  Entries that are not live (an
+// earlier occurrence of a repeated id, an id outside [0, ncols)) and the rows of users without a history are
+// never written: the output was cleared before the launch.  The row's pointers are scalar loads per chunk, like
+// the exclusion row's, so that they hold no scalar registers across the walk.
+template <int NW, typename KeyT>
+struct CandMode {
+  using Args = TopNCandArgs;
+  using Lds = ChunkLds<NW, KeyT>;
+  static constexpr bool kMarkHistory = false;
+  int user = 0;
+
+  // first entry of [r0, r1) whose id is >= bound
+  static __device__ __forceinline__ int64_t lower(const int2* __restrict__ pairs, int64_t lo, int64_t hi,
+                                                  const int64_t bound) {
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)pairs[mid].x < bound) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  }
+
+  __device__ __forceinline__ bool begin(const Args& T, const Lds& L, int& u, const int&, int64_t& h0, int64_t& h1) {
+    h0 = uni64(T.hptr[u]), h1 = uni64(T.hptr[u + 1]);
+    user = u;
+    const int64_t r0 = uni64(T.lptr[u]), r1 = uni64(T.lptr[u + 1]);
+    if (h0 == h1 || r0 == r1) return false;  // every slot of the row keeps its 0
+    if (T.bounds_table) {
+      int* bounds = reinterpret_cast<int*>(L.marea);
+      for (int c = L.tid; c <= T.nchunks; c += 64 * NW)
+        bounds[c] = (int)(lower(T.pairs, r0, r1, (int64_t)c * T.cw) - r0);
+      __syncthreads();
+    }
+    return true;
+  }
+
+  __device__ __forceinline__ void chunk(const Args& T, const Lds& L, const int base, const int width) {
+    const int64_t r0 = uni64(T.lptr[user]), c0 = uni64(T.cptr[user]);
+    int64_t lo, hi;
+    if (T.bounds_table) {
+      const int* bounds = reinterpret_cast<const int*>(L.marea);
+      const int c = base / T.cw;
+      lo = r0 + __builtin_amdgcn_readfirstlane(bounds[c]);
+      hi = r0 + __builtin_amdgcn_readfirstlane(bounds[c + 1]);
+    } else {
+      const int64_t r1 = uni64(T.lptr[user + 1]);
+      lo = uni64(lower(T.pairs, r0, r1, (int64_t)base));
+      hi = uni64(lower(T.pairs, lo, r1, (int64_t)base + width));
+    }
+    for (int64_t e = lo + L.lane; e < hi; e += 64) {
+      const int2 p = T.pairs[e];
+      const int k = p.x - base;  // in [0, width): the stretch holds the ids of this chunk only
+      const KeyT d = L.disc[k];
+      const float sc = L.score[k];
+      T.out[c0 + p.y] = d == Lds::kUnt ? 0.0f : sc;
+    }
+  }
+
+  __device__ __forceinline__ void finish(const Args&, const Lds&, int, const int&) {}
+};
+
 template <int NW, typename KeyT, class Mode>
 __device__ __forceinline__ void topn_chunk_body(const typename Mode::Args& T) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1085,7 +1171,7 @@ __device__ __forceinline__ void topn_chunk_body(const typename Mode::Args& T) {
       for (int c = L.wave; c < T.nchunks; c += NW) {
         const int base = c * T.cw;
         const int width = (T.ncols - base) < T.cw ? (T.ncols - base) : T.cw;
-        prepare_chunk(T, L, base, width, h0, h1, u);
+        prepare_chunk<Mode::kMarkHistory>(T, L, base, width, h0, h1, u);
         walk_history<KeyT>(T, L, c, base, h0, h1);
         M.chunk(T, L, base, width);
       }
@@ -1110,6 +1196,44 @@ __global__ __launch_bounds__(64 * NW) void topn_chunk_rank_kernel(const TopNRank
 template <int NW, typename KeyT>
 __global__ __launch_bounds__(64 * NW) void topn_chunk_long_kernel(const TopNLongArgs T) {
   topn_chunk_body<NW, KeyT, LongMode<NW, KeyT>>(T);
+}
+template <int NW, typename KeyT>
+__global__ __launch_bounds__(64 * NW) void topn_chunk_cand_kernel(const TopNCandArgs T) {
+  topn_chunk_body<NW, KeyT, CandMode<NW, KeyT>>(T);
+}
+
+// The lists of candidate rows, after the scorer on the same stream: one workgroup per position.  A row's records
+// (image of the slot's score, slot, id) -- every entry of the row as given, dead ones with their 0 -- are sorted
+// in LDS (long_sort: image ascending = score descending, then slot ascending: emit_best's order) and the first
+// min(nrcmds, row length) leave.  Rows are at most SLIMGPU_MAX_LIST long (the host refuses longer ones).
+constexpr int kCandListWaves = 4;
+__global__ __launch_bounds__(64 * kCandListWaves) void k_cand_lists(
+    int32_t npos, const int32_t* __restrict__ users, int32_t nrcmds, const int64_t* __restrict__ cptr,
+    const int32_t* __restrict__ cind, const float* __restrict__ slot_scores, int32_t* __restrict__ out_ids,
+    float* __restrict__ out_scores, int32_t* __restrict__ out_cnt) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint4* rec = reinterpret_cast<uint4*>(smem);
+  const int tid = threadIdx.x;
+  for (int q = (int)blockIdx.x; q < npos; q += (int)gridDim.x) {
+    const int u = users ? users[q] : q;
+    const int64_t c0 = cptr[u];
+    const int len = min((int)(cptr[u + 1] - c0), kLongMaxN);
+    int p2 = 1;
+    while (p2 < len) p2 <<= 1;
+    for (int j = tid; j < p2; j += 64 * kCandListWaves)
+      rec[j] = j < len ? make_uint4(score_image(slot_scores[c0 + j]), 0u, (uint32_t)j, (uint32_t)cind[c0 + j])
+                       : make_uint4(~0u, ~0u, ~0u, ~0u);
+    __syncthreads();
+    long_sort<kCandListWaves>(rec, p2);
+    const int n = len < nrcmds ? len : nrcmds;
+    for (int r = tid; r < n; r += 64 * kCandListWaves) {
+      const uint4 w = rec[r];
+      out_ids[(int64_t)q * nrcmds + r] = (int32_t)w.w;
+      out_scores[(int64_t)q * nrcmds + r] = image_score(w.x);
+    }
+    if (tid == 0) out_cnt[q] = n;
+    __syncthreads();  // the records are read: the next position may overwrite them
+  }
 }
 
 // facts[0] = entries of the longest row, facts[1] = 1 when some row's ids are not strictly ascending

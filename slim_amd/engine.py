@@ -135,6 +135,31 @@ class ResidentModel(object):
         out = (ids.reshape(n, nrcmds), scores.reshape(n, nrcmds))
         return out + (counts,) if return_counts else out
 
+    def score_candidates(self, device_matrix, cset, users=None, nrcmds=None):
+        """SLIMGPU_MatrixScoreCandidates: the 1-vs-k scores of the candidate rows of a CandidateSet
+        (DeviceMatrix.candidate_set) for every row of the staged matrix, or for the rows in `users` (strictly
+        ascending ids; the candidate row of a user goes by its id).  Returns the slot scores, laid out like the set
+        (cset.indptr; 0 in the rows of users not selected), and with nrcmds also (ids, scores, counts) of shape
+        [rows, nrcmds]: every row in order (score descending, then slot), ids -1 and scores 0 beyond a list."""
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = device_matrix.nrows if users is None else users.size
+        k = 0 if nrcmds is None else int(nrcmds)
+        slot = np.zeros(max(cset.size, 1), np.float32)
+        ids = np.full(max(n * k, 1), -1, np.int32)
+        scores = np.zeros(max(n * k, 1), np.float32)
+        counts = np.zeros(max(n, 1), np.int32)
+        st = self._lib.SLIMGPU_MatrixScoreCandidates(
+            self.handle, device_matrix.handle, cset.handle, 0 if users is None else users.size,
+            None if users is None else users.ctypes.data_as(C.c_void_p), k, slot.ctypes.data_as(C.c_void_p),
+            ids.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_MatrixScoreCandidates failed (%d): %s" % (st, _lib.last_error()))
+        slot = slot[:cset.size]
+        if nrcmds is None:
+            return slot
+        return slot, (ids[:n * k].reshape(n, k), scores[:n * k].reshape(n, k), counts[:n])
+
     def free(self):
         if self.handle:
             self._lib.SLIMGPU_ModelFree(C.byref(self.handle))
@@ -179,6 +204,41 @@ class ItemFilter(object):
     def close(self):
         if self.handle is not None and self.handle.value:
             self._lib.SLIMGPU_FilterFree(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+class CandidateSet(object):
+    """Per-user candidate rows (SLIMGPU_CandSetCreate, include/slim_gpu_cand.h) over `ncols` items; owns the handle.
+    rows: a scipy CSR taken as it is (its indptr / indices: no order, repeats and ids outside the items allowed),
+    or the pair (indptr, indices).  Row u holds the candidates of user u."""
+
+    def __init__(self, ncols, rows, lib=None):
+        self._lib = lib or _lib.load()
+        self.handle = C.c_void_p()
+        self.ncols = int(ncols)
+        indptr, indices = (rows.indptr, rows.indices) if sp.issparse(rows) else rows
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.int64).ravel()
+        if self.indptr.size < 1:
+            raise ValueError("candidate set: the row pointer needs at least one entry")
+        self.nusers = self.indptr.size - 1
+        # (one spare element: an empty set still has an address)
+        ind = np.concatenate((np.asarray(indices, dtype=np.int32).ravel(), np.zeros(1, np.int32)))
+        self.size = ind.size - 1
+        st = self._lib.SLIMGPU_CandSetCreate(self.ncols, self.nusers, self.indptr.ctypes.data_as(C.c_void_p),
+                                             ind.ctypes.data_as(C.c_void_p), C.byref(self.handle))
+        if st != SLIM_OK:
+            self.handle = C.c_void_p()
+            raise ValueError("SLIMGPU_CandSetCreate failed (%d): %s" % (st, _lib.last_error()))
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            self._lib.SLIMGPU_CandSetFree(self.handle)
         self.handle = None
 
     def __del__(self):
@@ -292,6 +352,19 @@ class Evaluator(object):
         return [{"nrcmds": int(c), "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(cut)]
+
+    def evaluate_candidates(self, model, cset):
+        """SLIMGPU_ModelEvaluateCandidates: one dict per list length (evaluate_at()'s keys) for the lists the
+        model makes of the users' candidate rows (a CandidateSet) -- HR on sampled negatives, in HBM."""
+        n = len(self.cutoffs)
+        met = np.zeros(4 * max(n, 1), np.float64)
+        nv = np.zeros(3 * max(n, 1), np.int32)
+        st = self._lib.SLIMGPU_ModelEvaluateCandidates(self.handle, model.handle, cset.handle, n, met, nv)
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_ModelEvaluateCandidates failed (%d): %s" % (st, _lib.last_error()))
+        return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
+                 "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
+                 "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
 
     def prepass_ms(self):
         """Milliseconds of the pre-pass (the test entries' scores and keys) of the most recent ranked call."""
@@ -507,6 +580,12 @@ class DeviceMatrix(object):
         for the Evaluator's calls.
         Pass at most one of allowed / blocked (item ids); exclusions: a scipy CSR over user rows."""
         return ItemFilter(self.ncols, allowed, blocked, exclusions, lib=self._lib)
+
+    def candidate_set(self, C_rows):
+        """SLIMGPU_CandSetCreate over this matrix's items: a CandidateSet (row u = the candidates of user u; a scipy
+        CSR taken as it is, or (indptr, indices)) for ResidentModel.score_candidates and
+        Evaluator.evaluate_candidates."""
+        return CandidateSet(self.ncols, C_rows, lib=self._lib)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)

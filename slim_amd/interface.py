@@ -450,6 +450,60 @@ class SLIM(object):
                                 np.array2string(outscores[key], max_line_width=np.inf) + "\n")
         return (out, outscores) if returnscores else out
 
+    def rerank(self, data, candidates, nrcmds=None, returnscores=False):
+        """Order the caller's own candidates per user (an engine extension, include/slim_gpu_cand.h): `candidates`
+        maps a user of `data` to a sequence of ORIGINAL item ids, of any length per user.  Every candidate gets its
+        1-vs-k score (history items are scored too; an item the model does not know scores 0 and is counted like
+        predict does); returns a dict from user to the items in model order -- score descending, ties in the
+        order given -- cut at nrcmds, and a dict of their scores with returnscores."""
+        if self.ismodel != SLIM_OK:
+            raise TypeError("Model not found. Please train a model.")
+        assert self.nItems == data.nItems, "The shape of the input matrix should match the model."
+        user_is_dict = isinstance(data.user2id, dict)
+        rows = [None] * data.nUsers
+        for user, items in candidates.items():
+            try:
+                rows[int(data.user2id[user])] = (user, list(items))
+            except (KeyError, IndexError):
+                raise KeyError("rerank: user %r is not in the input matrix" % (user,))
+        cptr = np.zeros(data.nUsers + 1, np.int64)
+        for u, r in enumerate(rows):
+            cptr[u + 1] = cptr[u] + (len(r[1]) if r else 0)
+        cind = np.full(int(cptr[-1]) + 1, -1, np.int32)
+        unknown = 0
+        for u, r in enumerate(rows):
+            for j, it in enumerate(r[1] if r else ()):
+                try:
+                    cind[cptr[u] + j] = self.item2id[it]
+                except (KeyError, IndexError):
+                    unknown += 1
+        if unknown:
+            print("%d candidate items not in the training set." % unknown)
+        ncols = int(C.cast(self.handle, C.POINTER(_lib.CsrView)).contents.ncols)
+        cs = C.c_void_p()
+        if self._lib.SLIMGPU_CandSetCreate(ncols, data.nUsers, cptr.ctypes.data_as(C.c_void_p),
+                                           cind.ctypes.data_as(C.c_void_p), C.byref(cs)) != SLIM_OK:
+            raise RuntimeError("Something went wrong with the candidate set. [%s]" % _lib.last_error())
+        slot = np.zeros(cind.size, np.float32)
+        try:
+            rc = self._lib.Py_SLIM_ScoreCandidates(self.handle, data.handle, cs, 0, slot.ctypes.data_as(C.c_void_p),
+                                                   None, None, None)
+        finally:
+            self._lib.SLIMGPU_CandSetFree(cs)
+        if rc != SLIM_OK:
+            raise RuntimeError("Something went wrong during prediction. [%s]" % _lib.last_error())
+        out, outscores = {}, {}
+        for u, r in enumerate(rows):
+            if r is None:
+                continue
+            sc = slot[cptr[u]:cptr[u + 1]]
+            order = np.argsort(-sc, kind="stable")     # score descending, then slot ascending
+            if nrcmds is not None:
+                order = order[:nrcmds]
+            out[r[0]] = [r[1][j] for j in order]
+            outscores[r[0]] = sc[order]
+        return (out, outscores) if returnscores else out
+
     # -- persistence -----------------------------------------------------------
     def save_model(self, modelfname, mapfname):
         if self.ismodel != SLIM_OK:
