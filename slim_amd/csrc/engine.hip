@@ -1385,6 +1385,8 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
     drop_float_gram(m);
   }
   size_t gramr_lds = 0;
+  bool gramr_ring = false;
+  int gramr_wps = 0;
   // rows through the LDS ring (global_load_lds) where a row is many groups long -- measured
   // (profiles/r05/gramr_dma_ab.txt): C4, 13 groups, kernel 6.62 -> 5.37 s; C5, 3 groups, where
   // one round of register loads already holds the whole row, 1.32 -> 1.41 s.
@@ -1392,7 +1394,7 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
   bool gramr_dma = (m->Gp_nchunks + kGramrNT - 1) / kGramrNT > 6;
   if (const char* e = std::getenv("SLIM_GPU_GRAMR_DMA")) gramr_dma = std::atoi(e) != 0;
   if (p.use_gram && m->Gp_ready && !std::getenv("SLIM_GPU_NO_GRAMR"))
-    p.fn_r = gramr_kernel(m->Gp_nchunks, gramr_dma, &p.gramr_kr, &p.gramr_kl, &gramr_lds);
+    p.fn_r = gramr_kernel(m->Gp_nchunks, gramr_dma, &p.gramr_kr, &p.gramr_kl, &gramr_lds, &gramr_ring, &gramr_wps);
   p.use_gramr = p.fn_r != nullptr;
   if (p.use_gram && !p.use_gramr && m->Gf_dropped)
     throw Refusal{SLIM_ERROR, "SLIMGPU_Learn: the floats of G were dropped and the byte-plane kernel cannot run this solve"};
@@ -1401,6 +1403,13 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
     p.gram_v = 1;  // (x only in the slab: g is on chip)
   }
   p.gram_lds = p.use_gramr ? gramr_lds : (p.gram_v > 0 ? sizeof(float) * (size_t)p.ncols_pad : 0);
+  if (p.use_gram && p.trace_level >= 1) {  // which instantiation this solve runs (gram_inst.hpp, gramr_inst.hpp)
+    if (p.use_gramr)
+      std::fprintf(stderr, "[trace] item-space kernel: packed <%d,%d>, %s loads, WPS %d\n", p.gramr_kr, p.gramr_kl,
+                   gramr_ring ? "ring" : "register", gramr_wps);
+    else
+      std::fprintf(stderr, "[trace] item-space kernel: float <%d,%d>\n", p.gram_nw, p.gram_v);
+  }
   // tile width: 32 item columns per workgroup (128-byte residual lines) unless the row
   // offsets would overflow the kernel's 32-bit byte offsets
   p.tileP = p.kernel == SLIMGPU_KERNEL_TILE16 ? 16 : 32;

@@ -4,12 +4,13 @@
 #include "cd_gramr.hpp"
 #include "gramr_inst.hpp"
 namespace slimamd {
-GramrFn gramr_kernel(int nchunks, bool dma, int* kr, int* kl, size_t* lds_bytes) {
+GramrFn gramr_kernel(int nchunks, bool dma, int* kr, int* kl, size_t* lds_bytes, bool* ring_used, int* wps) {
   const int k = (nchunks + kGramrNT - 1) / kGramrNT;
   *kl = 0;
   int ring_ah = 2;
   GramrFn fn = nullptr;
-  if (k <= 1) { *kr = 1; fn = dma ? cd_gramr_kernel<1, 0, true> : cd_gramr_kernel<1, 0, false>; }
+  *wps = 2;  // (the template's default from <3, 0> up)
+  if (k <= 1) { *kr = 1; *wps = 4; fn = dma ? cd_gramr_kernel<1, 0, true> : cd_gramr_kernel<1, 0, false>; }
   else if (k <= 3) {
     *kr = 3;
     // 128 VGPRs, two workgroups per CU (a few spills outside the row loop): a one-sweep C5 pair
@@ -17,7 +18,7 @@ GramrFn gramr_kernel(int nchunks, bool dma, int* kr, int* kl, size_t* lds_bytes)
     // pairs.  SLIM_GPU_GRAMR_WPS=2: 256 VGPRs, one workgroup per CU.
     const char* e = std::getenv("SLIM_GPU_GRAMR_WPS");
     if (e && std::atoi(e) == 2) fn = dma ? cd_gramr_kernel<3, 0, true> : cd_gramr_kernel<3, 0, false>;
-    else fn = dma ? cd_gramr_kernel<3, 0, true, 4> : cd_gramr_kernel<3, 0, false, 4>;
+    else { *wps = 4; fn = dma ? cd_gramr_kernel<3, 0, true, 4> : cd_gramr_kernel<3, 0, false, 4>; }
   }
   else if (k <= 6) { *kr = 6; fn = dma ? cd_gramr_kernel<6, 0, true> : cd_gramr_kernel<6, 0, false>; }
   else if (k <= kGramrMaxGroups) {
@@ -27,6 +28,7 @@ GramrFn gramr_kernel(int nchunks, bool dma, int* kr, int* kl, size_t* lds_bytes)
     // <10, 3>: one form, chosen at build time (gramr_k13.hip: the LDS ring, 4 slots)
     fn = gramr_kernel_k13(&dma, &ring_ah);
   }
+  *ring_used = dma;
   *lds_bytes = sizeof(float) * (size_t)*kl * kPackGroup + (dma ? (size_t)gramr_ring_bytes(ring_ah) : 0) + (size_t)gramr_hdr_bytes();
   return fn;
 }

@@ -11,8 +11,9 @@ using GramrFn = void (*)(const DevMatrix, const SolveArgs, const GramPacked);
 // the smallest instantiation whose K = KR + KL groups of 8192 ranks cover nchunks 16-rank chunks
 // (nullptr: more items than the largest one holds on chip -- 106 496)
 // dma: the variant that streams rows through an LDS ring (global_load_lds); lds_bytes = the dynamic
-// LDS the chosen instantiation needs
-GramrFn gramr_kernel(int nchunks, bool dma, int* kr, int* kl, size_t* lds_bytes);
+// LDS the chosen instantiation needs; ring_used / wps: what was instantiated (<10, 3> has one load
+// form, chosen at build time), for the solve's trace line
+GramrFn gramr_kernel(int nchunks, bool dma, int* kr, int* kl, size_t* lds_bytes, bool* ring_used, int* wps);
 GramrFn gramr_kernel_k13(bool* dma, int* ring_ah);  // <10, 3>: its own translation unit (compiles beside the others)
 
 // the tiles' union lists read off the byte planes (cd_gramr.hpp: gramr_union_kernel; kGramrUnionNT threads per tile)

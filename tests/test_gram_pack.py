@@ -9,15 +9,13 @@ form that streams transposed tiles of G (the default) -- every case twice over:
      which a decode cannot see.  The "G packed" trace line proves which form ran.
 
 G is built with gram_build_rows(0, ncols) + gram_commit(); below 8 GB the floats stay."""
-import contextlib
-import os
 import re
-import tempfile
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from library_output import stderr_of_the_library
 from slim_amd.engine import KERNEL_GRAM, DeviceMatrix
 
 gpu = pytest.mark.gpu
@@ -135,30 +133,6 @@ def check_same_planes(P, Q, what="streamed tiles vs gathers"):
 
 
 # ---- the device's side --------------------------------------------------------------------------
-@contextlib.contextmanager
-def stderr_of_the_library(env):
-    """Run the body with `env` set and file descriptor 2 in a file; yields a list that holds the text
-    afterwards."""
-    out = []
-    old = {k: os.environ.get(k) for k in env}
-    with tempfile.TemporaryFile(mode="w+b") as f:
-        keep = os.dup(2)
-        os.environ.update(env)
-        os.dup2(f.fileno(), 2)
-        try:
-            yield out
-        finally:
-            os.dup2(keep, 2)
-            os.close(keep)
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-            f.seek(0)
-            out.append(f.read().decode("utf-8", "replace"))
-
-
 def committed(R, binary, gather, blocks=None):
     """A fresh handle with G built (in `blocks`, default one call) and committed -> (handle, forms
     the trace names: [] when nothing was packed)."""
