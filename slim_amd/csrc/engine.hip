@@ -1201,6 +1201,7 @@ struct Path {
   int nwaves = 1;            // workgroups launched (tiles: re-planned by plan_tiles)
   int trace_level = 0;
   bool has_imodel = false;
+  bool exact_gram = false;   // the aTy sums in a fixed order, no float atomics (SolveArgs::exact_gram)
   // FSLIM in item space (cd_fslim_gram.hpp)
   bool use_fgram = false, f_block = false;
   int f_stride = 0, f_ustride = 0, f_tab_n = 0, f_waves = 1;
@@ -1336,6 +1337,9 @@ int32_t gram_for_solve(slimgpu_matrix* m, const LearnOptions& opt, int32_t trace
 // and how many workgroups fit.
 void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, const slim_csr_t* imodel,
                  const slimgpu_model* warm_dev, Path& p) {
+  // (FSLIM on ratings that can cancel: the fixed-order pass also counts co-ratings, so that
+  // a candidate whose sum is 0 stays a candidate -- neighbors.c:46-60 marks every co-rated item)
+  p.exact_gram = m->exact_gram || std::getenv("SLIM_GPU_EXACT_GRAM") || (opt.nnbrs > 0 && m->nonpositive);
   if (p.kernel == SLIMGPU_KERNEL_AUTO)
     p.kernel = p.lds_need <= 64 * 1024 ? SLIMGPU_KERNEL_WAVE_LDS : SLIMGPU_KERNEL_TILE;
   if (p.kernel == SLIMGPU_KERNEL_WAVE_LDS && p.lds_need > 160 * 1024)
@@ -1529,6 +1533,10 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
   }
   // wave kernels: one block = one wavefront; tile kernel: one block = 16 wavefronts
   p.nwaves = std::max(1, std::min(nwork, m->num_cus * waves_per_cu));
+  if (!p.use_gram && !p.use_tile && p.trace_level >= 1)  // which instantiation of cd_wave_kernel this solve runs
+    std::fprintf(stderr, "[trace] wave kernel: %s, %s, sums %s, %d wavefronts, %zu bytes of LDS\n",
+                 p.use_lds ? "lds" : "hbm", m->binary ? "binary" : "valued", p.exact_gram ? "ordered" : "atomic",
+                 p.nwaves, p.use_lds ? p.lds_need : (size_t)0);
   // co-resident tile workgroups: what the occupancy calculator grants this instantiation
   // (1 x 16 or 2 x 8 wavefronts per CU by design; fewer if the register or LDS footprint
   // of a build ever grows), never more than the design assumes
@@ -1909,10 +1917,7 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
   S.ubounds = p.use_tile ? m->split[t.cluster_lg].ubounds.get() : nullptr;
   S.csplit = p.use_tile ? m->split[t.cluster_lg].csplit.get() : nullptr;
   S.mailbox = L.s.mailbox;
-  // (FSLIM on ratings that can cancel: the fixed-order pass also counts co-ratings, so that
-  // a candidate whose sum is 0 stays a candidate -- neighbors.c:46-60 marks every co-rated item)
-  S.exact_gram = (m->exact_gram || std::getenv("SLIM_GPU_EXACT_GRAM") ||
-                  (opt.nnbrs > 0 && m->nonpositive)) ? 1 : 0;
+  S.exact_gram = p.exact_gram ? 1 : 0;  // (decided in finish_path, where the trace names it)
   S.atypart = L.s.part;
   S.bm_shift = L.s.bm_shift;
   S.bm_words = L.s.bm_words;
