@@ -21,8 +21,14 @@
  * fewer than 2^31 model entries and a split table of at most 2 GB; anything else is SLIM_ERROR_INPUT with a
  * SLIMGPU_LastError text and nothing is written.  One history walk per user serves a row of any length.
  *
- * Not built: the neg-file protocol of slim_predict (random tie order), a model-selection grid on sampled
- * negatives.  SLIMGPU_Predict1vsK is unchanged (rows of one width, up to 1024).
+ * Sampled negatives (slim_gpu_sample.h, included below): SLIMGPU_EvalSetSampleCandidates makes the set of the
+ * 1-vs-k protocol on the device -- per evaluated user nnegs sampled non-interacted items, then its held-out items --
+ * SLIMGPU_CandSetSample makes the same rows on the host, SLIMGPU_CandSetRows copies the rows of any set out.  The
+ * held-out items stand behind the negatives, so under "score descending, then slot ascending" a score tie goes to
+ * the negative: the pessimistic choice.  The option slots below put Py_SLIM_Mselect on that protocol.
+ *
+ * Not built: the neg-file protocol of slim_predict (random tie order), popularity-weighted negatives.
+ * SLIMGPU_Predict1vsK is unchanged (rows of one width, up to 1024).
  */
 #ifndef SLIM_AMD_SLIM_GPU_CAND_H_
 #define SLIM_AMD_SLIM_GPU_CAND_H_
@@ -64,8 +70,22 @@ int32_t SLIMGPU_ModelEvaluateCandidates(slimgpu_evalset_t *es, const slimgpu_mod
 int32_t Py_SLIM_ScoreCandidates(slim_t *model, slim_t *trn, slimgpu_candset_t *cs, int32_t nrcmds,
                                 float *slot_scores, int32_t *output, float *scores, int32_t *counts);
 
+/* Py_SLIM_Mselect / Py_SLIM_MselectFiltered on sampled negatives (slots beside SLIM_OPTION_GPU_EVALSTRIDE = 22):
+   with EVALNEGS > 0 the candidate set is sampled once, on the device, after the eval set exists, and every pair is
+   evaluated by SLIMGPU_ModelEvaluateCandidates' path -- HR / ARHR of the lists of nrcmds among nnegs negatives and
+   the held-out items.  The header prints nnegs, the seed and the set's entries; the selection of the best pairs is
+   unchanged; EVALSTRIDE combines.  SLIM_ERROR_INPUT before the first solve, with a text that says which: a filter,
+   nrcmds > 128 (the candidate lists use the eval set's cutoffs), and whatever keeps the evaluation out of HBM (ADMM,
+   several GPUs, SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0).  Never a fall-back to the full-catalogue figures. */
+enum {
+  SLIM_OPTION_GPU_EVALNEGS = 23, /* sampled negatives per user; -1 or 0: off */
+  SLIM_OPTION_GPU_EVALSEED = 24  /* the sampler's seed; -1: 1 */
+};
+
 #ifdef __cplusplus
 }
 #endif
+
+#include "slim_gpu_sample.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_CAND_H_ */

@@ -247,6 +247,19 @@ _CAND_SIGNATURES = {
 
 CAND_SYMBOLS = tuple(_CAND_SIGNATURES)
 
+# sampled negatives for the 1-vs-k protocol (include/slim_gpu_sample.h): candidate sets made on the device or on the
+# host, and the rows of any set copied out; users / cptr / cind are passed as pointers (any may be None)
+_SAMPLE_SIGNATURES = {
+    "SLIMGPU_EvalSetSampleCandidates": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "SLIMGPU_CandSetSample": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_uint64, C.POINTER(C.c_void_p)]),
+    "SLIMGPU_CandSetRows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_CandSetInfo": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int64)]),
+}
+
+SAMPLE_SYMBOLS = tuple(_SAMPLE_SIGNATURES)
+
 _lib = None
 
 
@@ -264,7 +277,7 @@ def load():
                               list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
                               list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
                               list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
-                              list(_CAND_SIGNATURES.items())):
+                              list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

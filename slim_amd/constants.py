@@ -50,6 +50,8 @@ class Opt(enum.IntEnum):
     GPU_SHARDCOUNT = 20    # SLIMGPU_Learn*: solve one shard of the requested columns ...
     GPU_SHARDINDEX = 21    # ... granules INDEX, INDEX + COUNT, ... of the cost-ordered work list
     GPU_EVALSTRIDE = 22    # Py_SLIM_Mselect: evaluate users 0, K, 2K, ... only (slim_gpu_eval.h; default: all)
+    GPU_EVALNEGS = 23      # Py_SLIM_Mselect: evaluate 1-vs-k on this many sampled negatives (slim_gpu_cand.h; 0: off)
+    GPU_EVALSEED = 24      # ... drawn with this seed (default 1)
 
 
 for _o in Opt:

@@ -1,0 +1,301 @@
+// cand_sample.hip -- the device sampler of slim_gpu_sample.h: the candidate set of the 1-vs-k protocol made where the
+// matrix and the test rows lie.  k_sample_negatives draws every selected user's negatives (one wavefront per user),
+// k_sample_rowlen and a scan give the row pointer, k_sample_rows writes "negatives, then the test row" into the
+// set's device copy, and candset_adopt (candidates.hip) indexes those rows as it indexes uploaded ones.  The host
+// learns the row pointer only.  The draws are those of host_csr.cpp: sample_candidates_host, bit for bit; both read
+// sample_mix64 & co. from host_csr.hpp, and include/slim_gpu_sample.h states the rule.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "host_csr.hpp"
+#include "host_stage.hpp"
+#include "scorer.hpp"
+
+namespace slimamd {
+namespace {
+struct SampleArgs {
+  int32_t nsel, ncols, nnegs;
+  uint64_t seed;
+  const int32_t* users;  // the user of every position; nullptr: position q is user q
+  const int64_t* hptr; const int32_t* hind;
+  const int64_t* tptr; const int32_t* tind;
+  int32_t* negs;         // [nsel][nnegs]: the negatives of a position, in order
+  int32_t* nneg;         // [nsel]: how many
+  int32_t rec_offset;    // LDS: where the dense rule's sort records start
+  int32_t rec_cap;       // how many of them there are (a power of two >= nnegs; 0: no user can be dense)
+};
+
+__device__ __forceinline__ bool bit_of(const uint32_t* bm, const int id) { return (bm[id >> 5] >> (id & 31)) & 1u; }
+// sets the bit of an id inside [0, ncols); 1 when it was clear
+__device__ __forceinline__ int mark_id(uint32_t* bm, const int id, const int ncols) {
+  if ((uint32_t)id >= (uint32_t)ncols) return 0;
+  const uint32_t bit = 1u << (id & 31);
+  return (atomicOr(&bm[id >> 5], bit) & bit) ? 0 : 1;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Bitonic sort of n = 2^k records (key high, key low, id) in LDS, ascending, by one wavefront; ends on a barrier.
+// (long_sort of topn_kernels.hpp for a workgroup of one wavefront: that header is topn.hip's alone.)
+__device__ __forceinline__ bool rec_before(const uint4 a, const uint4 b) {
+  return a.x < b.x || (a.x == b.x && (a.y < b.y || (a.y == b.y && a.z < b.z)));
+}
+__device__ __forceinline__ void sample_sort(uint4* rec, const int n) {
+  const int lane = threadIdx.x;
+  for (int k = 2; k <= n; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < (n >> 1); t += 64) {
+        const int lo = 2 * t - (t & (j - 1)), hi = lo + j;
+        const bool up = (lo & k) == 0;
+        const uint4 a = rec[lo], b = rec[hi];
+        if (rec_before(b, a) == up) {
+          rec[lo] = b;
+          rec[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// One wavefront (a workgroup of 64) per position.  LDS: one bit per item -- X_u and the accepted ids, which serves
+// exclusion and de-duplication at once and is cleared by un-marking what was marked --, the accepted ids in order,
+// and, when some user may fall under the dense rule, the records its sort needs.
+__global__ __launch_bounds__(64) void k_sample_negatives(const SampleArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint32_t* bm = reinterpret_cast<uint32_t*>(smem);
+  const int ncols = A.ncols, nnegs = A.nnegs;
+  const int nwords = (ncols + 31) >> 5;
+  int32_t* acc = reinterpret_cast<int32_t*>(bm + nwords);
+  uint4* rec = reinterpret_cast<uint4*>(smem + A.rec_offset);
+  const int lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;  // the lanes before this one
+  for (int w = lane; w < nwords; w += 64) bm[w] = 0u;
+  __syncthreads();
+  for (int q = (int)blockIdx.x; q < A.nsel; q += (int)gridDim.x) {
+    const int u = A.users ? A.users[q] : q;
+    const int64_t t0 = A.tptr[u], t1 = A.tptr[u + 1];
+    if (t1 <= t0) {  // (no held-out item: an empty row)
+      if (lane == 0) A.nneg[q] = 0;
+      continue;
+    }
+    const int64_t h0 = A.hptr[u], h1 = A.hptr[u + 1];
+    int fresh = 0;
+    for (int64_t e = h0 + lane; e < h1; e += 64) fresh += mark_id(bm, A.hind[e], ncols);
+    for (int64_t e = t0 + lane; e < t1; e += 64) fresh += mark_id(bm, A.tind[e], ncols);
+    const int E = wave_sum(fresh);
+    __syncthreads();
+    const uint64_t base = sample_base(A.seed, (uint64_t)u);
+    int got = 0;
+    const bool sparse = 2 * ((int64_t)E + nnegs) <= (int64_t)ncols;
+    if (sparse) {
+      const int stop = 16 * nnegs + 1024;  // the guard: the loop is bounded
+      for (int d0 = 0; d0 < stop && got < nnegs; d0 += 64) {
+        const int d = d0 + lane;
+        const int id = (int)sample_item(sample_key(base, (uint64_t)d), (uint32_t)ncols);
+        const bool cand = d < stop && !bit_of(bm, id);
+        // of equal draws in this batch the lowest lane is the first occurrence
+        bool dup = false;
+        unsigned long long rem = __ballot(cand);
+        while (rem) {
+          const int first = __ffsll((long long)rem) - 1;
+          const int v = __shfl(id, first);
+          const bool mine = cand && id == v;
+          if (mine && lane != first) dup = true;
+          rem &= ~__ballot(mine);
+        }
+        const bool ok = cand && !dup;
+        const unsigned long long okmask = __ballot(ok);
+        const int pos = got + __popcll(okmask & below);
+        if (ok && pos < nnegs) {  // (the last batch is cut at nnegs)
+          acc[pos] = id;
+          atomicOr(&bm[id >> 5], 1u << (id & 31));
+        }
+        got = min(nnegs, got + __popcll(okmask));
+        __syncthreads();
+      }
+    } else if (A.rec_cap > 0) {
+      // the m eligible ids with the smallest (key, id): the m-th smallest key bit by bit, then one collecting pass
+      const int m = min(nnegs, ncols - E);
+      uint64_t T = 0;
+      int k = m;  // ends as: how many of the ids whose key is T belong to the m
+      for (int b = 63; b >= 0 && m > 0; --b) {
+        int c = 0;
+        for (int i = lane; i < ncols; i += 64)
+          if (!bit_of(bm, i) && (sample_key(base, (uint64_t)i) >> b) == (T >> b)) ++c;
+        c = wave_sum(c);
+        if (k > c) {
+          k -= c;
+          T |= 1ull << b;
+        }
+      }
+      int n = 0, eqseen = 0;
+      for (int i0 = 0; i0 < ncols && m > 0; i0 += 64) {
+        const int i = i0 + lane;
+        const bool elig = i < ncols && !bit_of(bm, i);
+        const uint64_t key = elig ? sample_key(base, (uint64_t)i) : 0;
+        const bool eq = elig && key == T;
+        const unsigned long long eqmask = __ballot(eq);
+        const bool take = (elig && key < T) || (eq && eqseen + __popcll(eqmask & below) < k);
+        const unsigned long long tmask = __ballot(take);
+        const int pos = n + __popcll(tmask & below);
+        if (take && pos < A.rec_cap) rec[pos] = make_uint4((uint32_t)(key >> 32), (uint32_t)key, (uint32_t)i, 0u);
+        n += __popcll(tmask);
+        eqseen += __popcll(eqmask);
+      }
+      n = min(n, A.rec_cap);
+      int p2 = 1;
+      while (p2 < n) p2 <<= 1;
+      for (int j = n + lane; j < p2; j += 64) rec[j] = make_uint4(~0u, ~0u, ~0u, ~0u);
+      __syncthreads();
+      if (n > 0) sample_sort(rec, p2);  // (key, id) ascending
+      for (int j = lane; j < n; j += 64) acc[j] = (int32_t)rec[j].z;
+      got = n;
+      __syncthreads();
+    }
+    for (int j = lane; j < got; j += 64) A.negs[(int64_t)q * nnegs + j] = acc[j];
+    if (lane == 0) A.nneg[q] = got;
+    // un-mark: whole words go to 0, which is what every one of them was
+    for (int64_t e = h0 + lane; e < h1; e += 64) {
+      const int id = A.hind[e];
+      if ((uint32_t)id < (uint32_t)ncols) bm[id >> 5] = 0u;
+    }
+    for (int64_t e = t0 + lane; e < t1; e += 64) {
+      const int id = A.tind[e];
+      if ((uint32_t)id < (uint32_t)ncols) bm[id >> 5] = 0u;
+    }
+    if (sparse)
+      for (int j = lane; j < got; j += 64) bm[acc[j] >> 5] = 0u;
+    __syncthreads();
+  }
+}
+
+// len[u + 1] = entries of user u's row (len is preset to 0: the rows of users not selected are empty)
+__global__ void k_sample_rowlen(int32_t nsel, const int32_t* __restrict__ users, const int64_t* __restrict__ tptr,
+                                const int32_t* __restrict__ nneg, int64_t* __restrict__ len) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nsel; q += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t u = users ? users[q] : (int32_t)q;
+    const int64_t tl = tptr[u + 1] - tptr[u];
+    len[(int64_t)u + 1] = tl > 0 ? nneg[q] + tl : 0;
+  }
+}
+
+// the rows: the negatives, then the test row as staged.  One wavefront per position.
+__global__ void k_sample_rows(int32_t nsel, const int32_t* __restrict__ users, int32_t nnegs,
+                              const int32_t* __restrict__ negs, const int32_t* __restrict__ nneg,
+                              const int64_t* __restrict__ tptr, const int32_t* __restrict__ tind,
+                              const int64_t* __restrict__ cptr, int32_t* __restrict__ cind) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t q = wave; q < nsel; q += nwaves) {
+    const int32_t u = users ? users[q] : (int32_t)q;
+    const int64_t t0 = tptr[u], tl = tptr[u + 1] - t0;
+    if (tl <= 0) continue;
+    const int64_t c0 = cptr[u];
+    const int n = nneg[q];
+    for (int j = lane; j < n; j += 64) cind[c0 + j] = negs[q * nnegs + j];
+    for (int64_t j = lane; j < tl; j += 64) cind[c0 + n + j] = tind[t0 + j];
+  }
+}
+}  // namespace
+
+slimgpu_candset* evalset_sample_candidates(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed, int32_t* status) {
+  const std::string who = "SLIMGPU_EvalSetSampleCandidates: ";
+  auto bad = [&](const std::string& why) {
+    *status = refuse(who + why);
+    return static_cast<slimgpu_candset*>(nullptr);
+  };
+  EvalSetRows V;
+  if (evalset_rows(es, &V) != SLIM_OK) return bad("bad arguments (an eval set)");
+  if (nnegs < 1) return bad("nnegs must be at least 1, not " + std::to_string(nnegs));
+  if (V.merged)
+    return bad("the matrix was staged with SLIM_GPU_DUPLICATES=sum and repeated pairs were merged: its rows are not "
+               "the caller's");
+  if ((int64_t)nnegs + V.max_test > SLIMGPU_MAX_LIST)
+    return bad("nnegs " + std::to_string(nnegs) + " and the longest selected test row, " + std::to_string(V.max_test) +
+               " entries, give a candidate row above " + std::to_string(SLIMGPU_MAX_LIST) +
+               ": the evaluation needs lists");
+  if (V.ncols < 1 || V.ncols > SLIMGPU_SAMPLE_MAX_NCOLS)
+    return bad("the matrix has " + std::to_string(V.ncols) + " items: the device sampler keeps one bit per item in LDS "
+               "and takes at most " + std::to_string(SLIMGPU_SAMPLE_MAX_NCOLS) + " (SLIMGPU_CandSetSample serves)");
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(V.device));
+    hipStream_t stream = V.stream;
+    const int32_t nsel = V.nsel, nall = V.nall;
+    std::vector<int64_t> h_cptr((size_t)nall + 1, 0);
+    DeviceBuffer<int64_t> d_cptr((size_t)nall + 1);
+    DeviceBuffer<int32_t> d_cind;
+    if (nsel > 0) {
+      DeviceBuffer<int32_t> negs((size_t)nsel * (size_t)nnegs), nneg((size_t)nsel);
+      DeviceBuffer<int64_t> len((size_t)nall + 1);
+      SampleArgs A = {};
+      A.nsel = nsel; A.ncols = V.ncols; A.nnegs = nnegs; A.seed = seed;
+      A.users = V.d_users; A.hptr = V.hptr; A.hind = V.hind; A.tptr = V.tptr; A.tind = V.tind;
+      A.negs = negs.get(); A.nneg = nneg.get();
+      // a user is dense only when 2 * (E + nnegs) > ncols, and E is at most its history plus its test row
+      const bool dense = 2 * (V.max_hist + V.max_test + (int64_t)nnegs) > (int64_t)V.ncols;
+      size_t lds = sizeof(uint32_t) * (size_t)((V.ncols + 31) >> 5) + sizeof(int32_t) * (size_t)nnegs;
+      lds = (lds + 15) / 16 * 16;
+      A.rec_offset = (int32_t)lds;
+      if (dense) {
+        A.rec_cap = 1;
+        while (A.rec_cap < nnegs) A.rec_cap <<= 1;
+        lds += sizeof(uint4) * (size_t)A.rec_cap;
+      }
+      if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sample_negatives),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / (lds + 64)));
+      const int groups = std::max(1, std::min<int>(nsel, V.num_cus * per_cu));
+      hipLaunchKernelGGL(k_sample_negatives, dim3(groups), dim3(64), lds, stream, A);
+      HIP_TRY(hipGetLastError());
+      const unsigned flat = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)nsel + 255) / 256, (int64_t)V.num_cus * 16));
+      HIP_TRY(hipMemsetAsync(len.get(), 0, sizeof(int64_t) * ((size_t)nall + 1), stream));
+      hipLaunchKernelGGL(k_sample_rowlen, dim3(flat), dim3(256), 0, stream, nsel, V.d_users, V.tptr, nneg.get(),
+                         len.get());
+      HIP_TRY(hipGetLastError());
+      size_t scan_bytes = 0;
+      HIP_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, len.get(), d_cptr.get(), (size_t)nall + 1,
+                                      rocprim::plus<int64_t>(), stream));
+      DeviceBuffer<char> tmp(scan_bytes);
+      HIP_TRY(rocprim::inclusive_scan(tmp.get(), scan_bytes, len.get(), d_cptr.get(), (size_t)nall + 1,
+                                      rocprim::plus<int64_t>(), stream));
+      // the row pointer is all the host learns of the set: 8 bytes per user, once
+      HIP_TRY(hipMemcpyAsync(h_cptr.data(), d_cptr.get(), sizeof(int64_t) * ((size_t)nall + 1), hipMemcpyDeviceToHost,
+                             stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      const int64_t n = h_cptr[(size_t)nall];
+      if (n < 0 || n > (int64_t)nsel * nnegs + V.test_entries) throw HipFail{hipErrorUnknown, "the sampled row pointer"};
+      d_cind = DeviceBuffer<int32_t>((size_t)n);
+      const unsigned waves = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)nsel + 3) / 4, (int64_t)V.num_cus * 16));
+      hipLaunchKernelGGL(k_sample_rows, dim3(waves), dim3(256), 0, stream, nsel, V.d_users, nnegs, negs.get(),
+                         nneg.get(), V.tptr, V.tind, d_cptr.get(), d_cind.get());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(stream));  // (negs and nneg go with this block)
+    } else {
+      d_cind = DeviceBuffer<int32_t>(0);
+      HIP_TRY(hipMemsetAsync(d_cptr.get(), 0, sizeof(int64_t) * ((size_t)nall + 1), stream));
+    }
+    slimgpu_candset* cs = candset_adopt(V.ncols, std::move(h_cptr), std::move(d_cptr), std::move(d_cind), V.device,
+                                        V.num_cus, stream);
+    *status = SLIM_OK;
+    return cs;
+  } catch (const HipFail& e) {
+    *status = hip_failure("SLIMGPU_EvalSetSampleCandidates", e);
+    return nullptr;
+  } catch (const std::bad_alloc&) {
+    set_error(who + "out of host memory");
+    *status = SLIM_ERROR_MEMORY;
+    return nullptr;
+  }
+}
+}  // namespace slimamd

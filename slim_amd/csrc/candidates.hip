@@ -3,7 +3,8 @@
 // user ids taken as it is given, which the host scorer reads (host_csr.cpp: score_candidates_host).  The device
 // scorer (topn_kernels.hpp: CandMode) reads a copy that candset_on_device makes on the first call that scores on a
 // device: the rows as given and, per row, the live entries sorted by id with their slot.  Nothing here needs a
-// device before that.
+// device before that.  A set born on the device (cand_sample.hip) arrives with its rows in place: candset_adopt
+// runs the same index step on them and the host keeps the row pointer only, the ids until somebody asks.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -23,6 +24,7 @@ struct slimgpu_candset {
   int32_t ncols = 0, nusers = 0;
   std::vector<int64_t> cptr;  // nusers + 1
   std::vector<int32_t> cind;
+  bool host_ids = true;  // cind holds the ids (a set born on the device fetches them on first need)
   // the copy on `device` (-1: none yet)
   int device = -1;
   slimamd::DeviceBuffer<int64_t> d_cptr, d_lptr;
@@ -148,76 +150,95 @@ int32_t candset_check(const char* who, const slimgpu_candset* cs, int32_t model_
   return SLIM_OK;
 }
 
+namespace {
+// The index half of a set's device copy, which an uploaded set and a device-born one (cand_sample.hip) share:
+// d_cptr and d_cind hold the rows on the current device; d_lptr and d_pairs are made from them -- per row the live
+// entries sorted by id with their slot (k_cand_keys, the stable radix sort, the live pairs).  Drains `stream`.
+void candset_index(slimgpu_candset* cs, int num_cus, hipStream_t stream, int* allocs) {
+  const int64_t n = cs->cptr[cs->nusers];
+  const int32_t nrows = cs->nusers;
+  cs->d_lptr.reserve((size_t)nrows + 1);
+  if (allocs) ++*allocs;
+  HIP_TRY(hipMemsetAsync(cs->d_lptr.get(), 0, sizeof(int64_t) * ((size_t)nrows + 1), stream));
+  int64_t nlive = 0;
+  if (n > 0) {
+    // the sort's buffers live for this block only
+    DeviceBuffer<unsigned long long> k_in((size_t)n), k_out((size_t)n), count(1);
+    DeviceBuffer<uint32_t> s_in((size_t)n), s_out((size_t)n);
+    DeviceBuffer<uint8_t> flags((size_t)n);
+    if (allocs) *allocs += 7;
+    hipLaunchKernelGGL(k_cand_keys, dim3(grid_of((int64_t)nrows * 64, num_cus)), dim3(256), 0, stream, nrows,
+                       cs->ncols, cs->d_cptr.get(), cs->d_cind.get(), k_in.get(), s_in.get());
+    HIP_TRY(hipGetLastError());
+    unsigned bits = 33;  // the ids, and the rows up to nrows itself
+    while (bits < 64 && (1ull << (bits - 32)) <= (unsigned long long)nrows) ++bits;
+    size_t tmp_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in.get(), k_out.get(), s_in.get(), s_out.get(),
+                                      (size_t)n, 0u, bits, stream));
+    size_t sel_bytes = 0, sel2_bytes = 0;
+    HIP_TRY(rocprim::select(nullptr, sel_bytes, k_out.get(), flags.get(), k_in.get(), count.get(), (size_t)n,
+                            stream));
+    HIP_TRY(rocprim::select(nullptr, sel2_bytes, s_out.get(), flags.get(), s_in.get(), count.get(), (size_t)n,
+                            stream));
+    DeviceBuffer<char> tmp(std::max(tmp_bytes, std::max(sel_bytes, sel2_bytes)));
+    if (allocs) ++*allocs;
+    HIP_TRY(rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, k_in.get(), k_out.get(), s_in.get(), s_out.get(),
+                                      (size_t)n, 0u, bits, stream));
+    hipLaunchKernelGGL(k_cand_flags, dim3(grid_of(n, num_cus)), dim3(256), 0, stream, n, nrows, k_out.get(),
+                       flags.get());
+    HIP_TRY(hipGetLastError());
+    // the live entries, in order, back into the input buffers
+    HIP_TRY(rocprim::select(tmp.get(), sel_bytes, k_out.get(), flags.get(), k_in.get(), count.get(), (size_t)n,
+                            stream));
+    HIP_TRY(rocprim::select(tmp.get(), sel2_bytes, s_out.get(), flags.get(), s_in.get(), count.get(), (size_t)n,
+                            stream));
+    unsigned long long h_count = 0;
+    HIP_TRY(hipMemcpyAsync(&h_count, count.get(), sizeof(h_count), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    nlive = (int64_t)h_count;
+    cs->d_pairs.reserve((size_t)nlive);
+    if (allocs) ++*allocs;
+    if (nlive > 0) {
+      hipLaunchKernelGGL(k_cand_pairs, dim3(grid_of(nlive, num_cus)), dim3(256), 0, stream, nlive, k_in.get(),
+                         s_in.get(), cs->d_pairs.get());
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_cand_rowptr, dim3(grid_of((int64_t)nrows + 1, num_cus)), dim3(256), 0, stream, nrows,
+                         nlive, k_in.get(), cs->d_lptr.get());
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));  // the sort's buffers go; later calls may use another stream
+  } else {
+    cs->d_pairs.reserve(1);
+    if (allocs) ++*allocs;
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+}
+
+// The upload half: the host rows into d_cptr / d_cind on the current device, queued on `stream`.
+void candset_upload(slimgpu_candset* cs, hipStream_t stream, int* allocs, int64_t* h2d) {
+  const int64_t n = cs->cptr[cs->nusers];
+  const int32_t nrows = cs->nusers;
+  cs->d_cptr.reserve((size_t)nrows + 1);
+  cs->d_cind.reserve((size_t)n);
+  if (allocs) *allocs += 2;
+  HIP_TRY(hipMemcpyAsync(cs->d_cptr.get(), cs->cptr.data(), sizeof(int64_t) * ((size_t)nrows + 1),
+                         hipMemcpyHostToDevice, stream));
+  if (n > 0)
+    HIP_TRY(hipMemcpyAsync(cs->d_cind.get(), cs->cind.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice,
+                           stream));
+  if (h2d) *h2d += (int64_t)(sizeof(int64_t) * ((size_t)nrows + 1) + sizeof(int32_t) * (size_t)n);
+}
+}  // namespace
+
 CandidateRows candset_on_device(slimgpu_candset* cs, int device, int num_cus, hipStream_t stream, int* allocs,
                                 int64_t* h2d) {
   const int64_t n = cs->cptr[cs->nusers];
   if (cs->device != device) {  // first use here: the copy of another device goes
+    candset_need_ids(cs);      // (a set born on that device: its ids come down before they go)
     cs->d_cptr.reset(); cs->d_lptr.reset(); cs->d_cind.reset(); cs->d_pairs.reset();
     cs->device = -1;
-    const int32_t nrows = cs->nusers;
-    cs->d_cptr.reserve((size_t)nrows + 1);
-    cs->d_lptr.reserve((size_t)nrows + 1);
-    cs->d_cind.reserve((size_t)n);
-    if (allocs) *allocs += 3;
-    HIP_TRY(hipMemcpyAsync(cs->d_cptr.get(), cs->cptr.data(), sizeof(int64_t) * ((size_t)nrows + 1),
-                           hipMemcpyHostToDevice, stream));
-    if (n > 0)
-      HIP_TRY(hipMemcpyAsync(cs->d_cind.get(), cs->cind.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice,
-                             stream));
-    if (h2d) *h2d += (int64_t)(sizeof(int64_t) * ((size_t)nrows + 1) + sizeof(int32_t) * (size_t)n);
-    HIP_TRY(hipMemsetAsync(cs->d_lptr.get(), 0, sizeof(int64_t) * ((size_t)nrows + 1), stream));
-    int64_t nlive = 0;
-    if (n > 0) {
-      // the sort's buffers live for this block only
-      DeviceBuffer<unsigned long long> k_in((size_t)n), k_out((size_t)n), count(1);
-      DeviceBuffer<uint32_t> s_in((size_t)n), s_out((size_t)n);
-      DeviceBuffer<uint8_t> flags((size_t)n);
-      if (allocs) *allocs += 7;
-      hipLaunchKernelGGL(k_cand_keys, dim3(grid_of((int64_t)nrows * 64, num_cus)), dim3(256), 0, stream, nrows,
-                         cs->ncols, cs->d_cptr.get(), cs->d_cind.get(), k_in.get(), s_in.get());
-      HIP_TRY(hipGetLastError());
-      unsigned bits = 33;  // the ids, and the rows up to nrows itself
-      while (bits < 64 && (1ull << (bits - 32)) <= (unsigned long long)nrows) ++bits;
-      size_t tmp_bytes = 0;
-      HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in.get(), k_out.get(), s_in.get(), s_out.get(),
-                                        (size_t)n, 0u, bits, stream));
-      size_t sel_bytes = 0, sel2_bytes = 0;
-      HIP_TRY(rocprim::select(nullptr, sel_bytes, k_out.get(), flags.get(), k_in.get(), count.get(), (size_t)n,
-                              stream));
-      HIP_TRY(rocprim::select(nullptr, sel2_bytes, s_out.get(), flags.get(), s_in.get(), count.get(), (size_t)n,
-                              stream));
-      DeviceBuffer<char> tmp(std::max(tmp_bytes, std::max(sel_bytes, sel2_bytes)));
-      if (allocs) ++*allocs;
-      HIP_TRY(rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, k_in.get(), k_out.get(), s_in.get(), s_out.get(),
-                                        (size_t)n, 0u, bits, stream));
-      hipLaunchKernelGGL(k_cand_flags, dim3(grid_of(n, num_cus)), dim3(256), 0, stream, n, nrows, k_out.get(),
-                         flags.get());
-      HIP_TRY(hipGetLastError());
-      // the live entries, in order, back into the input buffers
-      HIP_TRY(rocprim::select(tmp.get(), sel_bytes, k_out.get(), flags.get(), k_in.get(), count.get(), (size_t)n,
-                              stream));
-      HIP_TRY(rocprim::select(tmp.get(), sel2_bytes, s_out.get(), flags.get(), s_in.get(), count.get(), (size_t)n,
-                              stream));
-      unsigned long long h_count = 0;
-      HIP_TRY(hipMemcpyAsync(&h_count, count.get(), sizeof(h_count), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      nlive = (int64_t)h_count;
-      cs->d_pairs.reserve((size_t)nlive);
-      if (allocs) ++*allocs;
-      if (nlive > 0) {
-        hipLaunchKernelGGL(k_cand_pairs, dim3(grid_of(nlive, num_cus)), dim3(256), 0, stream, nlive, k_in.get(),
-                           s_in.get(), cs->d_pairs.get());
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_cand_rowptr, dim3(grid_of((int64_t)nrows + 1, num_cus)), dim3(256), 0, stream, nrows,
-                           nlive, k_in.get(), cs->d_lptr.get());
-        HIP_TRY(hipGetLastError());
-      }
-      HIP_TRY(hipStreamSynchronize(stream));  // the sort's buffers go; later calls may use another stream
-    } else {
-      cs->d_pairs.reserve(1);
-      if (allocs) ++*allocs;
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
+    candset_upload(cs, stream, allocs, h2d);
+    candset_index(cs, num_cus, stream, allocs);
     cs->device = device;
   }
   CandidateRows R;
@@ -225,6 +246,67 @@ CandidateRows candset_on_device(slimgpu_candset* cs, int device, int num_cus, hi
   R.nrows = cs->nusers;
   R.entries = n;
   return R;
+}
+
+slimgpu_candset* candset_adopt(int32_t ncols, std::vector<int64_t>&& h_cptr, DeviceBuffer<int64_t>&& d_cptr,
+                               DeviceBuffer<int32_t>&& d_cind, int device, int num_cus, hipStream_t stream) {
+  slimgpu_candset* cs = new slimgpu_candset;
+  try {
+    cs->ncols = ncols;
+    cs->nusers = (int32_t)h_cptr.size() - 1;
+    cs->cptr = std::move(h_cptr);
+    cs->host_ids = cs->cptr[cs->nusers] == 0;
+    cs->d_cptr = std::move(d_cptr);
+    cs->d_cind = std::move(d_cind);
+    candset_index(cs, num_cus, stream, nullptr);
+    cs->device = device;
+    return cs;
+  } catch (...) {
+    delete cs;
+    throw;
+  }
+}
+
+void candset_need_ids(slimgpu_candset* cs) {
+  if (!cs || cs->host_ids) return;
+  int now = 0;
+  HIP_TRY(hipGetDevice(&now));
+  HIP_TRY(hipSetDevice(cs->device));
+  cs->cind.resize((size_t)cs->cptr[cs->nusers]);
+  const hipError_t e = hipMemcpy(cs->cind.data(), cs->d_cind.get(), sizeof(int32_t) * cs->cind.size(),
+                                 hipMemcpyDeviceToHost);
+  (void)hipSetDevice(now);
+  HIP_TRY(e);
+  cs->host_ids = true;
+}
+
+int32_t candset_fetch_ids(const char* who, slimgpu_candset* cs) {
+  try {
+    candset_need_ids(cs);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure(who, e);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+}
+
+int32_t candset_rows(slimgpu_candset* cs, int64_t* cptr, int32_t* cind) {
+  if (!cs) return refuse("SLIMGPU_CandSetRows: bad arguments (a candidate set)");
+  if (cind)
+    if (const int32_t rc = candset_fetch_ids("SLIMGPU_CandSetRows", cs); rc != SLIM_OK) return rc;
+  if (cptr) std::copy(cs->cptr.begin(), cs->cptr.end(), cptr);
+  if (cind) std::copy(cs->cind.begin(), cs->cind.end(), cind);
+  return SLIM_OK;
+}
+
+int32_t candset_info(const slimgpu_candset* cs, int32_t* nrows, int32_t* ncols, int64_t* entries) {
+  if (!cs) return refuse("SLIMGPU_CandSetInfo: bad arguments (a candidate set)");
+  if (nrows) *nrows = cs->nusers;
+  if (ncols) *ncols = cs->ncols;
+  if (entries) *entries = cs->cptr[cs->nusers];
+  return SLIM_OK;
 }
 
 size_t fetch_slot_scores(const ScorerWorkspace& ws, const slimgpu_candset* cs, int32_t nsel, const int32_t* users,

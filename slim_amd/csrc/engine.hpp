@@ -163,6 +163,14 @@ HostCandSet candset_host(const slimgpu_candset* cs);
 // (users: ascending, nullptr: users [0, nsel)), the list arguments, and for lists rows of at most SLIMGPU_MAX_LIST
 int32_t candset_check(const char* who, const slimgpu_candset* cs, int32_t model_ncols, int32_t nsel,
                       const int32_t* users, int32_t nrcmds, const int32_t* output, const float* scores);
+// slim_gpu_sample.h: the ids of a set born on the device brought to its host copy (no-op for any other set, and
+// from the second call on; throws HipFail / std::bad_alloc); the rows copied out; the sizes
+void candset_need_ids(slimgpu_candset* cs);
+int32_t candset_fetch_ids(const char* who, slimgpu_candset* cs);  // the same as a status, the failure as the error text
+int32_t candset_rows(slimgpu_candset* cs, int64_t* cptr, int32_t* cind);
+int32_t candset_info(const slimgpu_candset* cs, int32_t* nrows, int32_t* ncols, int64_t* entries);
+// cand_sample.hip: the sampled set of an eval set's users, made on the device; host_csr.cpp has the host form
+slimgpu_candset* evalset_sample_candidates(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed, int32_t* status);
 int32_t score_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_candset* cs, int32_t nrcmds,
                          float* slot_scores, int32_t* output, float* scores, int32_t* counts);
 int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs, int32_t nusers,

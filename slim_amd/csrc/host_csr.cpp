@@ -312,6 +312,59 @@ void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const Hos
   }
 }
 
+void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr_t* tst, int32_t nusers,
+                            const int32_t* users, int32_t nnegs, uint64_t seed, std::vector<int64_t>& cptr,
+                            std::vector<int32_t>& cind) {
+  const int32_t nall = std::min(trn->nrows, tst->nrows);
+  const int32_t nsel = users ? nusers : nall;
+  cptr.assign((size_t)nall + 1, 0);
+  cind.clear();
+  std::vector<uint8_t> mark((size_t)ncols, 0);  // X_u and the accepted ids; restored after each user
+  std::vector<int32_t> marked;
+  std::vector<std::pair<uint64_t, int32_t>> keyed;
+  int32_t next = 0;  // rows [next, u) are empty
+  for (int32_t q = 0; q < nsel; ++q) {
+    const int32_t u = users ? users[q] : q;
+    for (; next < u; ++next) cptr[(size_t)next + 1] = (int64_t)cind.size();
+    next = u + 1;
+    const ssize_t t0 = tst->rowptr[u], t1 = tst->rowptr[u + 1];
+    if (t1 > t0) {
+      marked.clear();
+      auto put = [&](int32_t id) {
+        if (id < 0 || id >= ncols || mark[id]) return;
+        mark[id] = 1;
+        marked.push_back(id);
+      };
+      for (ssize_t h = trn->rowptr[u]; h < trn->rowptr[u + 1]; ++h) put(trn->rowind[h]);
+      for (ssize_t t = t0; t < t1; ++t) put(tst->rowind[t]);
+      const int64_t E = (int64_t)marked.size();
+      const uint64_t base = sample_base(seed, (uint64_t)u);
+      if (2 * (E + nnegs) <= ncols) {
+        int32_t got = 0;
+        for (int64_t d = 0, stop = sample_guard(nnegs); d < stop && got < nnegs; ++d) {
+          const int32_t id = (int32_t)sample_item(sample_key(base, (uint64_t)d), (uint32_t)ncols);
+          if (mark[id]) continue;
+          mark[id] = 1;
+          marked.push_back(id);
+          cind.push_back(id);
+          ++got;
+        }
+      } else {
+        keyed.clear();
+        for (int32_t i = 0; i < ncols; ++i)
+          if (!mark[i]) keyed.emplace_back(sample_key(base, (uint64_t)i), i);
+        const size_t m = std::min<size_t>((size_t)nnegs, keyed.size());
+        std::partial_sort(keyed.begin(), keyed.begin() + m, keyed.end());
+        for (size_t k = 0; k < m; ++k) cind.push_back(keyed[k].second);
+      }
+      for (int32_t id : marked) mark[id] = 0;
+      cind.insert(cind.end(), tst->rowind + t0, tst->rowind + t1);
+    }
+    cptr[(size_t)u + 1] = (int64_t)cind.size();
+  }
+  for (; next < nall; ++next) cptr[(size_t)next + 1] = (int64_t)cind.size();
+}
+
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,
                          const int32_t* rowind) {
   int32_t* mark = xmalloc<int32_t>(ncols);

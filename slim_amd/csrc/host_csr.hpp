@@ -86,6 +86,28 @@ struct HostCandSet {
 void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nrcmds,
                            float* slot_scores, int32_t* output, float* scores, int32_t* counts);
 
+// The sampler of slim_gpu_sample.h, which states it; the device kernel (cand_sample.hip) uses the same three.
+constexpr uint64_t kSampleG = 0x9E3779B97F4A7C15ull;
+#if defined(__HIP__) || defined(__HIPCC__)
+#define SLIMAMD_HD __host__ __device__
+#else
+#define SLIMAMD_HD
+#endif
+SLIMAMD_HD inline uint64_t sample_mix64(uint64_t z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+SLIMAMD_HD inline uint64_t sample_base(uint64_t seed, uint64_t user) { return sample_mix64(seed + kSampleG * (user + 1)); }
+SLIMAMD_HD inline uint64_t sample_key(uint64_t base, uint64_t d) { return sample_mix64(base + kSampleG * (d + 1)); }
+SLIMAMD_HD inline uint32_t sample_item(uint64_t key, uint32_t ncols) { return (uint32_t)(((key >> 32) * ncols) >> 32); }
+inline int64_t sample_guard(int32_t nnegs) { return 16 * (int64_t)nnegs + 1024; }
+// The rows of SLIMGPU_CandSetSample: min(trn rows, tst rows) of them, those of the users listed (ascending;
+// nullptr: all) filled.  The arguments are checked by the caller.
+void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr_t* tst, int32_t nusers,
+                            const int32_t* users, int32_t nnegs, uint64_t seed, std::vector<int64_t>& cptr,
+                            std::vector<int32_t>& cind);
+
 // api.c:215-245.  malloc'd marker array (0 head / 1 tail).
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,
                          const int32_t* rowind);

@@ -10,7 +10,7 @@ int main(int argc, char** argv) {
       {"ifmt", true},    {"binarize", false}, {"optTol", true},  {"niters", true},
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
-      {"evalstride", true}, {"gpukernel", true}, {"help", false}};
+      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"gpukernel", true}, {"help", false}};
   specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() != 3) {
@@ -19,6 +19,8 @@ int main(int argc, char** argv) {
                 "   -nrcmds=i  -nthreads=i  -dbglvl=i  -nomodels (do not write '<l1 l2>.model' files)\n"
                 "   -ngpus=i   (engine extension: R replicated on i GPUs, every model sharded over them)\n"
                 "   -evalstride=i  (engine extension: evaluate users 0, i, 2i, ... only; needs the evaluation in HBM)\n"
+                "   -evalnegs=i -evalseed=i  (engine extension: evaluate 1-vs-k on i sampled negatives per user, drawn on\n"
+                "   the device with that seed (default 1); needs the evaluation in HBM, nrcmds <= 128 and no filter)\n"
                 "   (-nrcmds above 128 is evaluated in HBM from the ranks of the held-out items: no lists are formed)\n"
                 "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n"
                 "%s   (engine extension: every pair is evaluated under the filter; a held-out item it removes is a miss;\n"
@@ -32,8 +34,15 @@ int main(int argc, char** argv) {
   const int nrcmds = a.integer("nrcmds", 10);
   const int stride = a.integer("evalstride", 1);
   if (stride < 1) die("Invalid -evalstride of " + a.str("evalstride", "") + ".");
+  const int evalnegs = a.integer("evalnegs", 0);
+  const long long evalseed = a.has("evalseed") ? std::atoll(a.str("evalseed", "1").c_str()) : 1;
+  if (evalnegs < 0) die("Invalid -evalnegs of " + a.str("evalnegs", "") + ".");
+  if (evalseed < 0 || evalseed > 0xFFFFFFFFll) die("Invalid -evalseed of " + a.str("evalseed", "") + ".");
   const bool filtered = filter_options(a);
   filter_files_exist(a);
+  if (evalnegs > 0 && filtered) die("-evalnegs takes no item filter: candidate rows are scored as they are.");
+  if (evalnegs > 0 && nrcmds > 128)
+    die("-evalnegs needs nrcmds <= 128 (the candidate lists use the eval set's cutoffs), not " + std::to_string(nrcmds) + ".");
   Csr trn = read_matrix(a.pos[0], fmt), tst = read_matrix(a.pos[1], fmt);
   if (a.has("binarize")) trn.has_val = false;
   const std::string sim = a.str("simtype", "cos");
@@ -122,7 +131,26 @@ int main(int argc, char** argv) {
     SLIMGPU_MatrixInfo(R, &rrows, &rcols, &rnnz);
     flt = read_filter(a, rcols, fmt);
   }
+  // sampled negatives: the set is drawn once, on the device, from the eval set's users; never a fall-back to the
+  // full-catalogue figures
+  slimgpu_candset_t* cands = nullptr;
+  if (evalnegs > 0) {
+    if (!evalset)
+      die(std::string("-evalnegs needs the evaluation in HBM (one GPU, nrcmds >= 1, SLIM_GPU_RESIDENT and "
+                      "SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ") +
+          (!resident ? std::string("the models of this grid do not stay in HBM")
+           : evr_env && std::atoi(evr_env) == 0 ? std::string("SLIM_GPU_EVAL_RESIDENT=0")
+           : nrcmds < 1 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
+    if (SLIMGPU_EvalSetSampleCandidates(evalset, evalnegs, (uint64_t)evalseed, &cands) != SLIM_OK)
+      die(std::string("-evalnegs: ") + SLIMGPU_LastError());
+  }
   if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
+  if (cands) {
+    int64_t entries = 0;
+    SLIMGPU_CandSetInfo(cands, nullptr, nullptr, &entries);
+    std::printf("  sampled negatives: nnegs %d, seed %llu, %lld candidate entries\n", evalnegs,
+                (unsigned long long)evalseed, (long long)entries);
+  }
   if (filtered)
     std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)flt.allowed, rcols,
                 (long long)flt.excluded);
@@ -169,9 +197,10 @@ int main(int argc, char** argv) {
     int32_t env[3];
     // (one list length: the filtered call's only row is SLIMGPU_ModelEvaluate's; a null filter is no filter)
     const bool evaluated =
-        evalset && (ranked ? SLIMGPU_ModelEvaluateRankedFiltered(evalset, dmodel, flt.handle, 1, &cutoff, em, env)
-                           : SLIMGPU_ModelEvaluateAtFiltered(evalset, dmodel, flt.handle, 1, em, env)) == SLIM_OK;
-    if (!evaluated && (stride > 1 || filtered)) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
+        evalset && (cands    ? SLIMGPU_ModelEvaluateCandidates(evalset, dmodel, cands, 1, em, env)
+                    : ranked ? SLIMGPU_ModelEvaluateRankedFiltered(evalset, dmodel, flt.handle, 1, &cutoff, em, env)
+                             : SLIMGPU_ModelEvaluateAtFiltered(evalset, dmodel, flt.handle, 1, em, env)) == SLIM_OK;
+    if (!evaluated && (stride > 1 || filtered || cands)) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
     if (evaluated) {
       e.hr = em[0]; e.hr_head = em[1]; e.hr_tail = em[2]; e.arhr = em[3];
       e.nvalid = env[0]; e.nvalid_head = env[1]; e.nvalid_tail = env[2];
@@ -199,6 +228,7 @@ int main(int argc, char** argv) {
   std::printf("\nDone.\n------------------------------------------------------------------\n");
   SLIM_FreeModel(&model);
   SLIMGPU_ModelFree(&dmodel);
+  SLIMGPU_CandSetFree(cands);
   SLIMGPU_EvalSetFree(&evalset);
   SLIMGPU_FilterFree(flt.handle);
   std::free(fmarker);

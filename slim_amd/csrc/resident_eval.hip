@@ -23,6 +23,7 @@ struct slimgpu_evalset {
   slimgpu_matrix_t* mat = nullptr;
   int device = 0;
   int32_t nsel = 0, fm_ncols = 0;  // positions evaluated: the listed users, or every user
+  int32_t nall = 0;                // rows of the staged test matrix: min(rows of the matrix, rows of tst)
   bool listed = false;             // d_users holds the user of every position (else position q is user q)
   slimamd::Cutoffs cut = {};       // list lengths; the lists scored have the last one's
   int64_t hist_entries = 0;  // history entries of the evaluated users: the model rows one evaluation streams
@@ -136,6 +137,7 @@ slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* 
     es->mat = mat; es->device = R.device; es->cut = cut; es->fm_ncols = fm_ncols;
     es->listed = users != nullptr;
     es->nsel = users ? nusers : nall;
+    es->nall = nall;
     const int32_t nsel = es->nsel;
     es->tst = stage_csr(tst, nall, /*values=*/false, stream);
     es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
@@ -268,6 +270,22 @@ slimgpu_evalset_t* evalset_create_ranked(slimgpu_matrix_t* mat, const slim_csr_t
 }
 
 int64_t evalset_entries(const slimgpu_evalset_t* es) { return es ? es->entries : -1; }
+
+int32_t evalset_rows(const slimgpu_evalset_t* es, EvalSetRows* out) {
+  DeviceCsrView R;
+  if (!es || !out || matrix_csr_view(es->mat, &R) != SLIM_OK) return SLIM_ERROR_INPUT;
+  EvalSetRows V;
+  V.device = es->device; V.num_cus = R.num_cus; V.stream = static_cast<hipStream_t>(R.stream);
+  V.merged = R.merged;
+  V.ncols = R.ncols; V.nall = es->nall; V.nsel = es->nsel;
+  V.d_users = es->listed ? es->d_users.get() : nullptr;
+  V.h_users = es->listed ? es->h_users.data() : nullptr;
+  V.hptr = R.d_ptr; V.hind = R.d_ind;
+  V.tptr = es->tst.ptr.get(); V.tind = es->tst.ind.get();
+  V.max_hist = es->max_hist; V.max_test = es->max_test; V.test_entries = es->entries;
+  *out = V;
+  return SLIM_OK;
+}
 void evalset_free(slimgpu_evalset_t* es) { delete es; }
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es) { return es ? es->cut.n : 0; }
 

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <string>
 #include <variant>
+#include <vector>
 
 #include "engine.hpp"
 #include "eval_terms.hpp"
@@ -93,6 +94,26 @@ struct CandidateRows {
 // freed.  *allocs grows by the device allocations this made, *h2d (optional) by the bytes it sent.
 CandidateRows candset_on_device(slimgpu_candset* cs, int device, int num_cus, hipStream_t stream, int* allocs,
                                 int64_t* h2d = nullptr);
+// A set whose rows were made on the current device, `device` (cand_sample.hip): takes the rows over (d_cptr: nrows + 1,
+// d_cind: the entries; h_cptr: the row pointer's host copy), indexes them on `stream` as candset_on_device indexes
+// uploaded rows and drains the stream.  The host copy of the ids is fetched on first need (engine.hpp:
+// candset_need_ids).  Throws HipFail / std::bad_alloc.
+slimgpu_candset* candset_adopt(int32_t ncols, std::vector<int64_t>&& h_cptr, DeviceBuffer<int64_t>&& d_cptr,
+                               DeviceBuffer<int32_t>&& d_cind, int device, int num_cus, hipStream_t stream);
+// What the sampler (cand_sample.hip) reads of an eval set (resident_eval.hip): its users, the resident history
+// rows, the staged test rows.  nall: rows of the staged test matrix, the rows a sampled set has.
+struct EvalSetRows {
+  int device = 0, num_cus = 256;
+  hipStream_t stream = nullptr;
+  bool merged = false;
+  int32_t ncols = 0, nall = 0, nsel = 0;
+  const int32_t* d_users = nullptr;  // nullptr: position q is user q
+  const int32_t* h_users = nullptr;
+  const int64_t* hptr = nullptr; const int32_t* hind = nullptr;
+  const int64_t* tptr = nullptr; const int32_t* tind = nullptr;
+  int64_t max_hist = 0, max_test = 0, test_entries = 0;
+};
+int32_t evalset_rows(const slimgpu_evalset_t* es, EvalSetRows* out);
 struct CandTargets {  // the slot scores of the positions' candidate rows into ws.cand (cleared first, whole)
   CandidateRows rows;
 };

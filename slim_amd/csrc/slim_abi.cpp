@@ -176,6 +176,10 @@ int32_t Py_SLIM_Learn(slim_t* trnhandle, int32_t* ioptions, double* doptions,
   return SLIM_OK;
 }
 
+static const char kEvalNegsNeeds[] =
+    "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGS needs the candidate evaluation in HBM (cd on one GPU, no filter, "
+    "nrcmds <= 128, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ";
+
 // Py_SLIM_Mselect is this with no filter.  With one (slim_gpu_filter.h) every pair is evaluated under it, which
 // only the evaluation in HBM can do: where that is not to be had the call fails before the first solve.
 int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
@@ -207,6 +211,29 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
   int32_t status = SLIM_ERROR;
   if (ioptions == nullptr || ioptions[SLIM_OPTION_GPU_NGPUS] == -1)
     if (const char* e = std::getenv("SLIM_GPU_NGPUS")) base.ngpus = std::max(1, std::atoi(e));
+  // Sampled negatives (slots 23 / 24, slim_gpu_cand.h): the candidate set is drawn once, on the device, from the
+  // eval set's users, and every pair is evaluated on it.  Whatever stands in the way is refused here, before the
+  // first solve: there is no silent fall-back to the full-catalogue figures.
+  const int32_t evalnegs = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALNEGS] == -1) ? 0 : ioptions[SLIM_OPTION_GPU_EVALNEGS];
+  const uint64_t evalseed = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALSEED] == -1)
+                                ? 1 : (uint64_t)(uint32_t)ioptions[SLIM_OPTION_GPU_EVALSEED];
+  if (evalnegs != 0) {
+    const char* res0 = std::getenv("SLIM_GPU_RESIDENT");
+    const char* evr0 = std::getenv("SLIM_GPU_EVAL_RESIDENT");
+    std::string why;
+    if (evalnegs < 0) why = "SLIM_OPTION_GPU_EVALNEGS must be at least 0, not " + std::to_string(evalnegs);
+    else if (filter) why = "a candidate filter is given: candidate rows take no filter";
+    else if (admm) why = "the ADMM solver leaves no model in HBM";
+    else if (base.ngpus > 1) why = "the grid runs on several GPUs";
+    else if (res0 && std::atoi(res0) == 0) why = "SLIM_GPU_RESIDENT=0 keeps the models on the host";
+    else if (evr0 && std::atoi(evr0) == 0) why = "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host";
+    else if (nrcmds < 1 || nrcmds > 128)
+      why = "nrcmds is " + std::to_string(nrcmds) + ": the candidate lists use the eval set's cutoffs, 1 to 128";
+    if (!why.empty()) {
+      set_error(std::string(kEvalNegsNeeds) + why);
+      return SLIM_ERROR_INPUT;
+    }
+  }
   slimgpu_matrix_t* mat =
       admm ? nullptr : multi_from_host(trn->nrows, trn->rowptr, trn->rowind, trn->rowval, base, &status);
   if (!mat && !admm) return status;
@@ -290,6 +317,25 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
     }
   }
 
+  slimgpu_candset_t* cands = nullptr;
+  if (evalnegs > 0) {
+    std::string why;
+    if (!evalset || ranked) {  // (a matrix with merged duplicates, ...)
+      why = SLIMGPU_LastError();
+      if (why.empty()) why = "the eval set could not be made";
+    } else {
+      cands = evalset_sample_candidates(evalset, evalnegs, evalseed, &status);
+      if (!cands) why = SLIMGPU_LastError();
+    }
+    if (!cands) {
+      set_error(std::string(kEvalNegsNeeds) + why);
+      evalset_free(evalset);
+      std::free(fmarker);
+      matrix_free(mat);
+      return SLIM_ERROR_INPUT;
+    }
+  }
+
   std::printf("------------------------------------------------------------------\n");
   std::printf("SLIM, version %s (MI355X engine)\n", SLIM_VERSION);
   std::printf("------------------------------------------------------------------\n");
@@ -307,6 +353,12 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
     }
     std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)allowed, hflt.ncols,
                 (long long)(hflt.xptr ? hflt.xptr[hflt.xusers] : 0));
+  }
+  if (cands) {
+    int64_t entries = 0;
+    candset_info(cands, nullptr, nullptr, &entries);
+    std::printf("  sampled negatives: nnegs %d, seed %llu, %lld candidate entries\n", evalnegs,
+                (unsigned long long)evalseed, (long long)entries);
   }
   std::printf("\nEstimating & evaluating models...\n\n");
 
@@ -342,9 +394,11 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
           break;
         }
         model_nnz_now = (ssize_t)model_nnz(dmodel);
-        evaluated = evalset && (ranked ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev, filter)
-                                       : model_evaluate(evalset, dmodel, 1, &ev, filter)) == SLIM_OK;
-        if (!evaluated && (stride > 1 || filter)) {  // (no silent evaluation of everybody, or without the filter)
+        evaluated = evalset && (cands    ? model_evaluate_candidates(evalset, dmodel, cands, 1, &ev)
+                                : ranked ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev, filter)
+                                         : model_evaluate(evalset, dmodel, 1, &ev, filter)) == SLIM_OK;
+        // (no silent evaluation of everybody, without the filter, or on the whole catalogue)
+        if (!evaluated && (stride > 1 || filter || cands)) {
           rc = SLIM_ERROR;
           break;
         }
@@ -420,6 +474,7 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
   std::printf("\nDone.\n------------------------------------------------------------------\n");
   csr_free(model);
   model_free(dmodel);
+  candset_free(cands);
   evalset_free(evalset);
   std::free(fmarker);
   matrix_free(mat);
@@ -955,8 +1010,80 @@ int32_t Py_SLIM_ScoreCandidates(slim_t* model, slim_t* trnhandle, slimgpu_candse
     if (rc == SLIM_OK || policy == 2) return rc;
   }
   if (W->rowptr[W->nrows] > 0 && !W->rowval) return SLIM_ERROR;
+  // (a set born on the device brings its ids down on first need, as SLIMGPU_CandSetRows does)
+  if (const int32_t rc = candset_fetch_ids("Py_SLIM_ScoreCandidates", cs); rc != SLIM_OK) return rc;
   score_candidates_host(W, trn, candset_host(cs), nrcmds, slot_scores, output, scores, counts);
   return SLIM_OK;
+}
+
+// --------------------------------------------------- slim_gpu_sample.h ------
+
+int32_t SLIMGPU_EvalSetSampleCandidates(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed,
+                                        slimgpu_candset_t** out) {
+  set_error("");
+  if (!out) {
+    set_error("SLIMGPU_EvalSetSampleCandidates: bad arguments (out is NULL)");
+    return SLIM_ERROR_INPUT;
+  }
+  int32_t status = SLIM_ERROR;
+  slimgpu_candset_t* cs = evalset_sample_candidates(es, nnegs, seed, &status);
+  if (cs) *out = cs;
+  return status;
+}
+
+int32_t SLIMGPU_CandSetSample(int32_t ncols, slim_t* trnhandle, slim_t* tsthandle, int32_t nusers,
+                              const int32_t* users, int32_t nnegs, uint64_t seed, slimgpu_candset_t** out) {
+  set_error("");
+  const std::string who = "SLIMGPU_CandSetSample: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return SLIM_ERROR_INPUT;
+  };
+  const slim_csr_t* trn = as_csr(trnhandle);
+  const slim_csr_t* tst = as_csr(tsthandle);
+  if (!out || !trn || !tst || !trn->rowptr || !tst->rowptr) return bad("bad arguments (a history, test rows, out)");
+  if (ncols < 1) return bad("ncols must be at least 1, not " + std::to_string(ncols));
+  if (nnegs < 1) return bad("nnegs must be at least 1, not " + std::to_string(nnegs));
+  const int32_t nall = std::min(trn->nrows, tst->nrows);
+  if (users ? nusers < 1 : nusers != 0)
+    return bad(users ? "a user list needs at least one user" : "nusers must be 0 without a user list");
+  for (int32_t q = 0; q < nusers; ++q) {
+    if (users[q] < 0 || users[q] >= nall)
+      return bad("user " + std::to_string(users[q]) + " is outside [0, " + std::to_string(nall) + ")");
+    if (q > 0 && users[q] <= users[q - 1]) return bad("the user ids must ascend strictly");
+  }
+  int64_t max_test = 0;
+  for (int32_t q = 0, n = users ? nusers : nall; q < n; ++q) {
+    const int32_t u = users ? users[q] : q;
+    max_test = std::max<int64_t>(max_test, tst->rowptr[u + 1] - tst->rowptr[u]);
+  }
+  if ((int64_t)nnegs + max_test > SLIMGPU_MAX_LIST)
+    return bad("nnegs " + std::to_string(nnegs) + " and the longest selected test row, " + std::to_string(max_test) +
+               " entries, give a candidate row above " + std::to_string(SLIMGPU_MAX_LIST) +
+               ": the evaluation needs lists");
+  try {
+    std::vector<int64_t> cptr;
+    std::vector<int32_t> cind;
+    sample_candidates_host(ncols, trn, tst, nusers, users, nnegs, seed, cptr, cind);
+    cind.push_back(0);  // (an empty set still has an address)
+    int32_t status = SLIM_ERROR;
+    slimgpu_candset_t* cs = candset_create(ncols, nall, cptr.data(), cind.data(), &status);
+    if (cs) *out = cs;
+    return status;
+  } catch (const std::bad_alloc&) {
+    set_error(who + "out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+}
+
+int32_t SLIMGPU_CandSetRows(slimgpu_candset_t* cs, int64_t* cptr, int32_t* cind) {
+  set_error("");
+  return candset_rows(cs, cptr, cind);
+}
+
+int32_t SLIMGPU_CandSetInfo(slimgpu_candset_t* cs, int32_t* nrows, int32_t* ncols, int64_t* entries) {
+  set_error("");
+  return candset_info(cs, nrows, ncols, entries);
 }
 
 int32_t SLIMGPU_LastListStats(slimgpu_list_stats_t* out) {

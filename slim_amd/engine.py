@@ -236,6 +236,35 @@ class CandidateSet(object):
             self.handle = C.c_void_p()
             raise ValueError("SLIMGPU_CandSetCreate failed (%d): %s" % (st, _lib.last_error()))
 
+    @classmethod
+    def from_handle(cls, handle, lib=None):
+        """Adopt a set this class did not create (SLIMGPU_EvalSetSampleCandidates, SLIMGPU_CandSetSample); the object
+        owns the handle from here on.  Only the row pointer is read: the ids of a set born on the device stay there
+        until rows() asks."""
+        self = cls.__new__(cls)
+        self._lib = lib or _lib.load()
+        self.handle = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        nrows, ncols, size = C.c_int32(), C.c_int32(), C.c_int64()
+        st = self._lib.SLIMGPU_CandSetInfo(self.handle, C.byref(nrows), C.byref(ncols), C.byref(size))
+        if st != SLIM_OK:
+            self.handle = None
+            raise ValueError("SLIMGPU_CandSetInfo failed (%d): %s" % (st, _lib.last_error()))
+        self.ncols, self.nusers, self.size = ncols.value, nrows.value, size.value
+        self.indptr = np.zeros(self.nusers + 1, np.int64)
+        st = self._lib.SLIMGPU_CandSetRows(self.handle, self.indptr.ctypes.data_as(C.c_void_p), None)
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_CandSetRows failed (%d): %s" % (st, _lib.last_error()))
+        return self
+
+    def rows(self):
+        """SLIMGPU_CandSetRows: (indptr, indices), copies of the set's rows (a set born on the device brings its ids
+        down on the first call)."""
+        ind = np.zeros(self.size + 1, np.int32)
+        st = self._lib.SLIMGPU_CandSetRows(self.handle, None, ind.ctypes.data_as(C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_CandSetRows failed (%d): %s" % (st, _lib.last_error()))
+        return self.indptr.copy(), ind[:self.size]
+
     def close(self):
         if self.handle is not None and self.handle.value:
             self._lib.SLIMGPU_CandSetFree(self.handle)
@@ -246,6 +275,29 @@ class CandidateSet(object):
             self.close()
         except Exception:   # noqa: BLE001 -- interpreter shutdown
             pass
+
+
+def sample_candidates(trn, tst, nnegs, seed=1, users=None, ncols=None, lib=None):
+    """SLIMGPU_CandSetSample (include/slim_gpu_sample.h): the 1-vs-k candidate set made on the host -- per user with a
+    test row `nnegs` sampled items outside its history and test row, then the test row.  trn / tst: scipy matrices,
+    one row per user; users: ascending user ids (None: every user); ncols: the catalogue (None: the wider of the
+    two).  The rows equal those of Evaluator.sample_candidates for the same seed."""
+    lib = lib or _lib.load()
+    trn, tst = sp.csr_matrix(trn), sp.csr_matrix(tst)
+    ncols = max(trn.shape[1], tst.shape[1]) if ncols is None else int(ncols)
+    sel = None if users is None else np.ascontiguousarray(users, dtype=np.int32).ravel()
+    ht, hs = _wrap_rows(lib, trn), _wrap_rows(lib, tst)
+    h = C.c_void_p()
+    try:
+        st = lib.SLIMGPU_CandSetSample(ncols, ht, hs, 0 if sel is None else sel.size,
+                                       None if sel is None else sel.ctypes.data_as(C.c_void_p), int(nnegs),
+                                       int(seed), C.byref(h))
+    finally:
+        lib.Py_csr_free(ht)
+        lib.Py_csr_free(hs)
+    if st != SLIM_OK:
+        raise ValueError("SLIMGPU_CandSetSample failed (%d): %s" % (st, _lib.last_error()))
+    return CandidateSet.from_handle(h, lib=lib)
 
 
 def eval_stats(lib=None):
@@ -365,6 +417,17 @@ class Evaluator(object):
         return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
+
+    def sample_candidates(self, nnegs, seed=1):
+        """SLIMGPU_EvalSetSampleCandidates: the 1-vs-k CandidateSet of this eval set's users, made on the device --
+        `nnegs` sampled items outside the user's history and test row, then the test row (a score tie goes to the
+        negative).  Reproducible from the seed; evaluate_candidates(model, that set) gives HR / ARHR on sampled
+        negatives.  It costs about what evaluate() costs: a protocol, not a speed-up."""
+        h = C.c_void_p()
+        st = self._lib.SLIMGPU_EvalSetSampleCandidates(self.handle, int(nnegs), int(seed), C.byref(h))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_EvalSetSampleCandidates failed (%d): %s" % (st, _lib.last_error()))
+        return CandidateSet.from_handle(h, lib=self._lib)
 
     def prepass_ms(self):
         """Milliseconds of the pre-pass (the test entries' scores and keys) of the most recent ranked call."""
@@ -586,6 +649,11 @@ class DeviceMatrix(object):
         CSR taken as it is, or (indptr, indices)) for ResidentModel.score_candidates and
         Evaluator.evaluate_candidates."""
         return CandidateSet(self.ncols, C_rows, lib=self._lib)
+
+    def sample_candidates(self, trn, tst, nnegs, seed=1, users=None):
+        """SLIMGPU_CandSetSample over this matrix's items: the host form of Evaluator.sample_candidates (trn: the
+        scipy rows this matrix was staged from; the same rows for the same seed)."""
+        return sample_candidates(trn, tst, nnegs, seed=seed, users=users, ncols=self.ncols, lib=self._lib)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)
