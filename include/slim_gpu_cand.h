@@ -27,6 +27,8 @@
  * held-out items stand behind the negatives, so under "score descending, then slot ascending" a score tie goes to
  * the negative: the pessimistic choice.  The option slots below put Py_SLIM_Mselect on that protocol.
  *
+ * Explanations (slim_gpu_explain.h, included below): the terms behind a slot score, the largest of them per slot.
+ *
  * Not built: the neg-file protocol of slim_predict (random tie order), popularity-weighted negatives.
  * SLIMGPU_Predict1vsK is unchanged (rows of one width, up to 1024).
  */
@@ -87,5 +89,6 @@ enum {
 #endif
 
 #include "slim_gpu_sample.h"
+#include "slim_gpu_explain.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_CAND_H_ */

@@ -260,6 +260,20 @@ _SAMPLE_SIGNATURES = {
 
 SAMPLE_SYMBOLS = tuple(_SAMPLE_SIGNATURES)
 
+# explanations: the history items behind a candidate's score (include/slim_gpu_explain.h); why_items / why_terms /
+# support / users are passed as pointers (any may be None)
+_EXPLAIN_SIGNATURES = {
+    "SLIMGPU_ExplainCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "SLIMGPU_MatrixExplainCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "Py_SLIM_ExplainCandidates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+}
+
+EXPLAIN_SYMBOLS = tuple(_EXPLAIN_SIGNATURES)
+MAX_WHY = 16            # SLIMGPU_MAX_WHY
+
 _lib = None
 
 
@@ -277,7 +291,8 @@ def load():
                               list(_EVAL_AT_SIGNATURES.items()) + list(_PLANES_SIGNATURES.items()) +
                               list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
                               list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
-                              list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items())):
+                              list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items()) +
+                              list(_EXPLAIN_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

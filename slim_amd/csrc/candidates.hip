@@ -30,6 +30,7 @@ struct slimgpu_candset {
   slimamd::DeviceBuffer<int64_t> d_cptr, d_lptr;
   slimamd::DeviceBuffer<int32_t> d_cind;
   slimamd::DeviceBuffer<int2> d_pairs;
+  slimamd::ExplainWorkspace why;  // explain.hip: the outputs of the explanations of this set's rows, on `device`
 };
 
 namespace slimamd {
@@ -236,6 +237,7 @@ CandidateRows candset_on_device(slimgpu_candset* cs, int device, int num_cus, hi
   if (cs->device != device) {  // first use here: the copy of another device goes
     candset_need_ids(cs);      // (a set born on that device: its ids come down before they go)
     cs->d_cptr.reset(); cs->d_lptr.reset(); cs->d_cind.reset(); cs->d_pairs.reset();
+    cs->why = ExplainWorkspace();
     cs->device = -1;
     candset_upload(cs, stream, allocs, h2d);
     candset_index(cs, num_cus, stream, allocs);
@@ -291,6 +293,9 @@ int32_t candset_fetch_ids(const char* who, slimgpu_candset* cs) {
     return SLIM_ERROR_MEMORY;
   }
 }
+
+ExplainWorkspace& candset_explain_workspace(slimgpu_candset* cs) { return cs->why; }
+const int64_t* candset_row_pointer(const slimgpu_candset* cs) { return cs->cptr.data(); }
 
 int32_t candset_rows(slimgpu_candset* cs, int64_t* cptr, int32_t* cind) {
   if (!cs) return refuse("SLIMGPU_CandSetRows: bad arguments (a candidate set)");

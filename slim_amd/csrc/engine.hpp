@@ -176,6 +176,14 @@ int32_t score_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_can
 int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs, int32_t nusers,
                                 const int32_t* users, int32_t nrcmds, float* slot_scores, int32_t* output,
                                 float* scores, int32_t* counts);
+// explain.hip (slim_gpu_explain.h): the terms behind the slot scores; why_items / why_terms (both or neither) and
+// support may be null.  SLIM_ERROR_INPUT / SLIM_ERROR_MEMORY with every output untouched.
+int32_t explain_check(const char* who, int32_t nwhy, const int32_t* why_items, const float* why_terms);
+int32_t explain_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_candset* cs, int32_t nwhy,
+                           int32_t* why_items, float* why_terms, int32_t* support);
+int32_t matrix_explain_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs,
+                                  int32_t nusers, const int32_t* users, int32_t nwhy, int32_t* why_items,
+                                  float* why_terms, int32_t* support);
 slimgpu_list_stats_t& last_list_stats();
 int32_t model_row_view(const slimgpu_model* w, DeviceRowView* out);
 // the CSR of a staged matrix where it lies (the history of the resident scorer)

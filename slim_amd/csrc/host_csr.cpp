@@ -312,6 +312,53 @@ void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const Hos
   }
 }
 
+void explain_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nwhy,
+                             int32_t* why_items, float* why_terms, int32_t* support) {
+  const int32_t ncols = W->ncols, nrows = W->nrows;
+  std::vector<int32_t> slot_of(ncols, -2);  // -2: not a candidate
+  std::vector<int32_t> count, item;         // per slot: its terms; its places, [slot][nwhy]
+  std::vector<float> term;
+  for (int32_t u = 0; u < trn->nrows; ++u) {
+    const int32_t* cand = S.cind + S.cptr[u];
+    const int32_t len = (int32_t)(S.cptr[u + 1] - S.cptr[u]);
+    count.assign(len, 0);
+    item.resize((size_t)len * nwhy);
+    term.resize((size_t)len * nwhy);
+    for (int32_t c = 0; c < len; ++c)
+      if (cand[c] >= 0 && cand[c] < ncols) slot_of[cand[c]] = c;  // (a repeated id: the last occurrence)
+    for (ssize_t h = trn->rowptr[u]; h < trn->rowptr[u + 1]; ++h) {
+      const int32_t i = trn->rowind[h];
+      if (i < 0 || i >= nrows) continue;
+      const float rating = trn->rowval ? trn->rowval[h] : 1.0f;
+      for (ssize_t j = W->rowptr[i]; j < W->rowptr[i + 1]; ++j) {
+        const int32_t s = slot_of[W->rowind[j]];
+        if (s < 0) continue;
+        const float t = rating * W->rowval[j];
+        // positions ascend, so among equal terms this one is the last: it goes in front of the first smaller one
+        const int32_t have = std::min(count[s]++, nwhy);
+        int32_t* si = item.data() + (size_t)s * nwhy;
+        float* st = term.data() + (size_t)s * nwhy;
+        int32_t k = have;
+        while (k > 0 && st[k - 1] < t) --k;
+        if (k >= nwhy) continue;
+        for (int32_t m = std::min(have, nwhy - 1); m > k; --m) { si[m] = si[m - 1]; st[m] = st[m - 1]; }
+        si[k] = i; st[k] = t;
+      }
+    }
+    for (int32_t c = 0; c < len; ++c) {
+      const int64_t e = S.cptr[u] + c;
+      const bool live = cand[c] >= 0 && cand[c] < ncols && slot_of[cand[c]] == c;
+      if (support) support[e] = live ? count[c] : 0;
+      if (!live || !why_items) continue;
+      const int32_t n = std::min(count[c], nwhy);
+      std::copy(item.begin() + (size_t)c * nwhy, item.begin() + (size_t)c * nwhy + n, why_items + e * nwhy);
+      std::copy(term.begin() + (size_t)c * nwhy, term.begin() + (size_t)c * nwhy + n, why_terms + e * nwhy);
+    }
+    for (int32_t c = 0; c < len; ++c)
+      if (cand[c] >= 0 && cand[c] < ncols) slot_of[cand[c]] = -2;
+  }
+}
+
 void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr_t* tst, int32_t nusers,
                             const int32_t* users, int32_t nnegs, uint64_t seed, std::vector<int64_t>& cptr,
                             std::vector<int32_t>& cind) {

@@ -86,6 +86,14 @@ struct HostCandSet {
 void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nrcmds,
                            float* slot_scores, int32_t* output, float* scores, int32_t* counts);
 
+// slim_gpu_explain.h on the host, the plain loop: per user the slot table of score_candidates_host, per history
+// position a walk of the model row and, per live slot it touches, a count and a bounded insertion into the slot's
+// places (term descending, then position ascending; -0.0f ties with 0.0f).  Users [0, trn->nrows).  why_items and
+// why_terms ([entries][nwhy], both or neither) and support ([entries]) are optional; only the first
+// min(nwhy, support) places of a slot are written, and support = 0 for a slot that carries nothing.
+void explain_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nwhy,
+                             int32_t* why_items, float* why_terms, int32_t* support);
+
 // The sampler of slim_gpu_sample.h, which states it; the device kernel (cand_sample.hip) uses the same three.
 constexpr uint64_t kSampleG = 0x9E3779B97F4A7C15ull;
 #if defined(__HIP__) || defined(__HIPCC__)

@@ -114,6 +114,24 @@ struct EvalSetRows {
   int64_t max_hist = 0, max_test = 0, test_entries = 0;
 };
 int32_t evalset_rows(const slimgpu_evalset_t* es, EvalSetRows* out);
+// Explanations (slim_gpu_explain.h): the device outputs of explain.hip and their host images, grow-only like
+// ScorerWorkspace.  They belong to the candidate set (candidates.hip), live on the device of its copy and go with it.
+struct ExplainWorkspace {
+  DeviceBuffer<int32_t> items, support, users;
+  DeviceBuffer<float> terms;
+  DeviceBuffer<int64_t> obase;  // a user list: where every position's row starts in the outputs
+  std::vector<int32_t> h_items, h_support;
+  std::vector<float> h_terms;
+  int allocs = 0;  // device allocations since the caller last cleared it
+  template <class T>
+  T* need(DeviceBuffer<T>& b, size_t n) {
+    if (b.bytes() < sizeof(T) * (n ? n : 1)) ++allocs;
+    return b.reserve(n);
+  }
+  size_t held() const { return items.bytes() + support.bytes() + users.bytes() + terms.bytes() + obase.bytes(); }
+};
+ExplainWorkspace& candset_explain_workspace(slimgpu_candset* cs);
+const int64_t* candset_row_pointer(const slimgpu_candset* cs);  // the host copy, nusers + 1
 struct CandTargets {  // the slot scores of the positions' candidate rows into ws.cand (cleared first, whole)
   CandidateRows rows;
 };
@@ -127,6 +145,7 @@ enum ScorerPath : int {
   kRank = 3,     // the chunk kernel in rank mode
   kLong = 4,     // the chunk kernel's long-list form
   kCand = 5,     // the chunk kernel scoring candidate rows (slim_gpu_cand.h)
+  kExplain = 6,  // the explanation kernel (slim_gpu_explain.h, explain.hip)
 };
 struct ChunkPlan {  // geometry of the chunk kernel for a model / history pair: key width, chunk width, LDS
   bool key32 = false;

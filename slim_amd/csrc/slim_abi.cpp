@@ -1016,6 +1016,43 @@ int32_t Py_SLIM_ScoreCandidates(slim_t* model, slim_t* trnhandle, slimgpu_candse
   return SLIM_OK;
 }
 
+// -------------------------------------------------- slim_gpu_explain.h ------
+
+int32_t SLIMGPU_ExplainCandidates(slim_t* model, slim_t* trn, slimgpu_candset_t* cs, int32_t nwhy, int32_t* why_items,
+                                  float* why_terms, int32_t* support) {
+  set_error("");
+  return explain_candidates(as_csr(model), as_csr(trn), cs, nwhy, why_items, why_terms, support);
+}
+
+int32_t SLIMGPU_MatrixExplainCandidates(const slimgpu_model_t* model, slimgpu_matrix_t* mat, slimgpu_candset_t* cs,
+                                        int32_t nusers, const int32_t* users, int32_t nwhy, int32_t* why_items,
+                                        float* why_terms, int32_t* support) {
+  set_error("");
+  return matrix_explain_candidates(model, mat, cs, nusers, users, nwhy, why_items, why_terms, support);
+}
+
+// the policy of Py_SLIM_ScoreCandidates; both sides give the same explanations
+int32_t Py_SLIM_ExplainCandidates(slim_t* model, slim_t* trnhandle, slimgpu_candset_t* cs, int32_t nwhy,
+                                  int32_t* why_items, float* why_terms, int32_t* support) {
+  const char* who = "Py_SLIM_ExplainCandidates";
+  const slim_csr_t* W = as_csr(model);
+  const slim_csr_t* trn = as_csr(trnhandle);
+  if (!W || !trn || !W->rowptr || !trn->rowptr) return SLIM_ERROR;
+  set_error("");
+  if (const int32_t rc = explain_check(who, nwhy, why_items, why_terms); rc != SLIM_OK) return rc;
+  if (const int32_t rc = candset_check(who, cs, W->ncols, trn->nrows, nullptr, 0, nullptr, nullptr); rc != SLIM_OK)
+    return rc;
+  const int policy = predict_policy();
+  if (policy == 2 || (policy == 1 && trn->nrows > 0 && device_count() > 0)) {
+    const int32_t rc = explain_candidates(W, trn, cs, nwhy, why_items, why_terms, support);
+    if (rc == SLIM_OK || policy == 2) return rc;
+  }
+  if (W->rowptr[W->nrows] > 0 && !W->rowval) return SLIM_ERROR;
+  if (const int32_t rc = candset_fetch_ids(who, cs); rc != SLIM_OK) return rc;
+  explain_candidates_host(W, trn, candset_host(cs), nwhy, why_items, why_terms, support);
+  return SLIM_OK;
+}
+
 // --------------------------------------------------- slim_gpu_sample.h ------
 
 int32_t SLIMGPU_EvalSetSampleCandidates(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed,

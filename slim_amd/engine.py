@@ -160,6 +160,52 @@ class ResidentModel(object):
             return slot
         return slot, (ids[:n * k].reshape(n, k), scores[:n * k].reshape(n, k), counts[:n])
 
+    def explain(self, device_matrix, cset, users=None, nwhy=3):
+        """SLIMGPU_MatrixExplainCandidates: which history items carry the score of every candidate of a CandidateSet
+        (include/slim_gpu_explain.h), for every row of the staged matrix or for the rows in `users` (strictly
+        ascending ids; the candidate row of a user goes by its id).  Returns (why_items, why_terms, support) laid out
+        like the set: [entries, nwhy], [entries, nwhy] and [entries].  support counts all the terms of a slot; a slot
+        holds its min(nwhy, support) largest terms (term descending, then history position) with the engine ids of
+        their history items, -1 and 0 beyond them and in the rows of users not selected."""
+        nwhy = int(nwhy)
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = max(cset.size, 1)
+        items = np.full(n * max(nwhy, 1), -1, np.int32)
+        terms = np.zeros(n * max(nwhy, 1), np.float32)
+        support = np.zeros(n, np.int32)
+        st = self._lib.SLIMGPU_MatrixExplainCandidates(
+            self.handle, device_matrix.handle, cset.handle, 0 if users is None else users.size,
+            None if users is None else users.ctypes.data_as(C.c_void_p), nwhy, items.ctypes.data_as(C.c_void_p),
+            terms.ctypes.data_as(C.c_void_p), support.ctypes.data_as(C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_MatrixExplainCandidates failed (%d): %s" % (st, _lib.last_error()))
+        return (items[:cset.size * nwhy].reshape(cset.size, nwhy), terms[:cset.size * nwhy].reshape(cset.size, nwhy),
+                support[:cset.size])
+
+    def explain_lists(self, device_matrix, ids, counts, nwhy=3, users=None):
+        """Explains lists that predict() returned: `ids` [positions, nrcmds] and `counts` [positions] as predict gave
+        them for `users` (None: every row).  The candidate set holds, for the user of position q, the first counts[q]
+        ids of row q; it is explained and freed.  Returns (indptr, why_items, why_terms, support): entry
+        indptr[q] + r is item ids[q, r], with explain()'s three arrays."""
+        ids = np.asarray(ids, np.int32)
+        counts = np.asarray(counts, np.int64).ravel()
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        who = np.arange(device_matrix.nrows) if users is None else users
+        if ids.ndim != 2 or ids.shape[0] != who.size or counts.size != who.size:
+            raise ValueError("explain_lists: ids [positions, nrcmds] and counts [positions] for %d positions" % who.size)
+        rows = np.zeros(device_matrix.nrows, np.int64)
+        rows[who] = counts
+        rowptr = np.concatenate((np.zeros(1, np.int64), np.cumsum(rows)))
+        keep = np.arange(ids.shape[1])[None, :] < counts[:, None]
+        cset = CandidateSet(device_matrix.ncols, (rowptr, ids[keep]), lib=self._lib)  # (users ascend: row-major order)
+        try:
+            items, terms, support = self.explain(device_matrix, cset, users=users, nwhy=nwhy)
+        finally:
+            cset.close()
+        return np.concatenate((np.zeros(1, np.int64), np.cumsum(counts))), items, terms, support
+
     def free(self):
         if self.handle:
             self._lib.SLIMGPU_ModelFree(C.byref(self.handle))

@@ -511,6 +511,65 @@ class SLIM(object):
             outscores[r[0]] = sc[order]
         return (out, outscores) if returnscores else out
 
+    def explain(self, data, lists, nwhy=3):
+        """Why the model scores an item for a user (an engine extension, include/slim_gpu_explain.h): `lists` maps a
+        user of `data` to a sequence of ORIGINAL item ids, as predict() and rerank() return them.  Returns a dict from
+        user to one list per item, [(original id of a history item, term), ...]: the at most nwhy (1 to 16) largest
+        terms r[u, h] * w[h, item] of the item's score, term descending, ties in history order.  An item the model
+        does not know gets an empty explanation and is counted like rerank does."""
+        if self.ismodel != SLIM_OK:
+            raise TypeError("Model not found. Please train a model.")
+        assert self.nItems == data.nItems, "The shape of the input matrix should match the model."
+        nwhy = int(nwhy)
+        rows = [None] * data.nUsers
+        for user, items in lists.items():
+            try:
+                rows[int(data.user2id[user])] = (user, list(items))
+            except (KeyError, IndexError):
+                raise KeyError("explain: user %r is not in the input matrix" % (user,))
+        cptr = np.zeros(data.nUsers + 1, np.int64)
+        for u, r in enumerate(rows):
+            cptr[u + 1] = cptr[u] + (len(r[1]) if r else 0)
+        cind = np.full(int(cptr[-1]) + 1, -1, np.int32)
+        unknown = 0
+        for u, r in enumerate(rows):
+            for j, it in enumerate(r[1] if r else ()):
+                try:
+                    cind[cptr[u] + j] = self.item2id[it]
+                except (KeyError, IndexError):
+                    unknown += 1
+        if unknown:
+            print("%d candidate items not in the training set." % unknown)
+        ncols = int(C.cast(self.handle, C.POINTER(_lib.CsrView)).contents.ncols)
+        cs = C.c_void_p()
+        if self._lib.SLIMGPU_CandSetCreate(ncols, data.nUsers, cptr.ctypes.data_as(C.c_void_p),
+                                           cind.ctypes.data_as(C.c_void_p), C.byref(cs)) != SLIM_OK:
+            raise RuntimeError("Something went wrong with the candidate set. [%s]" % _lib.last_error())
+        why = np.full(cind.size * max(nwhy, 1), -1, np.int32)
+        terms = np.zeros(cind.size * max(nwhy, 1), np.float32)
+        support = np.zeros(cind.size, np.int32)
+        try:
+            rc = self._lib.Py_SLIM_ExplainCandidates(self.handle, data.handle, cs, nwhy,
+                                                     why.ctypes.data_as(C.c_void_p), terms.ctypes.data_as(C.c_void_p),
+                                                     support.ctypes.data_as(C.c_void_p))
+        finally:
+            self._lib.SLIMGPU_CandSetFree(cs)
+        if rc != SLIM_OK:
+            raise RuntimeError("Something went wrong during the explanation. [%s]" % _lib.last_error())
+        id2item = np.asarray(self.id2item)
+        out = {}
+        for u, r in enumerate(rows):
+            if r is None:
+                continue
+            per_item = []
+            for j in range(len(r[1])):
+                e = int(cptr[u]) + j
+                n = min(nwhy, int(support[e]))
+                hs = id2item[why[e * nwhy:e * nwhy + n]]
+                per_item.append([(hs[k].item(), float(terms[e * nwhy + k])) for k in range(n)])
+            out[r[0]] = per_item
+        return out
+
     # -- persistence -----------------------------------------------------------
     def save_model(self, modelfname, mapfname):
         if self.ismodel != SLIM_OK:
