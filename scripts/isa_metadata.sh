@@ -21,7 +21,7 @@ if [ "$1" = "topn" ]; then
 fi
 echo "# hipcc -O3 --offload-arch=gfx950 -munsafe-fp-atomics -Rpass-analysis=kernel-resource-usage, $(/opt/rocm/bin/hipcc --version | grep -m1 -i 'hip version')"
 echo "# cd_tile_kernel<P, HAS_VAL, PROFILE, NW, FSLIM, FOLD>, cd_gram_kernel<NW, V>, cd_gramr_kernel<KR, KL, DMA> : VGPRs, SGPRs, VGPR spills, SGPR spills (to VGPR lanes), scratch bytes per lane, LDS bytes"
-for f in tile_p32_nw16 tile_p32_nw8 tile_p32_cold tile_p32_rowfold tile_p32_fslim tile_p16_nw16 tile_p16_nw8 gram_inst gramr_inst gramr_k13; do
+for f in tile_p32_nw16 tile_p32_nw8 tile_p32_cold tile_p32_rowfold tile_p32_fslim tile_p16_nw16 tile_p16_nw8 gram_inst gramr_inst gramr_k13 gram_sym; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics --cuda-device-only \
     -Rpass-analysis=kernel-resource-usage -c -o $T/x.o $R/slim_amd/csrc/$f.hip 2>&1 |
   grep -E "Function Name|VGPRs:|TotalSGPRs|VGPRs Spill|SGPRs Spill|ScratchSize|LDS Size" | sed 's/.*remark: *//;s/ \[-Rpass.*//' |

@@ -161,6 +161,112 @@ __device__ __forceinline__ int tile_block_id(const SolveArgs& S) {
   return S.xcd_swizzle ? (b & 7) * (g >> 3) + (b >> 3) : b;
 }
 
+// G = R^T R (S.gram_mode 3), the sums of a tile into its P rows of G in whole lines (S.gram_store 1, 2).
+// Lanes = 64 consecutive column ids: a member's partial sums of a column are P contiguous numbers (64
+// bytes as 16-bit counts, 128 bytes as floats), so a wavefront reads one contiguous 4 KB or 8 KB of
+// every member's slab, every lane adds its column's P sums over the K members -- in member order, the
+// order of the one-thread-per-entry form, so any rating values give the same bits -- and tile item qq
+// leaves as ONE 256-byte run of row s_item[qq] (G_ld is a multiple of 64 floats: a run stays inside
+// its row).  The one-thread-per-entry form has the tile item as its fastest lane index: a wavefront's
+// store touches 32 rows of G and two neighbours in each.  The 64-column blocks are dealt to the K
+// members in contiguous shares and to a member's wavefronts round-robin; a block whose columns all
+// lie in front of the tile is dropped before any partial sum is read.  S.gram_store 1 also writes the
+// mirror entries G[i][item] of the columns of later tiles, one 4-byte store each as before; with 2
+// gram_sym_kernel fills that half once the build's last launch has ended.
+// A lane takes its column's sums eight tile items at a time (16 bytes of a member's 16-bit counts, 32
+// of its floats): the P sums at once cost the visit loop of the residual solver, which shares these
+// instantiations, its registers.  For the same reason the function is not inlined, keeps to the
+// registers a call may clobber, and gets what it reads of the launch's arguments by value (GramStore):
+// the arguments themselves stay where the kernel got them.
+struct GramStore {
+  float* G;
+  int64_t G_ld;
+  const int32_t* gram_pos;
+  const float* atypart;
+  int64_t x_stride;
+  int32_t gram_part16, gram_accum, gram_store;
+};
+template <int P, int NW>
+__device__ __noinline__ void gram_store_lines(const GramStore S, const int* s_item, const int cid, const int mk,
+                                              const int K_, const int base, const int ncols, const int wave,
+                                              const int lane) {
+  const int K = uni(K_);
+  float* const G = reinterpret_cast<float*>(uni(reinterpret_cast<int64_t>(S.G)));
+  const int64_t G_ld = uni(S.G_ld), x_stride = uni(S.x_stride);
+  // the slab of the cluster's member 0 (the members' slabs follow one another)
+  const float* const part0 =
+      reinterpret_cast<const float*>(uni(reinterpret_cast<int64_t>(S.atypart))) + (int64_t)uni(cid) * K * x_stride;
+  const bool p16 = uni(S.gram_part16) != 0, accum = uni(S.gram_accum) != 0, mirror = uni(S.gram_store) == 1;
+  const int nblk = (uni(ncols) + 63) >> 6;
+  const int per = (nblk + K - 1) / K;
+  const int bend = (uni(mk) + 1) * per < nblk ? (uni(mk) + 1) * per : nblk;
+  for (int blk = uni(mk) * per + uni(wave); blk < bend; blk += NW) {
+    const int i = blk * 64 + lane;
+    const int pi = i < ncols ? S.gram_pos[i] : -1;
+    const bool keep = pi >= base;  // (columns of earlier tiles: their tiles wrote these entries)
+    if (__ballot(keep) == 0ull) continue;
+    if (!keep) continue;  // (no cross-lane operation below)
+    for (int h = 0; h < P / 8; ++h) {
+      float a[8];
+      if (p16) {  // (the bit-sliced form left 16-bit counts: their sum is below 2^24)
+        uint32_t n[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) n[e] = 0u;
+        const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(part0) + (int64_t)i * P) + h;
+#pragma unroll 4
+        for (int k = 0; k < K; ++k) {
+          const uint4 v = *src;
+          src = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(src) + x_stride);
+          n[0] += v.x & 0xFFFFu;
+          n[1] += v.x >> 16;
+          n[2] += v.y & 0xFFFFu;
+          n[3] += v.y >> 16;
+          n[4] += v.z & 0xFFFFu;
+          n[5] += v.z >> 16;
+          n[6] += v.w & 0xFFFFu;
+          n[7] += v.w >> 16;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = (float)n[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = 0.0f;
+        const float4* src = reinterpret_cast<const float4*>(part0 + (int64_t)i * P) + 2 * h;
+#pragma unroll 2
+        for (int k = 0; k < K; ++k) {  // members in rank order
+          const float4 v = src[0], w = src[1];
+          src = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(src) + x_stride);
+          a[0] += v.x;
+          a[1] += v.y;
+          a[2] += v.z;
+          a[3] += v.w;
+          a[4] += w.x;
+          a[5] += w.y;
+          a[6] += w.z;
+          a[7] += w.w;
+        }
+      }
+      int it[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) it[e] = uni(s_item[8 * h + e]);
+      // (user passes: every pass holds the sums over ITS users; counts are integers below 2^24, so the
+      // float additions are exact in any order.  The loads are issued before the first store.)
+      if (accum) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (it[e] >= 0) a[e] += G[(int64_t)it[e] * G_ld + i];
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (it[e] >= 0) {
+          G[(int64_t)it[e] * G_ld + i] = a[e];
+          if (mirror && pi >= base + P) G[(int64_t)i * G_ld + it[e]] = a[e];
+        }
+      }
+    }
+  }
+}
+
 template <int P, bool HAS_VAL, bool PROFILE, int NW, bool FSLIM, bool HI, int FOLD>
 __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& S, uint32_t& epoch) {
   constexpr int NT = 64 * NW;  // threads per workgroup
@@ -776,7 +882,11 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
         }
         if (lane == 0) s_na[pq] = na;
       }
+    } else if (S.gram_mode == 3 && S.gram_store != 0) {
+      const GramStore gs{S.G, S.G_ld, S.gram_pos, S.atypart, S.x_stride, S.gram_part16, S.gram_accum, S.gram_store};
+      gram_store_lines<P, NW>(gs, s_item, cid, mk, K, base, ncols, wave, lane);
     } else if (S.gram_mode == 3) {
+      // (SLIM_GPU_GLINES=0: one thread per entry, the form before gram_store_lines)
       // rows item_q of G and, for the columns of later tiles, their mirror entries (the tile of
       // column i will skip this tile's columns); columns of earlier tiles were skipped.  The K
       // partial sums of an entry are added by ONE member: the members share the entries

@@ -137,6 +137,12 @@ struct SolveArgs {
   int32_t gview_range0;          // the launch's first range (user passes: 32 x pass)
   int32_t gview_sentinel;
   int32_t gram_part16;           // gram_bits 2: the members' partial counts in atypart are 16-bit, [ncols][P]
+  // gram_mode 3: how the sums leave the tile (cd_tile.hpp, gram_store_lines).  0: one thread per entry,
+  // tile item fastest -- 4-byte stores into P rows of G, and the mirror entries G[i][item] with them;
+  // 1: lanes = 64 consecutive columns, one 256-byte run per tile item, and the mirror entries as
+  // before (row blocks); 2: the runs only -- gram_sym_kernel (gram_sym.hpp) fills the mirror half
+  // after the build's last launch
+  int32_t gram_store;
   // packed item-space kernel (cd_gramr.hpp): g of every problem as the solve leaves it (g_save) / as an
   // earlier solve of the same problems left it (g_load: starts from it instead of set-up row + fold);
   // [item][g_stride] floats in the kernel's own thread layout; both may point at the same buffer

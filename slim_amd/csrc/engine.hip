@@ -29,6 +29,7 @@
 #include "tile_inst.hpp"
 #include "gram_inst.hpp"
 #include "gramr_inst.hpp"
+#include "gram_sym.hpp"
 #include "fslim_gram_inst.hpp"
 #include "cd_wave.hpp"
 #include "engine.hpp"
@@ -1946,6 +1947,7 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
   if (const char* e = std::getenv("SLIM_GPU_GBITS"); e && S.gram_bits) S.gram_bits = std::atoi(e) == 1 ? 1 : 2;
   S.gram_split_stride = t.clusterK + 1;
   S.gram_accum = 0;
+  S.gram_store = 0;
   S.gview = nullptr;  // (run_launches: build_gview)
   S.gview_base = nullptr;
   S.gview_cnt = nullptr;
@@ -1987,6 +1989,13 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
     HIP_TRY(hipStreamSynchronize(stream));  // (pos is a local)
     S.gram_pos = d_pos;
     S.gram_mode = 3;
+    // How the sums leave the tiles (SolveArgs::gram_store): in whole lines, and on the path that forms
+    // all of G the mirror half by gram_sym_kernel after the last launch (run_launches).  Row blocks keep
+    // the mirror stores in the tile kernel: their lists run the block's tiles only.
+    // SLIM_GPU_GLINES=1: whole lines with the mirror stores, no pass; =0: the form before both (A/B runs)
+    S.gram_store = opt.G_rows_end >= 0 ? 1 : 2;
+    if (const char* e = std::getenv("SLIM_GPU_GLINES"); e && std::atoi(e) >= 0 && std::atoi(e) < S.gram_store)
+      S.gram_store = std::atoi(e);
   }
   if (p.use_gram) {
     S.slab_stride = (int64_t)p.ncols_pad;
@@ -2345,6 +2354,24 @@ Entries run_launches(slimgpu_matrix* m, const LearnOptions& opt, const std::vect
     if (p.gram_passes > 1 && ++L.gram_pass < p.gram_passes) {
       --attempt;  // the same work list again, over the next user ranges
       continue;
+    }
+    if (opt.build_G && S.gram_store == 2) {
+      // every tile of the build has written its own rows (with user passes: this was the last one):
+      // the mirror half in one pass (gram_sym.hpp), counted with the build's kernels
+      const unsigned nb = (unsigned)((ncols + kSymB - 1) / kSymB);
+      int logp = 0;
+      while ((1 << logp) < p.tileP) ++logp;
+      HIP_TRY(hipEventRecord(ev0, stream));
+      hipLaunchKernelGGL(gram_sym_fn(), dim3(nb, nb), dim3(kSymNT), 0, stream, S.G, S.G_ld, ncols, S.gram_pos, logp);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(ev1, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      float sym_ms = 0;
+      HIP_TRY(hipEventElapsedTime(&sym_ms, ev0, ev1));
+      E.kernel_ms += sym_ms;
+      if (p.trace_level >= 1)
+        std::fprintf(stderr, "[trace] G builder: mirror half filled in %.2f ms (%u x %u blocks of %d)\n", sym_ms, nb, nb,
+                     kSymB);
     }
     if (S.gram_mode == 1) {  // the launch completed: its screen sums are reusable
       m->gram_order = order;
