@@ -186,10 +186,33 @@ struct GramStore {
   int64_t x_stride;
   int32_t gram_part16, gram_accum, gram_store;
 };
+// S.gram_read 1 (32-item tiles, a launch whose dynamic LDS holds kGramStageBytes per wavefront): every piece
+// of a member's run is requested ONCE per block, by neighbouring lanes.  The four-round body below comes
+// back to a member's 64 (128) bytes of a column four times, a round of K members apart, and by then the
+// line has left the L2: 1.2 of the 3.5 TB the C4 build fetched.  Here a wavefront takes a block's run a
+// quarter at a time -- 16 columns, 1 KB of every member's counts or 2 KB of its floats, in 16-byte loads at
+// consecutive addresses -- so a lane holds eight running sums over the K members, as before, but of
+// ITS 16 (32) bytes: with 16-bit counts lane l has column 16 r + l / 4, items 8 (l % 4) .. + 7; with floats
+// two loads 1 KB apart, column 16 r + l / 8 and the column eight further, items 4 (l % 8) .. + 3 of each.
+// The sums of a quarter go to a staging tile [32 items][64 columns] of the wavefront in LDS (rows of 66
+// floats: either form's stores fall into 64 different banks), and after the fourth the tile is read back
+// with lane = column and leaves in the 32 runs.  The pieces of a column in front of the tile are not
+// requested.  The staging tile lies in the launch's dynamic LDS, over the users' words or the bitmap,
+// which are dead behind the cluster barrier that published the sums and are cleared again for the next tile.
+constexpr int kGramStageLd = 66;
+constexpr int kGramStageBytes = 32 * kGramStageLd * (int)sizeof(float);  // per wavefront
+typedef __attribute__((address_space(3))) float lds_float_t;
+typedef __attribute__((address_space(3))) const int lds_cint_t;
+// (what one lane writes another reads: LDS operations of a wavefront execute in order, the compiler must keep it)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 template <int P, int NW>
-__device__ __noinline__ void gram_store_lines(const GramStore S, const int* s_item, const int cid, const int mk,
-                                              const int K_, const int base, const int ncols, const int wave,
-                                              const int lane) {
+__device__ __noinline__ void gram_store_lines(const GramStore S, lds_cint_t* const s_item, lds_float_t* const stage,
+                                              const int cid, const int mk, const int K_, const int base,
+                                              const int ncols, const int wave, const int lane) {
   const int K = uni(K_);
   float* const G = reinterpret_cast<float*>(uni(reinterpret_cast<int64_t>(S.G)));
   const int64_t G_ld = uni(S.G_ld), x_stride = uni(S.x_stride);
@@ -204,7 +227,98 @@ __device__ __noinline__ void gram_store_lines(const GramStore S, const int* s_it
     const int i = blk * 64 + lane;
     const int pi = i < ncols ? S.gram_pos[i] : -1;
     const bool keep = pi >= base;  // (columns of earlier tiles: their tiles wrote these entries)
-    if (__ballot(keep) == 0ull) continue;
+    const uint64_t km = __ballot(keep);
+    if (km == 0ull) continue;
+    if (P == 32 && stage != nullptr) {
+      // the block's run of member 0: 64 columns x P sums
+      const char* const run0 = reinterpret_cast<const char*>(part0) + (int64_t)blk * (p16 ? 64 * P * 2 : 64 * P * 4);
+      const int64_t mstride = x_stride * (int64_t)sizeof(float);
+#pragma unroll 1
+      for (int r = 0; r < 4; ++r) {
+        if (p16) {  // (the bit-sliced form left 16-bit counts: their sum is below 2^24)
+          uint32_t n[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) n[e] = 0u;
+          const int c = 16 * r + (lane >> 2);
+          if ((km >> c) & 1ull) {
+            const char* src = run0 + (r * 1024 + lane * 16);
+#pragma unroll 4
+            for (int k = 0; k < K; ++k) {
+              const uint4 v = *reinterpret_cast<const uint4*>(src);
+              src += mstride;
+              n[0] += v.x & 0xFFFFu;
+              n[1] += v.x >> 16;
+              n[2] += v.y & 0xFFFFu;
+              n[3] += v.y >> 16;
+              n[4] += v.z & 0xFFFFu;
+              n[5] += v.z >> 16;
+              n[6] += v.w & 0xFFFFu;
+              n[7] += v.w >> 16;
+            }
+          }
+          lds_float_t* const out = stage + (8 * (lane & 3)) * kGramStageLd + c;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) out[e * kGramStageLd] = (float)n[e];
+        } else {
+          float a[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) a[e] = 0.0f;
+          const int c = 16 * r + (lane >> 3);
+          const bool lo = (km >> c) & 1ull, hi = (km >> (c + 8)) & 1ull;
+          if (lo || hi) {
+            const char* src = run0 + (r * 2048 + lane * 16);
+#pragma unroll 2
+            for (int k = 0; k < K; ++k) {  // members in rank order
+              float4 v = make_float4(0.f, 0.f, 0.f, 0.f), w = v;
+              if (lo) v = *reinterpret_cast<const float4*>(src);
+              if (hi) w = *reinterpret_cast<const float4*>(src + 1024);
+              src += mstride;
+              a[0] += v.x;
+              a[1] += v.y;
+              a[2] += v.z;
+              a[3] += v.w;
+              a[4] += w.x;
+              a[5] += w.y;
+              a[6] += w.z;
+              a[7] += w.w;
+            }
+          }
+          lds_float_t* const out = stage + (4 * (lane & 7)) * kGramStageLd + c;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            out[e * kGramStageLd] = a[e];
+            out[e * kGramStageLd + 8] = a[4 + e];
+          }
+        }
+      }
+      wave_lds_sync();
+#pragma unroll 1
+      for (int h = 0; h < 4; ++h) {
+        float a[8];
+        int it[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          a[e] = stage[(8 * h + e) * kGramStageLd + lane];
+          it[e] = uni(s_item[8 * h + e]);
+        }
+        if (keep) {
+          if (accum) {  // (user passes, see below)
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (it[e] >= 0) a[e] += G[(int64_t)it[e] * G_ld + i];
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            if (it[e] >= 0) {
+              G[(int64_t)it[e] * G_ld + i] = a[e];
+              if (mirror && pi >= base + P) G[(int64_t)i * G_ld + it[e]] = a[e];
+            }
+          }
+        }
+      }
+      wave_lds_sync();  // (the next block's sums go to the same tile)
+      continue;
+    }
     if (!keep) continue;  // (no cross-lane operation below)
     for (int h = 0; h < P / 8; ++h) {
       float a[8];
@@ -884,7 +998,11 @@ __device__ __forceinline__ bool tile_phase(const DevMatrix& A, const SolveArgs& 
       }
     } else if (S.gram_mode == 3 && S.gram_store != 0) {
       const GramStore gs{S.G, S.G_ld, S.gram_pos, S.atypart, S.x_stride, S.gram_part16, S.gram_accum, S.gram_store};
-      gram_store_lines<P, NW>(gs, s_item, cid, mk, K, base, ncols, wave, lane);
+      // (the staging tiles lie over s_bits: its last reader is in front of the barrier above)
+      lds_float_t* const stage =
+          S.gram_read ? (lds_float_t*)s_bits + wave * (kGramStageBytes / (int)sizeof(float)) : (lds_float_t*)nullptr;
+      // (both as LDS addresses: together the two registers the pointer to s_item took)
+      gram_store_lines<P, NW>(gs, (lds_cint_t*)s_item, stage, cid, mk, K, base, ncols, wave, lane);
     } else if (S.gram_mode == 3) {
       // (SLIM_GPU_GLINES=0: one thread per entry, the form before gram_store_lines)
       // rows item_q of G and, for the columns of later tiles, their mirror entries (the tile of

@@ -143,6 +143,10 @@ struct SolveArgs {
   // before (row blocks); 2: the runs only -- gram_sym_kernel (gram_sym.hpp) fills the mirror half
   // after the build's last launch
   int32_t gram_store;
+  // gram_store 1, 2: how the members' partial sums are read.  1: every piece of a member's run once per
+  // 64-column block, through a staging tile per wavefront in the launch's dynamic LDS (which then holds
+  // kGramStageBytes per wavefront); 0: a column's sums eight tile items per round, four rounds
+  int32_t gram_read;
   // packed item-space kernel (cd_gramr.hpp): g of every problem as the solve leaves it (g_save) / as an
   // earlier solve of the same problems left it (g_load: starts from it instead of set-up row + fold);
   // [item][g_stride] floats in the kernel's own thread layout; both may point at the same buffer

@@ -1197,6 +1197,10 @@ struct Path {
   int tileP = 32, tileNW = 16;
   int req_cluster = 0;
   size_t gram_bits_lds = 0;  // G builder: one word per user of a member's range in LDS
+  // G builder: the staging tiles of the read-once sum (cd_tile.hpp, gram_store_lines), one per wavefront in
+  // the launch's dynamic LDS; 0: that launch cannot hold them and reads the sums in four rounds
+  size_t gram_stage_lds = 0;
+  const char* gram_stage_why = "";
   int gram_passes = 1;       // G builder: user passes
   int wg_slots = 0;          // co-resident tile workgroups
   int nwaves = 1;            // workgroups launched (tiles: re-planned by plan_tiles)
@@ -1550,6 +1554,37 @@ void finish_path(slimgpu_matrix* m, const LearnOptions& opt, int32_t nwork, cons
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)worst_lds));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(p.fn),
                                                          64 * p.tileNW, worst_lds));
+    // G builder: the launches of a build also hold a staging tile per wavefront (gram_store_lines reads
+    // every partial sum once) -- where that fits the CU next to the kernel's static LDS and costs the
+    // build's launches no workgroup per CU.  Only a build's launches are sized by it.
+    // SLIM_GPU_GREAD=0: the four-round read (A/B runs, tests)
+    if (opt.build_G && per_cu >= 1) {
+      const size_t stage = (size_t)kGramStageBytes * (size_t)p.tileNW;
+      const char* e = std::getenv("SLIM_GPU_GREAD");
+      if (e && std::atoi(e) == 0) {
+        p.gram_stage_why = "SLIM_GPU_GREAD=0";
+      } else if (p.tileP != 32) {
+        p.gram_stage_why = "16-item tiles";
+      } else if (stage > worst_lds) {
+        hipFuncAttributes fa{};
+        HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(p.fn)));
+        int per_cu_s = 0;
+        if (fa.sharedSizeBytes + stage <= (size_t)160 * 1024) {
+          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(p.fn),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage));
+          HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, reinterpret_cast<const void*>(p.fn),
+                                                               64 * p.tileNW, stage));
+        }
+        if (per_cu_s >= std::min(per_cu, 16 / p.tileNW)) {
+          p.gram_stage_lds = stage;
+          per_cu = per_cu_s;
+        } else {
+          p.gram_stage_why = "no room in LDS";
+        }
+      } else {
+        p.gram_stage_lds = stage;
+      }
+    }
     if (per_cu < 1)
       throw Refusal{SLIM_ERROR, "SLIMGPU_Learn: the tile kernel does not fit a compute unit of this device"};
     p.wg_slots = m->num_cus * std::min(per_cu, 16 / p.tileNW);
@@ -1667,6 +1702,7 @@ struct Slabs {
   // dynamic LDS of a tile workgroup: the user bitmap of the screen pass (FSLIM: the select
   // histograms)
   size_t tile_lds = 0;
+  bool gram_words = false;  // tile_lds holds the G builder's word per user (Path::gram_bits_lds)
   // item-space FSLIM: the neighbour lists of one slice of the work list, f_slice_tiles tiles long
   int32_t *f_n = nullptr, *f_id = nullptr, *f_slot = nullptr;
   float* f_aty = nullptr;
@@ -1724,7 +1760,10 @@ Slabs alloc_slabs(slimgpu_matrix* m, const LearnOptions& opt, const Path& p, con
       s.bm_shift = 0;
       s.bm_words = (int)(p.gram_bits_lds / sizeof(uint32_t));
       s.tile_lds = p.gram_bits_lds;
+      s.gram_words = true;
     }
+    // (a build's launches: the words or the bitmap, and over them the staging tiles of gram_store_lines)
+    if (opt.build_G) s.tile_lds = std::max(s.tile_lds, p.gram_stage_lds);
   } else if (!p.use_lds) {
     s.slab = m->ws_slab.reserve(p.vec_floats * (size_t)nwaves);
   }
@@ -1943,11 +1982,12 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
   S.gram_pos = nullptr;
   // (2: lanes = columns, bit-sliced counters; SLIM_GPU_GBITS=1: the round-4 form, one column
   // per wavefront and 32 ballots per 64 nnz)
-  S.gram_bits = (p.gram_bits_lds && t.clusterK == 32 && L.s.tile_lds == p.gram_bits_lds) ? 2 : 0;
+  S.gram_bits = (p.gram_bits_lds && t.clusterK == 32 && L.s.gram_words) ? 2 : 0;
   if (const char* e = std::getenv("SLIM_GPU_GBITS"); e && S.gram_bits) S.gram_bits = std::atoi(e) == 1 ? 1 : 2;
   S.gram_split_stride = t.clusterK + 1;
   S.gram_accum = 0;
   S.gram_store = 0;
+  S.gram_read = 0;
   S.gview = nullptr;  // (run_launches: build_gview)
   S.gview_base = nullptr;
   S.gview_cnt = nullptr;
@@ -1996,6 +2036,8 @@ SolveArgs solve_args(slimgpu_matrix* m, const LearnOptions& opt, Launch& L, cons
     S.gram_store = opt.G_rows_end >= 0 ? 1 : 2;
     if (const char* e = std::getenv("SLIM_GPU_GLINES"); e && std::atoi(e) >= 0 && std::atoi(e) < S.gram_store)
       S.gram_store = std::atoi(e);
+    // (the launch's LDS holds a staging tile per wavefront: finish_path, alloc_slabs)
+    S.gram_read = (S.gram_store != 0 && p.gram_stage_lds && L.s.tile_lds >= p.gram_stage_lds) ? 1 : 0;
   }
   if (p.use_gram) {
     S.slab_stride = (int64_t)p.ncols_pad;
@@ -2257,6 +2299,11 @@ Entries run_launches(slimgpu_matrix* m, const LearnOptions& opt, const std::vect
                      L.gview_bytes, (double)L.gview_bytes / (2.0 * (double)std::max<int64_t>(m->nnz, 1)), L.gview_ms);
       else
         std::fprintf(stderr, "[trace] G builder: ids from csc%s\n", S.gram_bits == 2 ? L.gview_why : "");
+      if (S.gram_read)  // how gram_store_lines reads the members' partial sums
+        std::fprintf(stderr, "[trace] G builder: sums read once, %zu of %zu bytes of LDS hold the staging tiles\n",
+                     p.gram_stage_lds, L.s.tile_lds);
+      else if (S.gram_store != 0)
+        std::fprintf(stderr, "[trace] G builder: sums read in rounds (%s)\n", p.gram_stage_why);
     }
 
     // clustered tiles: always launch whole clusters (every member must be resident)
