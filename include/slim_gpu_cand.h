@@ -29,7 +29,10 @@
  *
  * Explanations (slim_gpu_explain.h, included below): the terms behind a slot score, the largest of them per slot.
  *
- * Not built: the neg-file protocol of slim_predict (random tie order), popularity-weighted negatives.
+ * Popularity-weighted negatives: SLIMGPU_EvalSetSampleCandidatesWeighted / SLIMGPU_CandSetSampleWeighted
+ * (slim_gpu_sample.h states the rule) and option slot 25 below.
+ *
+ * Not built: the neg-file protocol of slim_predict (random tie order).
  * SLIMGPU_Predict1vsK is unchanged (rows of one width, up to 1024).
  */
 #ifndef SLIM_AMD_SLIM_GPU_CAND_H_
@@ -81,7 +84,11 @@ int32_t Py_SLIM_ScoreCandidates(slim_t *model, slim_t *trn, slimgpu_candset_t *c
    several GPUs, SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0).  Never a fall-back to the full-catalogue figures. */
 enum {
   SLIM_OPTION_GPU_EVALNEGS = 23, /* sampled negatives per user; -1 or 0: off */
-  SLIM_OPTION_GPU_EVALSEED = 24  /* the sampler's seed; -1: 1 */
+  SLIM_OPTION_GPU_EVALSEED = 24, /* the sampler's seed; -1: 1 */
+  /* 1: the negatives are drawn in proportion to item popularity (the weighted rule of slim_gpu_sample.h, NULL
+     weights) and the header line says "popularity"; -1 or 0: uniformly.  1 with EVALNEGS off is SLIM_ERROR_INPUT
+     before the first solve: there is nothing to weight */
+  SLIM_OPTION_GPU_EVALNEGPOP = 25
 };
 
 #ifdef __cplusplus

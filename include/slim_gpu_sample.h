@@ -28,8 +28,44 @@
  * as staged (ids beyond ncols, repeats and history items included).  A user with an empty test row, or one the
  * user list does not select, has an empty row.  THE TIE RULE: the order of a row is score descending, then slot
  * ascending, and the held-out items stand BEHIND the negatives, so a score tie goes to the negative.  SLIM gives
- * many items the score 0; this is the pessimistic choice.  The sampler is uniform only: popularity-weighted
- * negatives are not built.
+ * many items the score 0; this is the pessimistic choice.
+ *
+ * THE WEIGHTED RULE (SLIMGPU_EvalSetSampleCandidatesWeighted, SLIMGPU_CandSetSampleWeighted; declared in
+ * slim_gpu_wsample.h, included below): negatives drawn in proportion to a weight per item -- item popularity, the
+ * other published kind of 1-vs-k.  mix64, G, base and key are those above; mulhi64(a, b) is the upper 64 bits of the
+ * 128-bit product; all arithmetic is unsigned and exact.
+ *
+ *   Weights.  The caller gives w[0 .. ncols) as uint32_t, or NULL for "popularity": on the device the number of
+ *   stored entries of column i in all rows of the resident matrix, on the host the number of entries of all rows of
+ *   trn with id i in [0, ncols).  C[i] = w[0] + ... + w[i-1] in 64 bits and T = C[ncols].  T = 0 is refused.  An
+ *   item of weight 0 is never a negative.
+ *
+ *   One draw.  pick(d) = the item i with C[i] <= mulhi64(key(seed, u, d), T) < C[i+1].
+ *
+ *   Phase 1, rejection.  The negatives are the first nnegs distinct ids of pick(0), pick(1), ... outside X_u, in draw
+ *   order; a draw counts at its first occurrence; the sequence stops at D = 16 * nnegs + 1024 draws.  Drawing from
+ *   the full weights and rejecting what is taken is exactly successive weighted sampling without replacement.
+ *
+ *   Phase 2, only when phase 1 ended short.  F = the items of positive weight neither in X_u nor accepted.  For
+ *   j = 0 ... min(nnegs - got, |F|) - 1: R = the sum of the weights still in F, r = mulhi64(key(seed, u, D + j), R),
+ *   the negative is the item of F, in id order, at which the running sum of F's weights first exceeds r, and that
+ *   item leaves F.  Phase 2 continues the same distribution over what is left, so a row is short only when fewer
+ *   than nnegs eligible items of positive weight exist.
+ *
+ * One rule, no sparse / dense switch: with real popularity the head carries half the mass and "every draw is
+ * accepted with probability >= 1/2" cannot be promised.  Rows, empty rows, the tie rule, the refusals and the
+ * SLIMGPU_SAMPLE_MAX_NCOLS bound of the device call are those of the uniform calls; T = 0 is refused as well.  The
+ * uniform calls are unchanged: same symbols, same rows.
+ *
+ * The weighted device sampler keeps, beside the bitmap and the accepted ids, the prefix table C in HBM (8 bytes per
+ * item: 0.8 MB at 100 K items, L2-resident; a device scan of the uploaded weights -- 4 bytes per item host to device
+ * per call; for NULL weights the resident matrix's column pointer comes to the host first, 8 bytes per item, and its
+ * differences are the weights) and, for phase 2, the remaining mass per block of 1024 items in LDS (4 KB at the
+ * item bound): a user that enters phase 2 reads all of C once to form them, and a pick then scans the block sums and
+ * one block, not the catalogue again.  Bitmap + ids + block sums
+ * are 84 KB at SLIMGPU_SAMPLE_MAX_NCOLS items and nnegs = SLIMGPU_MAX_LIST.  Per draw: one hash, one 64 x 64 multiply
+ * and about log2(ncols) dependent reads of C.  Not built: weights for several GPUs, C cached on the handle between
+ * calls, the neg-file protocol of slim_predict.
  *
  * A sampled set has min(rows of trn, rows of tst) rows and is an ordinary candidate set in every call of
  * slim_gpu_cand.h.  The device call writes the rows straight into the set's device copy and indexes them as an
@@ -42,7 +78,8 @@
  *
  * SLIM_ERROR_INPUT with a SLIMGPU_LastError text, *out untouched: nnegs < 1; nnegs + the longest selected test row
  * above SLIMGPU_MAX_LIST (the evaluation needs lists); a matrix whose duplicates were merged; the device call above
- * SLIMGPU_SAMPLE_MAX_NCOLS items; ncols < 1, a user list that does not ascend strictly inside the rows.
+ * SLIMGPU_SAMPLE_MAX_NCOLS items; ncols < 1, a user list that does not ascend strictly inside the rows; under the
+ * weighted rule weights that sum to 0.
  */
 #ifndef SLIM_AMD_SLIM_GPU_SAMPLE_H_
 #define SLIM_AMD_SLIM_GPU_SAMPLE_H_
@@ -69,5 +106,7 @@ int32_t SLIMGPU_CandSetInfo(slimgpu_candset_t *cs, int32_t *nrows, int32_t *ncol
 #ifdef __cplusplus
 }
 #endif
+
+#include "slim_gpu_wsample.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_SAMPLE_H_ */

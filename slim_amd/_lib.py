@@ -260,6 +260,18 @@ _SAMPLE_SIGNATURES = {
 
 SAMPLE_SYMBOLS = tuple(_SAMPLE_SIGNATURES)
 
+# popularity-weighted negatives (include/slim_gpu_wsample.h): the two samplers under the weighted rule; weights is a
+# pointer to ncols uint32 (None: popularity)
+_WSAMPLE_SIGNATURES = {
+    "SLIMGPU_EvalSetSampleCandidatesWeighted": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p,
+                                                            C.POINTER(C.c_void_p)]),
+    "SLIMGPU_CandSetSampleWeighted": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                  C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "SLIMGPU_LastSampleKernelMs": (C.c_double, []),
+}
+
+WSAMPLE_SYMBOLS = tuple(_WSAMPLE_SIGNATURES)
+
 # explanations: the history items behind a candidate's score (include/slim_gpu_explain.h); why_items / why_terms /
 # support / users are passed as pointers (any may be None)
 _EXPLAIN_SIGNATURES = {
@@ -292,7 +304,7 @@ def load():
                               list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
                               list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
                               list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items()) +
-                              list(_EXPLAIN_SIGNATURES.items())):
+                              list(_WSAMPLE_SIGNATURES.items()) + list(_EXPLAIN_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

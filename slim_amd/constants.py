@@ -52,6 +52,7 @@ class Opt(enum.IntEnum):
     GPU_EVALSTRIDE = 22    # Py_SLIM_Mselect: evaluate users 0, K, 2K, ... only (slim_gpu_eval.h; default: all)
     GPU_EVALNEGS = 23      # Py_SLIM_Mselect: evaluate 1-vs-k on this many sampled negatives (slim_gpu_cand.h; 0: off)
     GPU_EVALSEED = 24      # ... drawn with this seed (default 1)
+    GPU_EVALNEGPOP = 25    # ... 1: in proportion to item popularity, not uniformly (slim_gpu_sample.h)
 
 
 for _o in Opt:

@@ -171,6 +171,10 @@ int32_t candset_rows(slimgpu_candset* cs, int64_t* cptr, int32_t* cind);
 int32_t candset_info(const slimgpu_candset* cs, int32_t* nrows, int32_t* ncols, int64_t* entries);
 // cand_sample.hip: the sampled set of an eval set's users, made on the device; host_csr.cpp has the host form
 slimgpu_candset* evalset_sample_candidates(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed, int32_t* status);
+// ... under the weighted rule: weights[ncols] (nullptr: the popularity of the resident matrix's columns)
+slimgpu_candset* evalset_sample_candidates_weighted(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed,
+                                                    const uint32_t* weights, int32_t* status);
+double last_weighted_sample_kernel_ms();  // the weighted kernel of this thread's most recent such call
 int32_t score_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_candset* cs, int32_t nrcmds,
                          float* slot_scores, int32_t* output, float* scores, int32_t* counts);
 int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs, int32_t nusers,

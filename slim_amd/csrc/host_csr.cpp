@@ -361,7 +361,7 @@ void explain_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const H
 
 void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr_t* tst, int32_t nusers,
                             const int32_t* users, int32_t nnegs, uint64_t seed, std::vector<int64_t>& cptr,
-                            std::vector<int32_t>& cind) {
+                            std::vector<int32_t>& cind, const uint64_t* wC) {
   const int32_t nall = std::min(trn->nrows, tst->nrows);
   const int32_t nsel = users ? nusers : nall;
   cptr.assign((size_t)nall + 1, 0);
@@ -386,7 +386,37 @@ void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr
       for (ssize_t t = t0; t < t1; ++t) put(tst->rowind[t]);
       const int64_t E = (int64_t)marked.size();
       const uint64_t base = sample_base(seed, (uint64_t)u);
-      if (2 * (E + nnegs) <= ncols) {
+      if (wC) {
+        // phase 1: draws from the full weights, rejecting what is taken; phase 2: over what is left, in id order
+        const uint64_t T = wC[ncols];
+        const int64_t stop = sample_guard(nnegs);
+        int32_t got = 0;
+        for (int64_t d = 0; d < stop && got < nnegs; ++d) {
+          const int32_t id = sample_search(wC, ncols, sample_mulhi64(sample_key(base, (uint64_t)d), T));
+          if (mark[id]) continue;
+          mark[id] = 1;
+          marked.push_back(id);
+          cind.push_back(id);
+          ++got;
+        }
+        if (got < nnegs) {
+          uint64_t left = 0;  // the weights still in F
+          for (int32_t i = 0; i < ncols; ++i)
+            if (!mark[i]) left += wC[i + 1] - wC[i];
+          for (int64_t j = 0; got < nnegs && left > 0; ++j) {
+            const uint64_t r = sample_mulhi64(sample_key(base, (uint64_t)(stop + j)), left);
+            uint64_t run = 0;
+            int32_t id = 0;
+            for (; id < ncols; ++id)
+              if (!mark[id] && (run += wC[id + 1] - wC[id]) > r) break;
+            mark[id] = 1;
+            marked.push_back(id);
+            cind.push_back(id);
+            left -= wC[id + 1] - wC[id];
+            ++got;
+          }
+        }
+      } else if (2 * (E + nnegs) <= ncols) {
         int32_t got = 0;
         for (int64_t d = 0, stop = sample_guard(nnegs); d < stop && got < nnegs; ++d) {
           const int32_t id = (int32_t)sample_item(sample_key(base, (uint64_t)d), (uint32_t)ncols);

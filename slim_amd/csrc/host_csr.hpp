@@ -94,7 +94,7 @@ void score_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const Hos
 void explain_candidates_host(const slim_csr_t* W, const slim_csr_t* trn, const HostCandSet& S, int32_t nwhy,
                              int32_t* why_items, float* why_terms, int32_t* support);
 
-// The sampler of slim_gpu_sample.h, which states it; the device kernel (cand_sample.hip) uses the same three.
+// The sampler of slim_gpu_sample.h, which states it; the device kernels (cand_sample.hip) use the same helpers.
 constexpr uint64_t kSampleG = 0x9E3779B97F4A7C15ull;
 #if defined(__HIP__) || defined(__HIPCC__)
 #define SLIMAMD_HD __host__ __device__
@@ -110,11 +110,25 @@ SLIMAMD_HD inline uint64_t sample_base(uint64_t seed, uint64_t user) { return sa
 SLIMAMD_HD inline uint64_t sample_key(uint64_t base, uint64_t d) { return sample_mix64(base + kSampleG * (d + 1)); }
 SLIMAMD_HD inline uint32_t sample_item(uint64_t key, uint32_t ncols) { return (uint32_t)(((key >> 32) * ncols) >> 32); }
 inline int64_t sample_guard(int32_t nnegs) { return 16 * (int64_t)nnegs + 1024; }
+// The weighted rule's two: the upper 64 bits of a * b, and the item i with C[i] <= r < C[i + 1] in the prefix table
+// C[0 .. n] (C[0] = 0, ascending, r < C[n]; an item of weight 0 has an empty interval and is never found).
+SLIMAMD_HD inline uint64_t sample_mulhi64(uint64_t a, uint64_t b) {
+  return (uint64_t)(((unsigned __int128)a * b) >> 64);
+}
+SLIMAMD_HD inline int32_t sample_search(const uint64_t* C, int32_t n, uint64_t r) {
+  int32_t lo = 0, hi = n;  // C[lo] <= r < C[hi]
+  while (hi - lo > 1) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (C[mid] <= r) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 // The rows of SLIMGPU_CandSetSample: min(trn rows, tst rows) of them, those of the users listed (ascending;
-// nullptr: all) filled.  The arguments are checked by the caller.
+// nullptr: all) filled.  wC (nullptr: the uniform rules): the weighted rule over the prefix table C[0 .. ncols] of the
+// weights, C[ncols] > 0.  The arguments are checked by the caller.
 void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr_t* tst, int32_t nusers,
                             const int32_t* users, int32_t nnegs, uint64_t seed, std::vector<int64_t>& cptr,
-                            std::vector<int32_t>& cind);
+                            std::vector<int32_t>& cind, const uint64_t* wC = nullptr);
 
 // api.c:215-245.  malloc'd marker array (0 head / 1 tail).
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,

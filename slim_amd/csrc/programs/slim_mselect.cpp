@@ -10,7 +10,7 @@ int main(int argc, char** argv) {
       {"ifmt", true},    {"binarize", false}, {"optTol", true},  {"niters", true},
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
-      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"gpukernel", true}, {"help", false}};
+      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"evalnegpop", false}, {"gpukernel", true}, {"help", false}};
   specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() != 3) {
@@ -21,6 +21,7 @@ int main(int argc, char** argv) {
                 "   -evalstride=i  (engine extension: evaluate users 0, i, 2i, ... only; needs the evaluation in HBM)\n"
                 "   -evalnegs=i -evalseed=i  (engine extension: evaluate 1-vs-k on i sampled negatives per user, drawn on\n"
                 "   the device with that seed (default 1); needs the evaluation in HBM, nrcmds <= 128 and no filter)\n"
+                "   -evalnegpop  (with -evalnegs: draw the negatives in proportion to item popularity, not uniformly)\n"
                 "   (-nrcmds above 128 is evaluated in HBM from the ranks of the held-out items: no lists are formed)\n"
                 "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n"
                 "%s   (engine extension: every pair is evaluated under the filter; a held-out item it removes is a miss;\n"
@@ -38,6 +39,8 @@ int main(int argc, char** argv) {
   const long long evalseed = a.has("evalseed") ? std::atoll(a.str("evalseed", "1").c_str()) : 1;
   if (evalnegs < 0) die("Invalid -evalnegs of " + a.str("evalnegs", "") + ".");
   if (evalseed < 0 || evalseed > 0xFFFFFFFFll) die("Invalid -evalseed of " + a.str("evalseed", "") + ".");
+  const bool evalnegpop = a.has("evalnegpop");
+  if (evalnegpop && evalnegs < 1) die("-evalnegpop weights the sampled negatives: it needs -evalnegs.");
   const bool filtered = filter_options(a);
   filter_files_exist(a);
   if (evalnegs > 0 && filtered) die("-evalnegs takes no item filter: candidate rows are scored as they are.");
@@ -141,15 +144,16 @@ int main(int argc, char** argv) {
           (!resident ? std::string("the models of this grid do not stay in HBM")
            : evr_env && std::atoi(evr_env) == 0 ? std::string("SLIM_GPU_EVAL_RESIDENT=0")
            : nrcmds < 1 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
-    if (SLIMGPU_EvalSetSampleCandidates(evalset, evalnegs, (uint64_t)evalseed, &cands) != SLIM_OK)
+    if ((evalnegpop ? SLIMGPU_EvalSetSampleCandidatesWeighted(evalset, evalnegs, (uint64_t)evalseed, nullptr, &cands)
+                    : SLIMGPU_EvalSetSampleCandidates(evalset, evalnegs, (uint64_t)evalseed, &cands)) != SLIM_OK)
       die(std::string("-evalnegs: ") + SLIMGPU_LastError());
   }
   if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
   if (cands) {
     int64_t entries = 0;
     SLIMGPU_CandSetInfo(cands, nullptr, nullptr, &entries);
-    std::printf("  sampled negatives: nnegs %d, seed %llu, %lld candidate entries\n", evalnegs,
-                (unsigned long long)evalseed, (long long)entries);
+    std::printf("  sampled negatives: nnegs %d, seed %llu, %s%lld candidate entries\n", evalnegs,
+                (unsigned long long)evalseed, evalnegpop ? "popularity, " : "", (long long)entries);
   }
   if (filtered)
     std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)flt.allowed, rcols,

@@ -283,6 +283,7 @@ int32_t evalset_rows(const slimgpu_evalset_t* es, EvalSetRows* out) {
   V.hptr = R.d_ptr; V.hind = R.d_ind;
   V.tptr = es->tst.ptr.get(); V.tind = es->tst.ind.get();
   V.max_hist = es->max_hist; V.max_test = es->max_test; V.test_entries = es->entries;
+  V.mat = es->mat;
   *out = V;
   return SLIM_OK;
 }

@@ -112,6 +112,7 @@ struct EvalSetRows {
   const int64_t* hptr = nullptr; const int32_t* hind = nullptr;
   const int64_t* tptr = nullptr; const int32_t* tind = nullptr;
   int64_t max_hist = 0, max_test = 0, test_entries = 0;
+  const slimgpu_matrix_t* mat = nullptr;  // the resident matrix (its column pointer gives the popularity weights)
 };
 int32_t evalset_rows(const slimgpu_evalset_t* es, EvalSetRows* out);
 // Explanations (slim_gpu_explain.h): the device outputs of explain.hip and their host images, grow-only like

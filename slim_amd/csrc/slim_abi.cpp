@@ -217,6 +217,15 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
   const int32_t evalnegs = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALNEGS] == -1) ? 0 : ioptions[SLIM_OPTION_GPU_EVALNEGS];
   const uint64_t evalseed = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALSEED] == -1)
                                 ? 1 : (uint64_t)(uint32_t)ioptions[SLIM_OPTION_GPU_EVALSEED];
+  // slot 25: the negatives are drawn in proportion to item popularity (the weighted rule of slim_gpu_sample.h)
+  const int32_t evalnegpop = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALNEGPOP] == -1) ? 0 : ioptions[SLIM_OPTION_GPU_EVALNEGPOP];
+  if (evalnegpop != 0 && (evalnegpop != 1 || evalnegs <= 0)) {
+    set_error(evalnegpop != 1
+                  ? "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGPOP must be 0 or 1, not " + std::to_string(evalnegpop)
+                  : "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGPOP weights the sampled negatives and "
+                    "SLIM_OPTION_GPU_EVALNEGS is off: there is nothing to weight");
+    return SLIM_ERROR_INPUT;
+  }
   if (evalnegs != 0) {
     const char* res0 = std::getenv("SLIM_GPU_RESIDENT");
     const char* evr0 = std::getenv("SLIM_GPU_EVAL_RESIDENT");
@@ -324,7 +333,8 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
       why = SLIMGPU_LastError();
       if (why.empty()) why = "the eval set could not be made";
     } else {
-      cands = evalset_sample_candidates(evalset, evalnegs, evalseed, &status);
+      cands = evalnegpop ? evalset_sample_candidates_weighted(evalset, evalnegs, evalseed, nullptr, &status)
+                         : evalset_sample_candidates(evalset, evalnegs, evalseed, &status);
       if (!cands) why = SLIMGPU_LastError();
     }
     if (!cands) {
@@ -357,8 +367,8 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
   if (cands) {
     int64_t entries = 0;
     candset_info(cands, nullptr, nullptr, &entries);
-    std::printf("  sampled negatives: nnegs %d, seed %llu, %lld candidate entries\n", evalnegs,
-                (unsigned long long)evalseed, (long long)entries);
+    std::printf("  sampled negatives: nnegs %d, seed %llu, %s%lld candidate entries\n", evalnegs,
+                (unsigned long long)evalseed, evalnegpop ? "popularity, " : "", (long long)entries);
   }
   std::printf("\nEstimating & evaluating models...\n\n");
 
@@ -1068,10 +1078,13 @@ int32_t SLIMGPU_EvalSetSampleCandidates(slimgpu_evalset_t* es, int32_t nnegs, ui
   return status;
 }
 
-int32_t SLIMGPU_CandSetSample(int32_t ncols, slim_t* trnhandle, slim_t* tsthandle, int32_t nusers,
-                              const int32_t* users, int32_t nnegs, uint64_t seed, slimgpu_candset_t** out) {
+extern "C++" {
+namespace {
+// SLIMGPU_CandSetSample and its weighted form: one check, one host sampler
+int32_t candset_sample(const std::string& who, int32_t ncols, slim_t* trnhandle, slim_t* tsthandle, int32_t nusers,
+                       const int32_t* users, int32_t nnegs, uint64_t seed, bool weighted, const uint32_t* weights,
+                       slimgpu_candset_t** out) {
   set_error("");
-  const std::string who = "SLIMGPU_CandSetSample: ";
   auto bad = [&](const std::string& why) {
     set_error(who + why);
     return SLIM_ERROR_INPUT;
@@ -1099,9 +1112,21 @@ int32_t SLIMGPU_CandSetSample(int32_t ncols, slim_t* trnhandle, slim_t* tsthandl
                " entries, give a candidate row above " + std::to_string(SLIMGPU_MAX_LIST) +
                ": the evaluation needs lists");
   try {
+    std::vector<uint64_t> wC;  // the weighted rule's prefix table; NULL weights: the popularity of trn's rows
+    if (weighted) {
+      wC.assign((size_t)ncols + 1, 0);
+      if (weights) {
+        for (int32_t i = 0; i < ncols; ++i) wC[(size_t)i + 1] = weights[i];
+      } else {
+        for (ssize_t k = 0; k < trn->rowptr[trn->nrows]; ++k)
+          if (trn->rowind[k] >= 0 && trn->rowind[k] < ncols) ++wC[(size_t)trn->rowind[k] + 1];
+      }
+      for (int32_t i = 0; i < ncols; ++i) wC[(size_t)i + 1] += wC[i];
+      if (wC[ncols] == 0) return bad("the weights sum to 0 (T = 0): nothing can be drawn");
+    }
     std::vector<int64_t> cptr;
     std::vector<int32_t> cind;
-    sample_candidates_host(ncols, trn, tst, nusers, users, nnegs, seed, cptr, cind);
+    sample_candidates_host(ncols, trn, tst, nusers, users, nnegs, seed, cptr, cind, weighted ? wC.data() : nullptr);
     cind.push_back(0);  // (an empty set still has an address)
     int32_t status = SLIM_ERROR;
     slimgpu_candset_t* cs = candset_create(ncols, nall, cptr.data(), cind.data(), &status);
@@ -1112,6 +1137,36 @@ int32_t SLIMGPU_CandSetSample(int32_t ncols, slim_t* trnhandle, slim_t* tsthandl
     return SLIM_ERROR_MEMORY;
   }
 }
+}  // namespace
+}  // extern "C++"
+
+int32_t SLIMGPU_CandSetSample(int32_t ncols, slim_t* trnhandle, slim_t* tsthandle, int32_t nusers,
+                              const int32_t* users, int32_t nnegs, uint64_t seed, slimgpu_candset_t** out) {
+  return candset_sample("SLIMGPU_CandSetSample: ", ncols, trnhandle, tsthandle, nusers, users, nnegs, seed, false,
+                        nullptr, out);
+}
+
+int32_t SLIMGPU_CandSetSampleWeighted(int32_t ncols, slim_t* trnhandle, slim_t* tsthandle, int32_t nusers,
+                                      const int32_t* users, int32_t nnegs, uint64_t seed, const uint32_t* weights,
+                                      slimgpu_candset_t** out) {
+  return candset_sample("SLIMGPU_CandSetSampleWeighted: ", ncols, trnhandle, tsthandle, nusers, users, nnegs, seed,
+                        true, weights, out);
+}
+
+int32_t SLIMGPU_EvalSetSampleCandidatesWeighted(slimgpu_evalset_t* es, int32_t nnegs, uint64_t seed,
+                                                const uint32_t* weights, slimgpu_candset_t** out) {
+  set_error("");
+  if (!out) {
+    set_error("SLIMGPU_EvalSetSampleCandidatesWeighted: bad arguments (out is NULL)");
+    return SLIM_ERROR_INPUT;
+  }
+  int32_t status = SLIM_ERROR;
+  slimgpu_candset_t* cs = evalset_sample_candidates_weighted(es, nnegs, seed, weights, &status);
+  if (cs) *out = cs;
+  return status;
+}
+
+double SLIMGPU_LastSampleKernelMs(void) { return last_weighted_sample_kernel_ms(); }
 
 int32_t SLIMGPU_CandSetRows(slimgpu_candset_t* cs, int64_t* cptr, int32_t* cind) {
   set_error("");

@@ -323,26 +323,65 @@ class CandidateSet(object):
             pass
 
 
-def sample_candidates(trn, tst, nnegs, seed=1, users=None, ncols=None, lib=None):
+def popularity_weights(R, alpha=1.0):
+    """Sampling weights from item popularity, for the `weights` of the samplers: the column counts of R (uint32) for
+    alpha == 1, else rint(counts ** alpha * 1024) -- alpha = 0.75 is word2vec's.  A host convenience: the array it
+    returns is the contract, not the exponent."""
+    R = sp.csr_matrix(R)
+    counts = np.bincount(R.indices, minlength=R.shape[1]).astype(np.int64)
+    if alpha == 1:
+        return counts.astype(np.uint32)
+    w = np.rint(counts.astype(np.float64) ** float(alpha) * 1024.0)
+    if w.size and w.max() >= 2.0 ** 32:
+        raise ValueError("popularity_weights: a weight reaches 2^32")
+    return w.astype(np.uint32)
+
+
+def _sampling_weights(weights, ncols):
+    """weights of the samplers -> (weighted, uint32 array or None): None: uniform; "popularity": NULL weights; else
+    ncols non-negative integers below 2^32."""
+    if weights is None:
+        return False, None
+    if isinstance(weights, str):
+        if weights != "popularity":
+            raise ValueError('weights: None, "popularity" or an array of ncols integers, not %r' % weights)
+        return True, None
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.size != ncols:
+        raise ValueError("weights: %d items need %d weights, not an array of shape %s" % (ncols, ncols, w.shape))
+    if w.dtype.kind not in "iu" or (w.size and (int(w.min()) < 0 or int(w.max()) >= 2 ** 32)):
+        raise ValueError("weights: non-negative integers below 2^32")
+    return True, np.ascontiguousarray(w, dtype=np.uint32)
+
+
+def sample_candidates(trn, tst, nnegs, seed=1, users=None, ncols=None, lib=None, weights=None):
     """SLIMGPU_CandSetSample (include/slim_gpu_sample.h): the 1-vs-k candidate set made on the host -- per user with a
     test row `nnegs` sampled items outside its history and test row, then the test row.  trn / tst: scipy matrices,
     one row per user; users: ascending user ids (None: every user); ncols: the catalogue (None: the wider of the
-    two).  The rows equal those of Evaluator.sample_candidates for the same seed."""
+    two).  weights (SLIMGPU_CandSetSampleWeighted): None: uniform; "popularity": in proportion to the entries trn has
+    of every item; an array of ncols non-negative integers below 2^32 (popularity_weights makes one).  The rows equal
+    those of Evaluator.sample_candidates for the same seed and weights."""
     lib = lib or _lib.load()
     trn, tst = sp.csr_matrix(trn), sp.csr_matrix(tst)
     ncols = max(trn.shape[1], tst.shape[1]) if ncols is None else int(ncols)
+    weighted, w = _sampling_weights(weights, ncols)
     sel = None if users is None else np.ascontiguousarray(users, dtype=np.int32).ravel()
     ht, hs = _wrap_rows(lib, trn), _wrap_rows(lib, tst)
     h = C.c_void_p()
+    name = "SLIMGPU_CandSetSampleWeighted" if weighted else "SLIMGPU_CandSetSample"
+    args = (ncols, ht, hs, 0 if sel is None else sel.size, None if sel is None else sel.ctypes.data_as(C.c_void_p),
+            int(nnegs), int(seed))
     try:
-        st = lib.SLIMGPU_CandSetSample(ncols, ht, hs, 0 if sel is None else sel.size,
-                                       None if sel is None else sel.ctypes.data_as(C.c_void_p), int(nnegs),
-                                       int(seed), C.byref(h))
+        if weighted:
+            st = lib.SLIMGPU_CandSetSampleWeighted(*(args + (None if w is None else w.ctypes.data_as(C.c_void_p),
+                                                             C.byref(h))))
+        else:
+            st = lib.SLIMGPU_CandSetSample(*(args + (C.byref(h),)))
     finally:
         lib.Py_csr_free(ht)
         lib.Py_csr_free(hs)
     if st != SLIM_OK:
-        raise ValueError("SLIMGPU_CandSetSample failed (%d): %s" % (st, _lib.last_error()))
+        raise ValueError("%s failed (%d): %s" % (name, st, _lib.last_error()))
     return CandidateSet.from_handle(h, lib=lib)
 
 
@@ -464,15 +503,24 @@ class Evaluator(object):
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
 
-    def sample_candidates(self, nnegs, seed=1):
+    def sample_candidates(self, nnegs, seed=1, weights=None):
         """SLIMGPU_EvalSetSampleCandidates: the 1-vs-k CandidateSet of this eval set's users, made on the device --
         `nnegs` sampled items outside the user's history and test row, then the test row (a score tie goes to the
         negative).  Reproducible from the seed; evaluate_candidates(model, that set) gives HR / ARHR on sampled
-        negatives.  It costs about what evaluate() costs: a protocol, not a speed-up."""
+        negatives.  It costs about what evaluate() costs: a protocol, not a speed-up.  weights
+        (SLIMGPU_EvalSetSampleCandidatesWeighted): None: uniform; "popularity": in proportion to the entries the
+        resident matrix has of every item; an array of ncols non-negative integers below 2^32."""
         h = C.c_void_p()
-        st = self._lib.SLIMGPU_EvalSetSampleCandidates(self.handle, int(nnegs), int(seed), C.byref(h))
+        weighted, w = _sampling_weights(weights, self._matrix.ncols if weights is not None else 0)
+        if weighted:
+            name = "SLIMGPU_EvalSetSampleCandidatesWeighted"
+            st = self._lib.SLIMGPU_EvalSetSampleCandidatesWeighted(
+                self.handle, int(nnegs), int(seed), None if w is None else w.ctypes.data_as(C.c_void_p), C.byref(h))
+        else:
+            name = "SLIMGPU_EvalSetSampleCandidates"
+            st = self._lib.SLIMGPU_EvalSetSampleCandidates(self.handle, int(nnegs), int(seed), C.byref(h))
         if st != SLIM_OK:
-            raise RuntimeError("SLIMGPU_EvalSetSampleCandidates failed (%d): %s" % (st, _lib.last_error()))
+            raise RuntimeError("%s failed (%d): %s" % (name, st, _lib.last_error()))
         return CandidateSet.from_handle(h, lib=self._lib)
 
     def prepass_ms(self):
@@ -696,10 +744,11 @@ class DeviceMatrix(object):
         Evaluator.evaluate_candidates."""
         return CandidateSet(self.ncols, C_rows, lib=self._lib)
 
-    def sample_candidates(self, trn, tst, nnegs, seed=1, users=None):
+    def sample_candidates(self, trn, tst, nnegs, seed=1, users=None, weights=None):
         """SLIMGPU_CandSetSample over this matrix's items: the host form of Evaluator.sample_candidates (trn: the
-        scipy rows this matrix was staged from; the same rows for the same seed)."""
-        return sample_candidates(trn, tst, nnegs, seed=seed, users=users, ncols=self.ncols, lib=self._lib)
+        scipy rows this matrix was staged from; the same rows for the same seed and weights)."""
+        return sample_candidates(trn, tst, nnegs, seed=seed, users=users, ncols=self.ncols, lib=self._lib,
+                                 weights=weights)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)

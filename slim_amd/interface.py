@@ -119,6 +119,7 @@ def build_options(params):
     # engine extensions ride along when present (include/slim_gpu.h)
     for key, slot in (("gpu_seed", Opt.GPU_SEED), ("gpu_evalstride", Opt.GPU_EVALSTRIDE),
                       ("gpu_evalnegs", Opt.GPU_EVALNEGS), ("gpu_evalseed", Opt.GPU_EVALSEED),
+                      ("gpu_evalnegpop", Opt.GPU_EVALNEGPOP),
                       ("gpu_device", Opt.GPU_DEVICE),
                       ("gpu_kernel", Opt.GPU_KERNEL), ("gpu_colbegin", Opt.GPU_COLBEGIN),
                       ("gpu_colend", Opt.GPU_COLEND)):
@@ -325,11 +326,13 @@ class SLIM(object):
         print("Learning takes %.3f secs." % elapsed)
 
     def mselect(self, params, trndata, tstdata, arrayl1, arrayl2, nrcmds, allowed_items=None, blocked_items=None,
-                exclude=None, nnegs=0, negseed=1):
+                exclude=None, nnegs=0, negseed=1, negpop=False):
         """nnegs > 0 (or params["gpu_evalnegs"] / ["gpu_evalseed"]): evaluate every pair 1-vs-k -- each held-out item
         against nnegs sampled items outside the user's history and test row, drawn once on the device from negseed
         (include/slim_gpu_sample.h); a score tie goes to the negative.  It takes no filter, needs nrcmds <= 128 and
-        the evaluation in HBM, and costs about what the full-catalogue evaluation costs.
+        the evaluation in HBM, and costs about what the full-catalogue evaluation costs.  negpop=True (or
+        params["gpu_evalnegpop"] = 1): the negatives are drawn in proportion to item popularity, not uniformly;
+        without nnegs that is refused.
         allowed_items / blocked_items / exclude: evaluate every pair under a candidate filter, with the rules
         of predict() -- ORIGINAL item ids through trndata's maps, at most one of allowed and blocked, unknown ids
         ignored, exclude a SLIMatrix whose rows are put in the order of trndata's users.  A held-out item the
@@ -345,6 +348,8 @@ class SLIM(object):
         iopt, dopt = build_options(view)
         if nnegs:
             iopt[Opt.GPU_EVALNEGS], iopt[Opt.GPU_EVALSEED] = int(nnegs), int(negseed)
+        if negpop:
+            iopt[Opt.GPU_EVALNEGPOP] = 1
         if len(arrayl1) < 1:
             raise TypeError("The l1 array must not be empty.")
         if len(arrayl2) < 1:
