@@ -57,4 +57,7 @@ int32_t SLIMGPU_LastListStats(slimgpu_list_stats_t *out);
 #ifdef __cplusplus
 }
 #endif
+
+#include "slim_gpu_exposure.h"
+
 #endif /* SLIM_AMD_SLIM_GPU_LISTS_H_ */

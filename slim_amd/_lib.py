@@ -286,6 +286,36 @@ _EXPLAIN_SIGNATURES = {
 EXPLAIN_SYMBOLS = tuple(_EXPLAIN_SIGNATURES)
 MAX_WHY = 16            # SLIMGPU_MAX_WHY
 
+
+class Exposure(C.Structure):
+    """slimgpu_exposure_t (include/slim_gpu_exposure.h): the summary of one cutoff."""
+    _fields_ = [("lists", C.c_int64), ("slots", C.c_int64), ("tail_slots", C.c_int64), ("outside", C.c_int64),
+                ("distinct", C.c_int32), ("ncols", C.c_int32), ("coverage", C.c_double), ("tail_share", C.c_double),
+                ("gini", C.c_double), ("avg_pop", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# exposure of top-N lists (include/slim_gpu_exposure.h): per-item counts and their summaries; pop / fmarker / ids /
+# counts / users / cutoffs / exposure / summary are passed as pointers (those the header lets be NULL may be None)
+_EXPOSURE_SIGNATURES = {
+    "SLIMGPU_ListExposure": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_MatrixListExposure": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_MatrixPredictExposure": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "SLIMGPU_ModelEvaluateExposure": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, f64_1d, i32_1d,
+                                                  C.c_void_p, C.c_void_p]),
+    "Py_SLIM_MselectExposure": (C.c_int32, [C.c_void_p, C.c_void_p, i32_1d, f64_1d, f64_1d, f64_1d,
+                                            C.c_int32, C.c_int32] + [C.c_void_p] * 10),
+}
+
+EXPOSURE_SYMBOLS = tuple(_EXPOSURE_SIGNATURES)
+EXPOSURE_CELL = 8       # SLIMGPU_EXPOSURE_CELL: l1, l2, HR, ARHR, coverage, tail_share, gini, avg_pop
+
 _lib = None
 
 
@@ -304,7 +334,8 @@ def load():
                               list(_RANK_SIGNATURES.items()) + list(_LIST_SIGNATURES.items()) +
                               list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
                               list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items()) +
-                              list(_WSAMPLE_SIGNATURES.items()) + list(_EXPLAIN_SIGNATURES.items())):
+                              list(_WSAMPLE_SIGNATURES.items()) + list(_EXPLAIN_SIGNATURES.items()) +
+                              list(_EXPOSURE_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

@@ -53,6 +53,7 @@ class Opt(enum.IntEnum):
     GPU_EVALNEGS = 23      # Py_SLIM_Mselect: evaluate 1-vs-k on this many sampled negatives (slim_gpu_cand.h; 0: off)
     GPU_EVALSEED = 24      # ... drawn with this seed (default 1)
     GPU_EVALNEGPOP = 25    # ... 1: in proportion to item popularity, not uniformly (slim_gpu_sample.h)
+    GPU_EVALEXPOSURE = 26  # Py_SLIM_Mselect: 1 = one exposure line per pair (slim_gpu_exposure.h; 0: off)
 
 
 for _o in Opt:

@@ -237,6 +237,19 @@ int32_t matrix_predict(int32_t nrcmds, const slimgpu_model* model, slimgpu_matri
 int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu_matrix_t* mat, int32_t nusers,
                              const int32_t* users, int32_t* output, float* scores, int32_t* counts,
                              slimgpu_filter* filter = nullptr);
+// slim_gpu_exposure.h: per-item counts of the places of top-N lists at ncutoffs cutoffs, counted on the device
+// (exposure.hip), and their summaries; exposure ([ncutoffs][ncols]) and summary ([ncutoffs]) may be null.  A
+// caller's lists uploaded (exposure.hip); the lists of matrix_predict_lists and of model_evaluate counted where
+// they are made (resident_eval.hip).  SLIM_ERROR_INPUT with nothing queued or written.
+int32_t matrix_list_exposure(slimgpu_matrix_t* mat, const int32_t* fmarker, int32_t fm_ncols, int64_t nlists,
+                             int32_t nrcmds, const int32_t* ids, const int32_t* counts, int32_t ncutoffs,
+                             const int32_t* cutoffs, uint32_t* exposure, slimgpu_exposure_t* summary);
+int32_t matrix_predict_exposure(slimgpu_matrix_t* mat, const slimgpu_model* model, int32_t nrcmds, int32_t nusers,
+                                const int32_t* users, slimgpu_filter* filter, const int32_t* fmarker, int32_t fm_ncols,
+                                int32_t ncutoffs, const int32_t* cutoffs, uint32_t* exposure,
+                                slimgpu_exposure_t* summary);
+int32_t model_evaluate_exposure(slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
+                                int32_t ncutoffs, EvalResult* out, uint32_t* exposure, slimgpu_exposure_t* summary);
 slimgpu_eval_stats_t& last_eval_stats();
 // facts of a row view, for the scorers: d_facts[0] = entries of its longest row, d_facts[1] = 1 when the
 // ids of some row do not ascend strictly (both preset to 0 by the caller).  Queues one kernel on

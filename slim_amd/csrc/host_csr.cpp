@@ -601,4 +601,85 @@ slim_csr_t* read_text_csr(const char* path) {
   return m;
 }
 
+// ---- slim_gpu_exposure.h ------------------------------------------------------
+int32_t exposure_cutoffs_check(const char* who, int32_t nrcmds, int32_t ncutoffs, const int32_t* cutoffs) {
+  std::string what;
+  if (nrcmds < 1) what = "nrcmds must be at least 1, not " + std::to_string(nrcmds);
+  else if (!cutoffs || ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS)
+    what = "between 1 and " + std::to_string(SLIMGPU_MAX_CUTOFFS) + " cutoffs, not " + std::to_string(ncutoffs);
+  for (int32_t k = 0; k < ncutoffs && what.empty(); ++k) {
+    if (cutoffs[k] < 1) what = "a cutoff must be at least 1, not " + std::to_string(cutoffs[k]);
+    else if (k > 0 && cutoffs[k] <= cutoffs[k - 1]) what = "the cutoffs must ascend strictly";
+  }
+  if (what.empty() && cutoffs[ncutoffs - 1] > nrcmds)
+    what = "the last cutoff is " + std::to_string(cutoffs[ncutoffs - 1]) + ", the lists have " +
+           std::to_string(nrcmds) + " places";
+  if (what.empty()) return SLIM_OK;
+  set_error(std::string(who) + ": " + what);
+  return SLIM_ERROR_INPUT;
+}
+
+int32_t exposure_lists_check(const char* who, int32_t ncols, int64_t nlists, int32_t nrcmds, const int32_t* ids,
+                             const int32_t* counts, int32_t ncutoffs, const int32_t* cutoffs) {
+  if (const int32_t rc = exposure_cutoffs_check(who, nrcmds, ncutoffs, cutoffs); rc != SLIM_OK) return rc;
+  std::string what;
+  if (ncols < 1) what = "ncols must be at least 1, not " + std::to_string(ncols);
+  else if (nlists < 0) what = "nlists must be at least 0, not " + std::to_string(nlists);
+  else if (nlists > 0 && !ids) what = "no lists are given for nlists = " + std::to_string(nlists);
+  for (int64_t q = 0; counts && q < nlists && what.empty(); ++q)
+    if (counts[q] < 0 || counts[q] > nrcmds)
+      what = "counts[" + std::to_string(q) + "] is " + std::to_string(counts[q]) + ", outside [0, " +
+             std::to_string(nrcmds) + "]";
+  if (what.empty()) return SLIM_OK;
+  set_error(std::string(who) + ": " + what);
+  return SLIM_ERROR_INPUT;
+}
+
+void list_exposure_host(int32_t ncols, int64_t nlists, int32_t nrcmds, const int32_t* ids, const int32_t* counts,
+                        int32_t K, const int32_t* cutoffs, uint32_t* E, int64_t* outside) {
+  std::fill(E, E + (size_t)K * (size_t)ncols, 0u);
+  std::fill(outside, outside + K, (int64_t)0);
+  for (int64_t q = 0; q < nlists; ++q) {
+    const int32_t len = std::min(counts ? counts[q] : nrcmds, cutoffs[K - 1]);
+    const int32_t* row = ids + q * (int64_t)nrcmds;
+    int32_t b = 0;  // the band of place p: the first cutoff above it
+    for (int32_t p = 0; p < len; ++p) {
+      while (p >= cutoffs[b]) ++b;
+      const int32_t i = row[p];
+      if (i < 0 || i >= ncols) ++outside[b];
+      else ++E[(size_t)b * (size_t)ncols + (size_t)i];
+    }
+  }
+  for (int32_t k = 1; k < K; ++k) {
+    outside[k] += outside[k - 1];
+    for (int32_t i = 0; i < ncols; ++i) E[(size_t)k * (size_t)ncols + i] += E[(size_t)(k - 1) * (size_t)ncols + i];
+  }
+}
+
+void exposure_summary(int32_t ncols, const uint32_t* pop, const int32_t* fmarker, int32_t fm_ncols, int64_t nlists,
+                      const uint32_t* E, int64_t outside, slimgpu_exposure_t* out) {
+  typedef __int128 wide;
+  slimgpu_exposure_t s = {};
+  s.lists = nlists; s.outside = outside; s.ncols = ncols;
+  wide popsum = 0;
+  for (int32_t i = 0; i < ncols; ++i) {
+    const uint32_t e = E[i];
+    if (!e) continue;
+    s.slots += e;
+    ++s.distinct;
+    if (fmarker && (i >= fm_ncols || fmarker[i] != 0)) s.tail_slots += e;
+    if (pop) popsum += (wide)e * (wide)pop[i];
+  }
+  std::vector<uint32_t> x(E, E + ncols);
+  std::sort(x.begin(), x.end());
+  wide gnum = 0;
+  for (int32_t j = 1; j <= ncols; ++j) gnum += (wide)(2 * (int64_t)j - ncols - 1) * (wide)x[(size_t)j - 1];
+  auto ratio = [](wide num, wide den) { return den == 0 ? 0.0 : (double)num / (double)den; };
+  s.coverage = ratio(s.distinct, ncols);
+  s.tail_share = ratio(s.tail_slots, s.slots);
+  s.gini = ratio(gnum, (wide)ncols * (wide)s.slots);
+  s.avg_pop = ratio(popsum, s.slots);
+  *out = s;
+}
+
 }  // namespace slimamd

@@ -146,6 +146,21 @@ EvalResult evaluate(const slim_csr_t* model, const slim_csr_t* trn,
                     int32_t fm_ncols, const int32_t* lists = nullptr,
                     const int32_t* counts = nullptr);
 
+// slim_gpu_exposure.h on the host.  exposure_cutoffs_check: 1 <= K <= SLIMGPU_MAX_CUTOFFS cutoffs, each at least
+// 1, strictly ascending, the last at most nrcmds.  exposure_lists_check: that and the lists of a caller (ncols >= 1,
+// nlists >= 0, ids unless nlists == 0, every counts[q] in [0, nrcmds]).  Both: SLIM_OK, or SLIM_ERROR_INPUT with
+// "<who>: ..." as the error text.
+int32_t exposure_cutoffs_check(const char* who, int32_t nrcmds, int32_t ncutoffs, const int32_t* cutoffs);
+int32_t exposure_lists_check(const char* who, int32_t ncols, int64_t nlists, int32_t nrcmds, const int32_t* ids,
+                             const int32_t* counts, int32_t ncutoffs, const int32_t* cutoffs);
+// the definition in code: E[K][ncols] and outside[K] are cleared, then every place p < min(len_q, c_{K-1}) adds one
+// to the counter of its band and a last pass turns bands into cumulative counts (the device kernel's two steps)
+void list_exposure_host(int32_t ncols, int64_t nlists, int32_t nrcmds, const int32_t* ids, const int32_t* counts,
+                        int32_t ncutoffs, const int32_t* cutoffs, uint32_t* E, int64_t* outside);
+// the summary of one cutoff's counters E[ncols]: exact integers, 128-bit numerators, one division per double
+void exposure_summary(int32_t ncols, const uint32_t* pop, const int32_t* fmarker, int32_t fm_ncols, int64_t nlists,
+                      const uint32_t* E, int64_t outside, slimgpu_exposure_t* out);
+
 // ---- files ------------------------------------------------------------------
 bool write_binrow(const slim_csr_t* m, const char* path);   // api.c:174-177
 slim_csr_t* read_binrow(const char* path);                  // api.c:187-194

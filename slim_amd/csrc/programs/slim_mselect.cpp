@@ -10,7 +10,7 @@ int main(int argc, char** argv) {
       {"ifmt", true},    {"binarize", false}, {"optTol", true},  {"niters", true},
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
-      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"evalnegpop", false}, {"gpukernel", true}, {"help", false}};
+      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"evalnegpop", false}, {"evalexposure", false}, {"gpukernel", true}, {"help", false}};
   specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() != 3) {
@@ -22,6 +22,8 @@ int main(int argc, char** argv) {
                 "   -evalnegs=i -evalseed=i  (engine extension: evaluate 1-vs-k on i sampled negatives per user, drawn on\n"
                 "   the device with that seed (default 1); needs the evaluation in HBM, nrcmds <= 128 and no filter)\n"
                 "   -evalnegpop  (with -evalnegs: draw the negatives in proportion to item popularity, not uniformly)\n"
+                "   -evalexposure  (engine extension: one more line per pair on what its lists show -- coverage, tail share,\n"
+                "   Gini, mean popularity, counted on the device; needs the evaluation in HBM, nrcmds <= 128, no -evalnegs)\n"
                 "   (-nrcmds above 128 is evaluated in HBM from the ranks of the held-out items: no lists are formed)\n"
                 "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n"
                 "%s   (engine extension: every pair is evaluated under the filter; a held-out item it removes is a miss;\n"
@@ -41,6 +43,10 @@ int main(int argc, char** argv) {
   if (evalseed < 0 || evalseed > 0xFFFFFFFFll) die("Invalid -evalseed of " + a.str("evalseed", "") + ".");
   const bool evalnegpop = a.has("evalnegpop");
   if (evalnegpop && evalnegs < 1) die("-evalnegpop weights the sampled negatives: it needs -evalnegs.");
+  const bool evalexposure = a.has("evalexposure");
+  if (evalexposure && evalnegs > 0) die("-evalexposure does not combine with -evalnegs: the exposure of sampled lists is not built.");
+  if (evalexposure && (nrcmds < 1 || nrcmds > 128))
+    die("-evalexposure needs lists of 1 to 128 places (the lists behind the evaluation), not " + std::to_string(nrcmds) + ".");
   const bool filtered = filter_options(a);
   filter_files_exist(a);
   if (evalnegs > 0 && filtered) die("-evalnegs takes no item filter: candidate rows are scored as they are.");
@@ -120,6 +126,11 @@ int main(int argc, char** argv) {
     die(std::string("-evalstride needs the evaluation in HBM (one GPU, nrcmds >= 1, SLIM_GPU_RESIDENT and "
                     "SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ") +
         (nrcmds < 1 ? "nrcmds is " + std::to_string(nrcmds) : std::string(SLIMGPU_LastError())));
+  if (evalexposure && (!evalset || ranked))
+    die(std::string("-evalexposure needs the evaluation in HBM (one GPU, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT "
+                    "not 0, a matrix staged without merged pairs): ") +
+        (!resident ? std::string("the models of this grid do not stay in HBM")
+         : evr_env && std::atoi(evr_env) == 0 ? std::string("SLIM_GPU_EVAL_RESIDENT=0") : std::string(SLIMGPU_LastError())));
   // nor is there an evaluation under a filter outside HBM: no silent evaluation on the raw catalogue
   CliFilter flt;
   int32_t rrows = 0, rcols = 0;  // the resident models are as wide as the staged matrix
@@ -199,12 +210,15 @@ int main(int argc, char** argv) {
     Eval e;
     double em[4];
     int32_t env[3];
+    slimgpu_exposure_t expo = {};
     // (one list length: the filtered call's only row is SLIMGPU_ModelEvaluate's; a null filter is no filter)
     const bool evaluated =
         evalset && (cands    ? SLIMGPU_ModelEvaluateCandidates(evalset, dmodel, cands, 1, em, env)
                     : ranked ? SLIMGPU_ModelEvaluateRankedFiltered(evalset, dmodel, flt.handle, 1, &cutoff, em, env)
-                             : SLIMGPU_ModelEvaluateAtFiltered(evalset, dmodel, flt.handle, 1, em, env)) == SLIM_OK;
-    if (!evaluated && (stride > 1 || filtered || cands)) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
+                    : evalexposure
+                        ? SLIMGPU_ModelEvaluateExposure(evalset, dmodel, flt.handle, 1, em, env, nullptr, &expo)
+                        : SLIMGPU_ModelEvaluateAtFiltered(evalset, dmodel, flt.handle, 1, em, env)) == SLIM_OK;
+    if (!evaluated && (stride > 1 || filtered || cands || evalexposure)) die(std::string("evaluation failed: ") + SLIMGPU_LastError());
     if (evaluated) {
       e.hr = em[0]; e.hr_head = em[1]; e.hr_tail = em[2]; e.arhr = em[3];
       e.nvalid = env[0]; e.nvalid_head = env[1]; e.nvalid_tail = env[2];
@@ -223,6 +237,9 @@ int main(int argc, char** argv) {
     }
     std::printf("l1r: %.2le l2r: %.2le nnz: %7zd hr: %.4f hr_head: %.4f hr_tail: %.4f arhr: %.4f time: %.2lf\n",
                 l1, l2, resident ? (ssize_t)SLIMGPU_ModelNnz(dmodel) : static_cast<slim_csr_t*>(model)->rowptr[static_cast<slim_csr_t*>(model)->nrows], e.hr, e.hr_head, e.hr_tail, e.arhr, st.total_ms / 1e3);
+    if (evalexposure)
+      std::printf("  exposure@%d: coverage: %.4f tail_share: %.4f gini: %.4f avg_pop: %.2f distinct: %d slots: %lld\n",
+                  nrcmds, expo.coverage, expo.tail_share, expo.gini, expo.avg_pop, expo.distinct, (long long)expo.slots);
     if (e.hr > best_hr) { best_hr = e.hr; bh_l1 = l1; bh_l2 = l2; }
     if (e.arhr > best_ar) { best_ar = e.arhr; ba_l1 = l1; ba_l2 = l2; }
   }

@@ -42,6 +42,10 @@ struct slimgpu_evalset {
   slimamd::DeviceBuffer<int64_t> d_tbase;
   slimamd::DeviceBuffer<slimamd::UserTerms> d_rterms;  // [SLIMGPU_MAX_CUTOFFS][nsel]: one slice of cutoffs
   hipEvent_t evk0 = nullptr, evk1 = nullptr;
+  // exposure (slim_gpu_exposure.h): the marker's host copy, the matrix's column counts (fetched by the first
+  // exposure call) and the host image of the counters: the summaries are formed on the host
+  std::vector<int32_t> h_fm;
+  std::vector<uint32_t> h_pop, h_expo;
   const int64_t* tbase() const { return d_tbase.get() ? d_tbase.get() : tst.ptr.get(); }
   ~slimgpu_evalset() {
     (void)hipSetDevice(device);
@@ -141,6 +145,7 @@ slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* 
     const int32_t nsel = es->nsel;
     es->tst = stage_csr(tst, nall, /*values=*/false, stream);
     es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
+    es->h_fm.assign(fmarker, fmarker + fm_ncols);
     es->d_terms = DeviceBuffer<UserTerms>((size_t)cut.n * (size_t)nsel);
     es->d_out = DeviceBuffer<unsigned long long>(sizeof(EvalOut) / sizeof(unsigned long long));
     if (fm_ncols > 0)
@@ -320,6 +325,76 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
     return SLIM_OK;
   } catch (const HipFail& e) {
     return hip_failure(who, e);
+  }
+}
+
+namespace {
+// the column counts of a staged matrix (the popularity of slimgpu_exposure_t::avg_pop)
+void column_counts(const slimgpu_matrix_t* mat, int32_t ncols, std::vector<uint32_t>& pop) {
+  std::vector<int64_t> cp((size_t)ncols + 1);
+  if (matrix_get_column_view(mat, cp.data(), nullptr, nullptr, nullptr) != SLIM_OK)
+    throw HipFail{hipErrorUnknown, "the column pointer of the staged matrix"};
+  pop.resize((size_t)ncols);
+  for (int32_t i = 0; i < ncols; ++i) pop[(size_t)i] = (uint32_t)(cp[(size_t)i + 1] - cp[(size_t)i]);
+}
+int32_t check_exposure_width(const char* who, const DeviceCsrView& R, const DeviceRowView& W) {
+  if (W.ncols == R.ncols) return SLIM_OK;
+  return refuse(std::string(who) + ": the model has " + std::to_string(W.ncols) + " columns, the matrix " +
+                std::to_string(R.ncols) + ": the exposure is counted over the matrix's items");
+}
+}  // namespace
+
+// model_evaluate with the lists kept (EvalTargets::keep_lists: the fused kernel writes them beside its terms, the
+// wave path writes them anyway) and counted where they lie (exposure.hip).  The figures are model_evaluate's: the
+// same kernels form the same records.  The list buffers and the counters are the workspace's and only grow.
+int32_t model_evaluate_exposure(slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
+                                int32_t ncutoffs, EvalResult* out, uint32_t* exposure, slimgpu_exposure_t* summary) {
+  const char* who = "SLIMGPU_ModelEvaluateExposure";
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (es && es->cut.n < 1)
+    return refuse(std::string(who) + ": the eval set was made by SLIMGPU_EvalSetCreateRanked and has no list length");
+  if (const int32_t rc = check_evaluation(who, out != nullptr, es, model, &ncutoffs, W, R); rc != SLIM_OK) return rc;
+  if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
+  if (const int32_t rc = check_exposure_width(who, R, W); rc != SLIM_OK) return rc;
+  const int32_t ncut = es->cut.n, nrcmds = es->cut.c[ncut - 1], ncols = R.ncols;
+  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    es->ws.allocs = 0;
+    int64_t first_down = 0;
+    if (es->h_pop.size() != (size_t)ncols) {  // (the first call on this eval set)
+      column_counts(es->mat, ncols, es->h_pop);
+      first_down = (int64_t)sizeof(int64_t) * ((int64_t)ncols + 1);
+    }
+    const HistoryView H = history_of(R, es);
+    if (es->nsel > 0) {
+      const ScorerRequest rq = EvalTargets{es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols,
+                                           es->d_terms.get(), es->cut, /*keep_lists=*/true};
+      const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
+      HIP_TRY(hipEventRecord(es->ev0, stream));
+      queue_exposure_clear(stream, ncols, es->cut, es->ws);
+      st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
+      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      queue_exposure_count(stream, R.num_cus, es->ws.oid.get(), es->ws.ocnt.get(), es->nsel, nrcmds, ncols, es->cut,
+                           es->ws);
+      queue_exposure_cumulate(stream, R.num_cus, ncols, es->cut, es->ws);
+    }
+    finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
+    const size_t down = fetch_exposure(stream, ncols, es->cut, es->ws, es->h_expo, es->h_pop.data(), es->h_fm.data(),
+                                       es->fm_ncols, es->nsel, /*engine_lists=*/true, exposure, summary);
+    g_eval_stats.d2h_bytes += (int64_t)down + first_down;
+    g_eval_stats.total_ms = ms_since(t_begin);
+    return SLIM_OK;
+  } catch (const HipFail& e) {
+    return hip_failure(who, e);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return SLIM_ERROR_MEMORY;
   }
 }
 
@@ -553,5 +628,87 @@ int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu
                              slimgpu_filter* filter) {
   return matrix_predict_impl("SLIMGPU_MatrixPredictLists", SLIMGPU_MAX_LIST, nrcmds, model, mat, nusers, users, output,
                              scores, counts, filter);
+}
+
+// matrix_predict_lists with the lists counted where they are made (score_exposure): only the counters come down
+int32_t matrix_predict_exposure(slimgpu_matrix_t* mat, const slimgpu_model* model, int32_t nrcmds, int32_t nusers,
+                                const int32_t* users, slimgpu_filter* filter, const int32_t* fmarker, int32_t fm_ncols,
+                                int32_t ncutoffs, const int32_t* cutoffs, uint32_t* exposure,
+                                slimgpu_exposure_t* summary) {
+  const char* who = "SLIMGPU_MatrixPredictExposure";
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (!model || !mat || nrcmds < 1 || nrcmds > SLIMGPU_MAX_LIST || (fmarker && fm_ncols < 0) ||
+      model_row_view(model, &W) != SLIM_OK || matrix_csr_view(mat, &R) != SLIM_OK)
+    return refuse(std::string(who) + ": bad arguments (a resident model, a staged matrix, 1 <= nrcmds <= " +
+                  std::to_string(SLIMGPU_MAX_LIST) + ")");
+  if (const int32_t rc = exposure_cutoffs_check(who, nrcmds, ncutoffs, cutoffs); rc != SLIM_OK) return rc;
+  if (const int32_t rc = check_user_list(who, nusers, users, R.nrows); rc != SLIM_OK) return rc;
+  if (const int32_t rc = check_pair(who, R, W); rc != SLIM_OK) return rc;
+  if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
+  if (const int32_t rc = check_exposure_width(who, R, W); rc != SLIM_OK) return rc;
+  Cutoffs cut = {};
+  cut.n = ncutoffs;
+  for (int32_t k = 0; k < ncutoffs; ++k) cut.c[k] = cutoffs[k];
+  const auto t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int32_t rc = SLIM_OK;
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+    const int32_t nu = users ? nusers : R.nrows;
+    std::vector<uint32_t> pop, h_E;
+    column_counts(mat, R.ncols, pop);
+    ScorerWorkspace ws;
+    DeviceBuffer<int32_t> d_users;
+    if (nu > 0) {
+      ++ws.allocs;  // (the longest history's length)
+      if (users) {  // (pageable source: the copy has left the caller's array before the scorer is queued)
+        d_users = DeviceBuffer<int32_t>((size_t)nu);
+        ++ws.allocs;
+        HIP_TRY(hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)nu, hipMemcpyHostToDevice, stream));
+      }
+      const HistoryView H = resident_history(R, nu, d_users.get(),
+                                             longest_history(stream, R.num_cus, nu, d_users.get(), R.d_ptr, nullptr));
+      const ScorerChoice C = choose_scorer(W, H, ScorerRequest(LongListsRequest{nrcmds}));
+      const CandidateFilter F = filter_on_device(filter, R.device, stream, &ws.allocs);
+      HIP_TRY(hipEventCreate(&ev0));
+      HIP_TRY(hipEventCreate(&ev1));
+      HIP_TRY(hipEventRecord(ev0, stream));
+      st.path = score_exposure(W, H, C, R.num_cus, stream, ws, cut, F);
+      if (st.path == kRefused) {
+        set_error(std::string(who) + ": " + std::string(last_error()));
+        rc = SLIM_ERROR_INPUT;
+      } else {
+        HIP_TRY(hipEventRecord(ev1, stream));
+      }
+    }
+    if (rc == SLIM_OK) {
+      st.d2h_bytes = (int64_t)fetch_exposure(stream, R.ncols, cut, ws, h_E, pop.data(), fmarker, fm_ncols, nu,
+                                             /*engine_lists=*/true, exposure, summary) +
+                     (int64_t)sizeof(int64_t) * ((int64_t)R.ncols + 1) + (nu > 0 ? (int64_t)sizeof(int32_t) : 0);
+      if (nu > 0) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        st.kernel_ms = ms;
+        st.w_rows_read = R.nnz;
+      } else {
+        last_list_stats() = slimgpu_list_stats_t{};
+      }
+      st.device_allocs = ws.allocs;
+      st.total_ms = ms_since(t_begin);
+      g_eval_stats = st;
+    }
+  } catch (const HipFail& e) {
+    rc = hip_failure(who, e);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    rc = SLIM_ERROR_MEMORY;
+  }
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  return rc;
 }
 }  // namespace slimamd

@@ -27,7 +27,10 @@ struct ScorerWorkspace {
   DeviceBuffer<uint4> slab;
   DeviceBuffer<unsigned long long> lstats;
   DeviceBuffer<float> cand;                // candidate rows: the slot scores, laid out like the set
-  int allocs = 0;                          // device allocations since the caller last cleared it
+  // exposure (slim_gpu_exposure.h, exposure.hip): the counters [K][ncols], the places outside [0, ncols) [K]
+  DeviceBuffer<uint32_t> expo;
+  DeviceBuffer<unsigned long long> expo_out;
+  int allocs = 0;                         // device allocations since the caller last cleared it
   template <class T>
   T* need(DeviceBuffer<T>& b, size_t n) {
     if (b.bytes() < sizeof(T) * (n ? n : 1)) ++allocs;
@@ -72,6 +75,7 @@ struct EvalTargets {  // the users' terms of lists of cut.c[cut.n - 1]: the fuse
   int32_t fm_ncols;
   UserTerms* terms;  // [cut.n][positions]
   Cutoffs cut;
+  bool keep_lists = false;  // the lists behind the terms into ws.oid / osc / ocnt as well (the exposure call)
 };
 struct RankTargets {  // ranks and scores of the positions' test entries into ws.rank / ws.rscore
   const int64_t* tptr; const int32_t* tind;
@@ -190,7 +194,27 @@ size_t fetch_lists(const ScorerWorkspace& ws, int32_t nusers, int32_t nrcmds, hi
 ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice, int num_cus,
                        hipStream_t stream, ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts,
                        size_t* down, const CandidateFilter& F = {});
-// resident_eval.hip: what the calls on a staged matrix check of their arguments.  The matrix and the model of one
+// Exposure (slim_gpu_exposure.h, exposure.hip).  Three steps on `stream`, all queued: the counters ws.expo
+// [cut.n][ncols] and ws.expo_out [cut.n] reserved and cleared; every place p < min(cnt[q], cut.c[cut.n - 1]) of the
+// device lists ids[npos][N] (cnt == nullptr: N places each; ids 16-byte aligned) added once, to the counter of its
+// band -- any number of such calls add into the same counters; the bands turned into cumulative counts.
+void queue_exposure_clear(hipStream_t stream, int32_t ncols, const Cutoffs& cut, ScorerWorkspace& ws);
+void queue_exposure_count(hipStream_t stream, int num_cus, const int32_t* ids, const int32_t* cnt, int64_t npos,
+                          int32_t N, int32_t ncols, const Cutoffs& cut, ScorerWorkspace& ws);
+void queue_exposure_cumulate(hipStream_t stream, int num_cus, int32_t ncols, const Cutoffs& cut, ScorerWorkspace& ws);
+// Brings the counters down (drains `stream`), copies them to `exposure` ([cut.n][ncols], may be null) and forms the
+// summaries ([cut.n], may be null) on the host.  h_E: the host image, grown as needed.  engine_lists: the lists
+// were a scorer's, which writes no id outside [0, ncols): that tally stays where it is.  Returns the bytes.
+// Without a position (nlists == 0) nothing was queued and nothing comes down: the counters are all zero.
+size_t fetch_exposure(hipStream_t stream, int32_t ncols, const Cutoffs& cut, const ScorerWorkspace& ws,
+                      std::vector<uint32_t>& h_E, const uint32_t* pop, const int32_t* fmarker, int32_t fm_ncols,
+                      int64_t nlists, bool engine_lists, uint32_t* exposure, slimgpu_exposure_t* summary);
+// The lists of every position of H counted where they are made (score_lists without the fetch): up to 128 one
+// launch, on the long-list path slice after slice into the same counters; the counters are cumulative when the
+// stream has run.  Returns the path (kRefused: set_error says why, nothing is queued).
+ScorerPath score_exposure(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& choice, int num_cus,
+                          hipStream_t stream, ScorerWorkspace& ws, const Cutoffs& cut, const CandidateFilter& F = {});
+// resident_eval.hip: what the calls on a staged matrix check of their arguments. The matrix and the model of one
 // call: one device, one width, rows that are the caller's.  A list of users: at least one, without a list nusers
 // is 0 (nrows < 0: no more); rows of [0, nrows), ascending.  SLIM_OK, or SLIM_ERROR_INPUT with "<who>: ...".
 int32_t check_pair(const char* who, const DeviceCsrView& R, const DeviceRowView& W);

@@ -180,13 +180,19 @@ static const char kEvalNegsNeeds[] =
     "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGS needs the candidate evaluation in HBM (cd on one GPU, no filter, "
     "nrcmds <= 128, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ";
 
+static const char kEvalExposureNeeds[] =
+    "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALEXPOSURE needs the evaluation in HBM and lists of at most 128 (cd on one "
+    "GPU, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs, no sampled "
+    "negatives): ";
+
 // Py_SLIM_Mselect is this with no filter.  With one (slim_gpu_filter.h) every pair is evaluated under it, which
 // only the evaluation in HBM can do: where that is not to be had the call fails before the first solve.
-int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
-                                double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
-                                int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
-                                double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
-                                double* bestARAR, slimgpu_filter_t* filter) {
+// force_exposure / cells: Py_SLIM_MselectExposure (slim_gpu_exposure.h), slot 26 on whatever ioptions says.
+static int32_t mselect_impl(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
+                            double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
+                            int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
+                            double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
+                            double* bestARAR, slimgpu_filter_t* filter, bool force_exposure, double* cells) {
   const slim_csr_t* trn = as_csr(trnhandle);
   const slim_csr_t* tst = as_csr(tsthandle);
   if (!trn || !tst || !trn->rowptr || !tst->rowptr) return SLIM_ERROR_INPUT;
@@ -243,6 +249,29 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
       return SLIM_ERROR_INPUT;
     }
   }
+  // Exposure (slot 26, slim_gpu_exposure.h): every pair's lists are counted where the evaluation makes them.  What
+  // stands in the way is refused here, or below once the eval set is known: before the first solve.
+  const int32_t evalexpo = force_exposure ? 1
+                           : (!ioptions || ioptions[SLIM_OPTION_GPU_EVALEXPOSURE] == -1) ? 0
+                                                                                         : ioptions[SLIM_OPTION_GPU_EVALEXPOSURE];
+  if (evalexpo != 0) {
+    const char* res0 = std::getenv("SLIM_GPU_RESIDENT");
+    const char* evr0 = std::getenv("SLIM_GPU_EVAL_RESIDENT");
+    std::string why;
+    if (evalexpo != 1) why = "SLIM_OPTION_GPU_EVALEXPOSURE must be 0 or 1, not " + std::to_string(evalexpo);
+    else if (admm) why = "the ADMM solver leaves no model in HBM";
+    else if (base.ngpus > 1) why = "the grid runs on several GPUs";
+    else if (res0 && std::atoi(res0) == 0) why = "SLIM_GPU_RESIDENT=0 keeps the models on the host";
+    else if (evr0 && std::atoi(evr0) == 0) why = "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host";
+    else if (nrcmds < 1 || nrcmds > 128)
+      why = "nrcmds is " + std::to_string(nrcmds) + ": the lists behind the evaluation have 1 to 128 places";
+    else if (evalnegs > 0)
+      why = "SLIM_OPTION_GPU_EVALNEGS is on: the exposure of sampled candidate lists is not built";
+    if (!why.empty()) {
+      set_error(std::string(kEvalExposureNeeds) + why);
+      return SLIM_ERROR_INPUT;
+    }
+  }
   slimgpu_matrix_t* mat =
       admm ? nullptr : multi_from_host(trn->nrows, trn->rowptr, trn->rowind, trn->rowval, base, &status);
   if (!mat && !admm) return status;
@@ -278,12 +307,12 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
   if (resident && !(evr_env && std::atoi(evr_env) == 0)) {
     evalset = evalset_create(mat, tst, fmarker, ncols, 1, &nrcmds, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
                              &status);
-    if (!evalset && stride == 1 && !filter) set_error("");
+    if (!evalset && stride == 1 && !filter && !evalexpo) set_error("");
   } else if (may_reside && nrcmds > 128 && !(evr_env && std::atoi(evr_env) == 0)) {
     evalset = evalset_create_ranked(mat, tst, fmarker, ncols, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
                                     &status);
     ranked = resident = evalset != nullptr;
-    if (!evalset && stride == 1 && !filter) set_error("");
+    if (!evalset && stride == 1 && !filter && !evalexpo) set_error("");
   }
   if (stride > 1 && !evalset) {
     const std::string why = SLIMGPU_LastError();
@@ -292,6 +321,15 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
               "merged pairs; above 128 a model the chunk scorer serves)" +
               (nrcmds < 1 ? ": nrcmds is " + std::to_string(nrcmds) : std::string()) +
               (why.empty() ? std::string() : ": " + why));
+    std::free(fmarker);
+    matrix_free(mat);
+    return SLIM_ERROR_INPUT;
+  }
+  if (evalexpo && (!evalset || ranked)) {  // (a matrix with merged duplicates, replicas on other GPUs, ...)
+    std::string why = mat && !matrix_replicas(mat).empty() ? "the grid runs on several GPUs" : SLIMGPU_LastError();
+    if (why.empty()) why = "the eval set could not be made";
+    set_error(std::string(kEvalExposureNeeds) + why);
+    evalset_free(evalset);
     std::free(fmarker);
     matrix_free(mat);
     return SLIM_ERROR_INPUT;
@@ -394,6 +432,7 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
       };
       bool on_gpu = false, evaluated = false;
       EvalResult ev;
+      slimgpu_exposure_t expo = {};
       ssize_t model_nnz_now = 0;
       if (resident) {
         slimgpu_model* dprev = dmodel;
@@ -404,11 +443,12 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
           break;
         }
         model_nnz_now = (ssize_t)model_nnz(dmodel);
-        evaluated = evalset && (cands    ? model_evaluate_candidates(evalset, dmodel, cands, 1, &ev)
-                                : ranked ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev, filter)
-                                         : model_evaluate(evalset, dmodel, 1, &ev, filter)) == SLIM_OK;
-        // (no silent evaluation of everybody, without the filter, or on the whole catalogue)
-        if (!evaluated && (stride > 1 || filter || cands)) {
+        evaluated = evalset && (cands      ? model_evaluate_candidates(evalset, dmodel, cands, 1, &ev)
+                                : ranked   ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev, filter)
+                                : evalexpo ? model_evaluate_exposure(evalset, dmodel, filter, 1, &ev, nullptr, &expo)
+                                           : model_evaluate(evalset, dmodel, 1, &ev, filter)) == SLIM_OK;
+        // (no silent evaluation of everybody, without the filter, on the whole catalogue, or without the exposure)
+        if (!evaluated && (stride > 1 || filter || cands || evalexpo)) {
           rc = SLIM_ERROR;
           break;
         }
@@ -457,6 +497,16 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
                   "arhr: %.4f time: %.2lf\n",
                   opt.l1r, opt.l2r, model_nnz_now, ev.hr, ev.hr_head, ev.hr_tail,
                   ev.arhr, last_stats().total_ms / 1e3);
+      if (evalexpo) {  // (the lists of the grid's nrcmds, counted where the evaluation made them)
+        std::printf("  exposure@%d: coverage: %.4f tail_share: %.4f gini: %.4f avg_pop: %.2f distinct: %d slots: %lld\n",
+                    nrcmds, expo.coverage, expo.tail_share, expo.gini, expo.avg_pop, expo.distinct,
+                    (long long)expo.slots);
+        if (cells) {
+          double* c = cells + (size_t)SLIMGPU_EXPOSURE_CELL * ((size_t)a * (size_t)nl2 + (size_t)b);
+          c[0] = opt.l1r; c[1] = opt.l2r; c[2] = ev.hr; c[3] = ev.arhr;
+          c[4] = expo.coverage; c[5] = expo.tail_share; c[6] = expo.gini; c[7] = expo.avg_pop;
+        }
+      }
       if (resident && model) {  // (a fetched copy served the host scorer only)
         csr_free(model);
         model = nullptr;
@@ -489,6 +539,24 @@ int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
   std::free(fmarker);
   matrix_free(mat);
   return rc;
+}
+
+int32_t Py_SLIM_MselectFiltered(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
+                                double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
+                                int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
+                                double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
+                                double* bestARAR, slimgpu_filter_t* filter) {
+  return mselect_impl(trnhandle, tsthandle, ioptions, doptions, arrayl1, arrayl2, nl1, nl2, bestl1HR, bestl2HR,
+                      bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR, bestARAR, filter, false, nullptr);
+}
+
+int32_t Py_SLIM_MselectExposure(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
+                                double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
+                                int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
+                                double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
+                                double* bestARAR, slimgpu_filter_t* filter, double* cells) {
+  return mselect_impl(trnhandle, tsthandle, ioptions, doptions, arrayl1, arrayl2, nl1, nl2, bestl1HR, bestl2HR,
+                      bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR, bestARAR, filter, true, cells);
 }
 
 int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
@@ -1060,6 +1128,76 @@ int32_t Py_SLIM_ExplainCandidates(slim_t* model, slim_t* trnhandle, slimgpu_cand
   if (W->rowptr[W->nrows] > 0 && !W->rowval) return SLIM_ERROR;
   if (const int32_t rc = candset_fetch_ids(who, cs); rc != SLIM_OK) return rc;
   explain_candidates_host(W, trn, candset_host(cs), nwhy, why_items, why_terms, support);
+  return SLIM_OK;
+}
+
+// ------------------------------------------------- slim_gpu_exposure.h ------
+
+int32_t SLIMGPU_ListExposure(int32_t ncols, const uint32_t* pop, const int32_t* fmarker, int32_t fm_ncols,
+                             int64_t nlists, int32_t nrcmds, const int32_t* ids, const int32_t* counts,
+                             int32_t ncutoffs, const int32_t* cutoffs, uint32_t* exposure,
+                             slimgpu_exposure_t* summary) {
+  const char* who = "SLIMGPU_ListExposure";
+  set_error("");
+  if (const int32_t rc = exposure_lists_check(who, ncols, nlists, nrcmds, ids, counts, ncutoffs, cutoffs);
+      rc != SLIM_OK)
+    return rc;
+  if (fmarker && fm_ncols < 0) {
+    set_error(std::string(who) + ": fm_ncols must be at least 0");
+    return SLIM_ERROR_INPUT;
+  }
+  try {
+    std::vector<uint32_t> own;
+    uint32_t* E = exposure;
+    if (!E) {
+      own.resize((size_t)ncutoffs * (size_t)ncols);
+      E = own.data();
+    }
+    int64_t outside[SLIMGPU_MAX_CUTOFFS];
+    list_exposure_host(ncols, nlists, nrcmds, ids, counts, ncutoffs, cutoffs, E, outside);
+    for (int32_t k = 0; summary && k < ncutoffs; ++k)
+      exposure_summary(ncols, pop, fmarker, fm_ncols, nlists, E + (size_t)k * (size_t)ncols, outside[k], &summary[k]);
+    return SLIM_OK;
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+}
+
+int32_t SLIMGPU_MatrixListExposure(slimgpu_matrix_t* mat, const int32_t* fmarker, int32_t fm_ncols, int64_t nlists,
+                                   int32_t nrcmds, const int32_t* ids, const int32_t* counts, int32_t ncutoffs,
+                                   const int32_t* cutoffs, uint32_t* exposure, slimgpu_exposure_t* summary) {
+  set_error("");
+  return matrix_list_exposure(mat, fmarker, fm_ncols, nlists, nrcmds, ids, counts, ncutoffs, cutoffs, exposure, summary);
+}
+
+int32_t SLIMGPU_MatrixPredictExposure(slimgpu_matrix_t* mat, const slimgpu_model_t* model, int32_t nrcmds,
+                                      int32_t nusers, const int32_t* users, slimgpu_filter_t* filter,
+                                      const int32_t* fmarker, int32_t fm_ncols, int32_t ncutoffs,
+                                      const int32_t* cutoffs, uint32_t* exposure, slimgpu_exposure_t* summary) {
+  set_error("");
+  return matrix_predict_exposure(mat, model, nrcmds, nusers, users, filter, fmarker, fm_ncols, ncutoffs, cutoffs,
+                                 exposure, summary);
+}
+
+int32_t SLIMGPU_ModelEvaluateExposure(slimgpu_evalset_t* es, const slimgpu_model_t* model, slimgpu_filter_t* filter,
+                                      int32_t ncutoffs, double* metrics, int32_t* nvalid, uint32_t* exposure,
+                                      slimgpu_exposure_t* summary) {
+  set_error("");
+  if (!metrics || !nvalid) return SLIM_ERROR_INPUT;
+  EvalResult ev[SLIMGPU_MAX_CUTOFFS];
+  if (ncutoffs < 1 || ncutoffs > SLIMGPU_MAX_CUTOFFS) {
+    set_error("SLIMGPU_ModelEvaluateExposure: ncutoffs must be the eval set's number of list lengths");
+    return SLIM_ERROR_INPUT;
+  }
+  const int32_t rc = model_evaluate_exposure(es, model, filter, ncutoffs, ev, exposure, summary);
+  if (rc != SLIM_OK) return rc;
+  for (int32_t k = 0; k < ncutoffs; ++k) {
+    double* m = metrics + 4 * k;
+    int32_t* n = nvalid + 3 * k;
+    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
+    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
+  }
   return SLIM_OK;
 }
 

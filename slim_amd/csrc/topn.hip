@@ -253,7 +253,8 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
   const ChunkPlan& P = C.plan;
   const int32_t ncols = std::max(W.ncols, 1), nrcmds = C.nrcmds;
   const EvalTargets* ev = std::get_if<EvalTargets>(&rq);
-  const bool lists = std::holds_alternative<ListsRequest>(rq) || std::holds_alternative<LongListsRequest>(rq);
+  const bool lists = std::holds_alternative<ListsRequest>(rq) || std::holds_alternative<LongListsRequest>(rq) ||
+                     (ev && ev->keep_lists);
   reserve_scorer(ws, C, W.nrows, ncols, H.nusers, num_cus, lists);
   HIP_TRY(hipMemsetAsync(ws.queue.get(), 0, 2 * sizeof(int32_t), stream));
   if (lists || C.path == kWave) HIP_TRY(hipMemsetAsync(ws.ocnt.get(), 0, sizeof(int32_t) * (size_t)H.nusers, stream));
@@ -271,6 +272,7 @@ ScorerLaunch queue_scorer(const DeviceRowView& W, const HistoryView& H, const Sc
         fill_common(A, W, H, C, ws);
         A.tptr = ev->tptr; A.tind = ev->tind; A.fmarker = ev->fmarker; A.fm_ncols = ev->fm_ncols; A.terms = ev->terms;
         A.cut = ev->cut;
+        if (ev->keep_lists) fill_lists(A, ws);
         fill_filter(A.flt, F);
         launch_scorer(pick_kernel<TopNEvalArgs>(P), L, 64 * P.t2w, P.lds, stream, A);
       } else {
@@ -452,6 +454,44 @@ ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const Score
   }
   ls.path = C.path;
   if (down) *down = bytes;
+  g_list_stats = ls;
+  return C.path;
+}
+
+ScorerPath score_exposure(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& C, int num_cus,
+                          hipStream_t stream, ScorerWorkspace& ws, const Cutoffs& cut, const CandidateFilter& F) {
+  if (C.path == kRefused) {
+    set_error(C.refusal);
+    return kRefused;
+  }
+  slimgpu_list_stats_t ls = {};
+  const int32_t nrcmds = C.nrcmds, ncols = std::max(W.ncols, 1);
+  const ScorerRequest rq = LongListsRequest{nrcmds};
+  queue_exposure_clear(stream, ncols, cut, ws);
+  if (C.path != kLong) {
+    queue_scorer(W, H, C, rq, num_cus, stream, ws, F);
+    queue_exposure_count(stream, num_cus, ws.oid.get(), ws.ocnt.get(), H.nusers, nrcmds, ncols, cut, ws);
+    ls.slices = 1;
+  } else {
+    ws.need(ws.lstats, 8);
+    HIP_TRY(hipMemsetAsync(ws.lstats.get(), 0, 8 * sizeof(unsigned long long), stream));
+    const int32_t step = long_slice_users(H.nusers, nrcmds);
+    for (int32_t s0 = 0; s0 < H.nusers; s0 += step) {  // (one stream: a slice is counted before the next overwrites it)
+      HistoryView S = H;
+      S.nusers = std::min(step, H.nusers - s0);
+      if (H.users) S.users = H.users + s0; else S.user0 = H.user0 + s0;
+      queue_scorer(W, S, C, rq, num_cus, stream, ws, F);
+      queue_exposure_count(stream, num_cus, ws.oid.get(), ws.ocnt.get(), S.nusers, nrcmds, ncols, cut, ws);
+      ++ls.slices;
+    }
+    unsigned long long h[5] = {};
+    HIP_TRY(hipMemcpyAsync(h, ws.lstats.get(), sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    ls.candidates = (int64_t)h[0]; ls.contenders = (int64_t)h[1]; ls.refine_passes = (int64_t)h[2];
+    ls.lds_sorts = (int64_t)h[3]; ls.key_refines = (int64_t)h[4];
+  }
+  queue_exposure_cumulate(stream, num_cus, ncols, cut, ws);
+  ls.path = C.path;
   g_list_stats = ls;
   return C.path;
 }

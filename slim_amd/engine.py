@@ -135,6 +135,27 @@ class ResidentModel(object):
         out = (ids.reshape(n, nrcmds), scores.reshape(n, nrcmds))
         return out + (counts,) if return_counts else out
 
+    def exposure(self, device_matrix, nrcmds=10, cutoffs=None, users=None, filter=None, fmarker=None):
+        """SLIMGPU_MatrixPredictExposure: how often every item stands in the lists predict() would return with the
+        same nrcmds / users / filter, cut at each of `cutoffs` (ascending, at most 8, the last <= nrcmds; None:
+        (nrcmds,)).  The lists are counted where they are made: only the counters come down.  fmarker (0 head /
+        1 tail per item) gives the tail share.  Returns (E [len(cutoffs), ncols] uint32, summaries): one dict per
+        cutoff with the fields of slimgpu_exposure_t (include/slim_gpu_exposure.h) and "nrcmds"."""
+        nrcmds = int(nrcmds)
+        cut = _cutoff_array((nrcmds,) if cutoffs is None else cutoffs)
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        fm = None if fmarker is None else np.ascontiguousarray(fmarker, np.int32)
+        E = np.zeros((max(cut.size, 1), device_matrix.ncols), np.uint32)
+        summ = (_lib.Exposure * max(cut.size, 1))()
+        st = self._lib.SLIMGPU_MatrixPredictExposure(
+            device_matrix.handle, self.handle, nrcmds, 0 if users is None else users.size, _ptr(users),
+            None if filter is None else filter.handle, _ptr(fm), 0 if fm is None else fm.size, cut.size, _ptr(cut),
+            _ptr(E), C.cast(summ, C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_MatrixPredictExposure failed (%d): %s" % (st, _lib.last_error()))
+        return E[:cut.size], _exposure_dicts(summ, cut)
+
     def score_candidates(self, device_matrix, cset, users=None, nrcmds=None):
         """SLIMGPU_MatrixScoreCandidates: the 1-vs-k scores of the candidate rows of a CandidateSet
         (DeviceMatrix.candidate_set) for every row of the staged matrix, or for the rows in `users` (strictly
@@ -392,6 +413,51 @@ def eval_stats(lib=None):
     return st.as_dict()
 
 
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _cutoff_array(cutoffs):
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(cutoffs)), np.int32)
+
+
+def _exposure_dicts(summ, cut):
+    return [dict(summ[k].as_dict(), nrcmds=int(c)) for k, c in enumerate(cut)]
+
+
+def _exposure_lists(ids, counts):
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim != 2:
+        raise ValueError("list_exposure: ids is [lists, nrcmds]")
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, np.int32).ravel()
+        if counts.size != ids.shape[0]:
+            raise ValueError("list_exposure: one count per list")
+    return ids, counts
+
+
+def list_exposure(ids, counts, ncols, cutoffs, pop=None, fmarker=None, lib=None):
+    """SLIMGPU_ListExposure, on the host: E[k, i] = the places p < min(counts[q], cutoffs[k]) of the lists
+    ids [lists, nrcmds] that hold item i (counts None: every list is full).  pop (uint32 per item) gives avg_pop,
+    fmarker (0 head / 1 tail) the tail share.  Returns (E [len(cutoffs), ncols] uint32, summaries) as
+    ResidentModel.exposure does."""
+    lib = lib or _lib.load()
+    ids, counts = _exposure_lists(ids, counts)
+    cut = _cutoff_array(cutoffs)
+    pop = None if pop is None else np.ascontiguousarray(pop, np.uint32)
+    fm = None if fmarker is None else np.ascontiguousarray(fmarker, np.int32)
+    if pop is not None and pop.size != ncols:
+        raise ValueError("list_exposure: pop has one entry per item")
+    E = np.zeros((max(cut.size, 1), max(int(ncols), 1)), np.uint32)
+    summ = (_lib.Exposure * max(cut.size, 1))()
+    st = lib.SLIMGPU_ListExposure(int(ncols), _ptr(pop), _ptr(fm), 0 if fm is None else fm.size, ids.shape[0],
+                                  ids.shape[1], _ptr(ids), _ptr(counts), cut.size, _ptr(cut), _ptr(E),
+                                  C.cast(summ, C.c_void_p))
+    if st != SLIM_OK:
+        raise RuntimeError("SLIMGPU_ListExposure failed (%d): %s" % (st, _lib.last_error()))
+    return E[:cut.size], _exposure_dicts(summ, cut)
+
+
 def list_stats(lib=None):
     """Counters of the most recent PredictLists / ModelPredictLists / MatrixPredictLists on this thread."""
     st = _lib.ListStats()
@@ -452,6 +518,25 @@ class Evaluator(object):
         return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
+
+    def evaluate_exposure(self, model, filter=None):
+        """SLIMGPU_ModelEvaluateExposure: evaluate_at()'s list and, from the same scoring pass, the exposure of the
+        lists behind it at the eval set's cutoffs, users and marker: (figures, (E, summaries)) with E
+        [len(cutoffs), ncols] uint32 and one dict per cutoff (slimgpu_exposure_t's fields and "nrcmds")."""
+        n = len(self.cutoffs)
+        met = np.zeros(4 * max(n, 1), np.float64)
+        nv = np.zeros(3 * max(n, 1), np.int32)
+        E = np.zeros((max(n, 1), self._matrix.ncols), np.uint32)
+        summ = (_lib.Exposure * max(n, 1))()
+        st = self._lib.SLIMGPU_ModelEvaluateExposure(self.handle, model.handle,
+                                                     None if filter is None else filter.handle, n, met, nv,
+                                                     _ptr(E), C.cast(summ, C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_ModelEvaluateExposure failed (%d): %s" % (st, _lib.last_error()))
+        figures = [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
+                    "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
+                    "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
+        return figures, (E[:n], _exposure_dicts(summ, self.cutoffs))
 
     def ranks(self, model, scores=False, filter=None):
         """SLIMGPU_ModelRanks(Filtered): the rank of every test entry of the evaluated users among the user's candidates
@@ -749,6 +834,21 @@ class DeviceMatrix(object):
         scipy rows this matrix was staged from; the same rows for the same seed and weights)."""
         return sample_candidates(trn, tst, nnegs, seed=seed, users=users, ncols=self.ncols, lib=self._lib,
                                  weights=weights)
+
+    def list_exposure(self, ids, counts, cutoffs, fmarker=None):
+        """SLIMGPU_MatrixListExposure: list_exposure() of a caller's lists counted on this matrix's device; ncols and
+        pop (the column counts) are the matrix's.  The outputs equal the host call's bit for bit."""
+        ids, counts = _exposure_lists(ids, counts)
+        cut = _cutoff_array(cutoffs)
+        fm = None if fmarker is None else np.ascontiguousarray(fmarker, np.int32)
+        E = np.zeros((max(cut.size, 1), self.ncols), np.uint32)
+        summ = (_lib.Exposure * max(cut.size, 1))()
+        st = self._lib.SLIMGPU_MatrixListExposure(self.handle, _ptr(fm), 0 if fm is None else fm.size, ids.shape[0],
+                                                  ids.shape[1], _ptr(ids), _ptr(counts), cut.size, _ptr(cut), _ptr(E),
+                                                  C.cast(summ, C.c_void_p))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_MatrixListExposure failed (%d): %s" % (st, _lib.last_error()))
+        return E[:cut.size], _exposure_dicts(summ, cut)
 
     def column_stats(self):
         return ColumnStats(self._lib, self.ncols)

@@ -119,7 +119,7 @@ def build_options(params):
     # engine extensions ride along when present (include/slim_gpu.h)
     for key, slot in (("gpu_seed", Opt.GPU_SEED), ("gpu_evalstride", Opt.GPU_EVALSTRIDE),
                       ("gpu_evalnegs", Opt.GPU_EVALNEGS), ("gpu_evalseed", Opt.GPU_EVALSEED),
-                      ("gpu_evalnegpop", Opt.GPU_EVALNEGPOP),
+                      ("gpu_evalnegpop", Opt.GPU_EVALNEGPOP), ("gpu_evalexposure", Opt.GPU_EVALEXPOSURE),
                       ("gpu_device", Opt.GPU_DEVICE),
                       ("gpu_kernel", Opt.GPU_KERNEL), ("gpu_colbegin", Opt.GPU_COLBEGIN),
                       ("gpu_colend", Opt.GPU_COLEND)):
@@ -326,8 +326,14 @@ class SLIM(object):
         print("Learning takes %.3f secs." % elapsed)
 
     def mselect(self, params, trndata, tstdata, arrayl1, arrayl2, nrcmds, allowed_items=None, blocked_items=None,
-                exclude=None, nnegs=0, negseed=1, negpop=False):
-        """nnegs > 0 (or params["gpu_evalnegs"] / ["gpu_evalseed"]): evaluate every pair 1-vs-k -- each held-out item
+                exclude=None, nnegs=0, negseed=1, negpop=False, exposure=False):
+        """exposure=True (or params["gpu_evalexposure"] = 1): besides HR / ARHR every pair reports what its lists show
+        (include/slim_gpu_exposure.h) -- catalogue coverage, tail share, Gini and mean popularity of the top-nrcmds
+        lists, counted on the device where the evaluation makes them.  One more line is printed per pair and the
+        table stays on the object as last_exposure: one dict per pair, in the order solved, with l1, l2, hr, arhr,
+        coverage, tail_share, gini, avg_pop.  The best pairs are chosen as before.  It needs the evaluation in HBM and
+        nrcmds <= 128, combines with the filter arguments and does not combine with nnegs.
+        nnegs > 0 (or params["gpu_evalnegs"] / ["gpu_evalseed"]): evaluate every pair 1-vs-k -- each held-out item
         against nnegs sampled items outside the user's history and test row, drawn once on the device from negseed
         (include/slim_gpu_sample.h); a score tie goes to the negative.  It takes no filter, needs nrcmds <= 128 and
         the evaluation in HBM, and costs about what the full-catalogue evaluation costs.  negpop=True (or
@@ -337,6 +343,10 @@ class SLIM(object):
         of predict() -- ORIGINAL item ids through trndata's maps, at most one of allowed and blocked, unknown ids
         ignored, exclude a SLIMatrix whose rows are put in the order of trndata's users.  A held-out item the
         filter removes counts as a miss.  (An engine extension; it needs the evaluation in HBM.)"""
+        if not isinstance(exposure, (bool, np.bool_)):
+            raise TypeError("exposure must be True or False.")
+        if exposure and nnegs:
+            raise TypeError("exposure=True does not combine with nnegs: the exposure of sampled lists is not built.")
         assert type(trndata) == SLIMatrix, "trndata must be a SLIMatrix object."
         assert type(tstdata) == SLIMatrix, "tstdata must be a SLIMatrix object."
         if allowed_items is not None and blocked_items is not None:
@@ -360,14 +370,21 @@ class SLIM(object):
                 np.ascontiguousarray(np.sort(arrayl2), dtype=np.float64),
                 len(arrayl1), len(arrayl2)) + tuple(C.byref(b) for b in best)
         t0 = time.time()
-        if allowed_items is None and blocked_items is None and exclude is None:
+        self.last_exposure = None
+        cells = np.zeros((len(arrayl1) * len(arrayl2), _lib.EXPOSURE_CELL), np.float64) if exposure else None
+        if exposure and allowed_items is None and blocked_items is None and exclude is None:
+            rc = self._lib.Py_SLIM_MselectExposure(*(grid + (None, cells.ctypes.data_as(C.c_void_p))))
+        elif allowed_items is None and blocked_items is None and exclude is None:
             rc = self._lib.Py_SLIM_Mselect(*grid)
         else:   # the models of the grid are as wide as the staged training matrix: its largest item id + 1
             ncols = max(int(C.cast(trndata.handle, C.POINTER(_lib.CsrView)).contents.ncols), 1)
             flt = _candidate_filter(self._lib, trndata.item2id, trndata.nItems, ncols, trndata, allowed_items,
                                     blocked_items, exclude)
             try:
-                rc = self._lib.Py_SLIM_MselectFiltered(*(grid + (flt.handle,)))
+                if exposure:
+                    rc = self._lib.Py_SLIM_MselectExposure(*(grid + (flt.handle, cells.ctypes.data_as(C.c_void_p))))
+                else:
+                    rc = self._lib.Py_SLIM_MselectFiltered(*(grid + (flt.handle,)))
             finally:
                 flt.close()
         elapsed = time.time() - t0
@@ -382,6 +399,9 @@ class SLIM(object):
         print("The best AR is achieved by, l1: %.4f, l2:%.4f, HR:%.4f, AR:%.4f."
               % (l1ar, l2ar, hrar, arar))
         self.mselect_result = dict(bestHR=(l1hr, l2hr, hrhr, arhr), bestAR=(l1ar, l2ar, hrar, arar))
+        if exposure:
+            names = ("l1", "l2", "hr", "arhr", "coverage", "tail_share", "gini", "avg_pop")
+            self.last_exposure = [dict(zip(names, (float(v) for v in row))) for row in cells]
 
     # -- prediction ----------------------------------------------------------
     def _candidate_filter(self, data, allowed_items, blocked_items, exclude):
