@@ -80,8 +80,8 @@ int32_t Py_SLIM_ScoreCandidates(slim_t *model, slim_t *trn, slimgpu_candset_t *c
    evaluated by SLIMGPU_ModelEvaluateCandidates' path -- HR / ARHR of the lists of nrcmds among nnegs negatives and
    the held-out items.  The header prints nnegs, the seed and the set's entries; the selection of the best pairs is
    unchanged; EVALSTRIDE combines.  SLIM_ERROR_INPUT before the first solve, with a text that says which: a filter,
-   nrcmds > 128 (the candidate lists use the eval set's cutoffs), and whatever keeps the evaluation out of HBM (ADMM,
-   several GPUs, SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0).  Never a fall-back to the full-catalogue figures. */
+   nrcmds > 128 (the candidate lists use the eval set's cutoffs), and whatever keeps the evaluation out of HBM
+   (slim_gpu_grid.h has the list).  Never a fall-back to the full-catalogue figures. */
 enum {
   SLIM_OPTION_GPU_EVALNEGS = 23, /* sampled negatives per user; -1 or 0: off */
   SLIM_OPTION_GPU_EVALSEED = 24, /* the sampler's seed; -1: 1 */

@@ -62,10 +62,9 @@ slimgpu_evalset_t *SLIMGPU_EvalSetCreateAt(slimgpu_matrix_t *mat, slim_t *tsthan
 int32_t SLIMGPU_ModelEvaluateAt(slimgpu_evalset_t *es, const slimgpu_model_t *model,
                                 int32_t ncutoffs, double *metrics, int32_t *nvalid);
 /* Option slot of Py_SLIM_Mselect (and slim_mselect -evalstride=K): with K > 1 the grid evaluates users
- * 0, K, 2K, ... only; -1 or 1: every user.  Needs the evaluation in HBM: with ADMM, several GPUs,
- * SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0 or a matrix whose duplicates were merged the call fails
- * with SLIM_ERROR_INPUT before the first solve.  (nrcmds above 128 is served from the ranks of the held-out
- * items, slim_gpu_rank.h.) */
+ * 0, K, 2K, ... only; -1 or 1: every user.  Needs the evaluation in HBM (slim_gpu_grid.h lists what that
+ * takes): without it the call fails with SLIM_ERROR_INPUT before the first solve.  (nrcmds above 128 is served
+ * from the ranks of the held-out items, slim_gpu_rank.h.) */
 enum { SLIM_OPTION_GPU_EVALSTRIDE = 22 };
 /* Top-N of every row of the resident matrix through a resident model: only the lists come down.
  * Bit-identical to SLIMGPU_ModelPredict on the host handle of the same rows. */

@@ -96,10 +96,10 @@ enum { SLIM_OPTION_GPU_EVALEXPOSURE = 26 };   /* Py_SLIM_Mselect*: 1 = one expos
 /* Py_SLIM_MselectFiltered (filter NULL: Py_SLIM_Mselect) with slot 26 forced on; cells:
    [nl1*nl2][SLIMGPU_EXPOSURE_CELL] in the order the pairs are solved, or NULL.  With slot 26 every pair line is
    followed by one line of the lists of the grid's nrcmds: coverage, tail_share, gini, avg_pop, distinct, slots.
-   The slot needs the evaluation in HBM and lists of at most 128: ADMM, several GPUs, SLIM_GPU_RESIDENT=0 or
-   SLIM_GPU_EVAL_RESIDENT=0, merged duplicates, nrcmds > 128 or sampled negatives (slot 23) are SLIM_ERROR_INPUT
-   before the first solve, with a text that says which.  SLIM_OPTION_GPU_EVALSTRIDE and a filter combine.  The
-   choice of the best pairs is unchanged */
+   The slot needs the evaluation in HBM (slim_gpu_grid.h lists what that takes) and lists of at most 128: without
+   it, with nrcmds > 128 or with sampled negatives (slot 23) the call is SLIM_ERROR_INPUT before the first solve,
+   with a text that says which.  SLIM_OPTION_GPU_EVALSTRIDE and a filter combine.  The choice of the best pairs is
+   unchanged */
 int32_t Py_SLIM_MselectExposure(slim_t *trnhandle, slim_t *tsthandle, int32_t *ioptions, double *doptions,
                                 double *arrayl1, double *arrayl2, int32_t nl1, int32_t nl2, double *bestl1HR,
                                 double *bestl2HR, double *bestHRHR, double *bestARHR, double *bestl1AR,

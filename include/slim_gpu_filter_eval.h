@@ -42,10 +42,9 @@ int32_t SLIMGPU_ModelEvaluateRankedFiltered(slimgpu_evalset_t *es, const slimgpu
 /* Py_SLIM_Mselect with every pair evaluated under a filter (NULL: Py_SLIM_Mselect itself).  At nrcmds <= 128 the
    eval set serves, above it the ranked eval set; SLIM_OPTION_GPU_EVALSTRIDE combines (exclusion rows by user
    id).  The header prints one more line: the items allowed out of ncols and the number of exclusion entries.
-   A filtered grid needs the evaluation in HBM: ADMM, several GPUs, SLIM_GPU_RESIDENT=0, SLIM_GPU_EVAL_RESIDENT=0,
-   a matrix with merged duplicates or a filter whose ncols is not the resident models' width is
-   SLIM_ERROR_INPUT before the first solve, with a SLIMGPU_LastError text that says which -- never an
-   evaluation on the raw catalogue. */
+   A filtered grid needs the evaluation in HBM and a filter as wide as the resident models (slim_gpu_grid.h lists
+   what that takes): anything else is SLIM_ERROR_INPUT before the first solve, with a SLIMGPU_LastError text that
+   says which -- never an evaluation on the raw catalogue. */
 int32_t Py_SLIM_MselectFiltered(slim_t *trnhandle, slim_t *tsthandle, int32_t *ioptions, double *doptions,
                                 double *arrayl1, double *arrayl2, int32_t nl1, int32_t nl2, double *bestl1HR,
                                 double *bestl2HR, double *bestHRHR, double *bestARHR, double *bestl1AR,

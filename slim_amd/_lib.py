@@ -316,6 +316,27 @@ _EXPOSURE_SIGNATURES = {
 EXPOSURE_SYMBOLS = tuple(_EXPOSURE_SIGNATURES)
 EXPOSURE_CELL = 8       # SLIMGPU_EXPOSURE_CELL: l1, l2, HR, ARHR, coverage, tail_share, gini, avg_pop
 
+
+
+class GridCell(C.Structure):
+    """slimgpu_grid_cell_t (include/slim_gpu_grid.h): what one solved pair of a grid gives."""
+    _fields_ = [("l1r", C.c_double), ("l2r", C.c_double), ("nnz", C.c_int64), ("metrics", C.c_double * 4),
+                ("nvalid", C.c_int32 * 3), ("has_exposure", C.c_int32), ("exposure", Exposure),
+                ("solve_seconds", C.c_double)]
+
+
+# the model-selection grid's evaluator (include/slim_gpu_grid.h): what Py_SLIM_Mselect* and slim_mselect loop over
+_GRID_SIGNATURES = {
+    "SLIMGPU_GridOpen": (C.c_int32, [C.c_void_p, C.c_void_p, i32_1d, f64_1d, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.POINTER(C.c_void_p)]),
+    "SLIMGPU_GridDescribe": (None, [C.c_void_p]),
+    "SLIMGPU_GridSolve": (C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.POINTER(GridCell)]),
+    "SLIMGPU_GridModel": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "SLIMGPU_GridFree": (None, [C.POINTER(C.c_void_p)]),
+}
+
+GRID_SYMBOLS = tuple(_GRID_SIGNATURES)
+
 _lib = None
 
 
@@ -335,7 +356,7 @@ def load():
                               list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
                               list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items()) +
                               list(_WSAMPLE_SIGNATURES.items()) + list(_EXPLAIN_SIGNATURES.items()) +
-                              list(_EXPOSURE_SIGNATURES.items())):
+                              list(_EXPOSURE_SIGNATURES.items()) + list(_GRID_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

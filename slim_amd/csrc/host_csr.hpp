@@ -138,6 +138,11 @@ struct EvalResult {
   float hr = 0, hr_head = 0, hr_tail = 0, arhr = 0;
   int32_t nvalid = 0, nvalid_head = 0, nvalid_tail = 0;
 };
+// the four figures and the three counts as the C ABI hands them out: metrics[4], nvalid[3]
+inline void figures_out(const EvalResult& e, double* metrics, int32_t* nvalid) {
+  metrics[0] = e.hr; metrics[1] = e.hr_head; metrics[2] = e.hr_tail; metrics[3] = e.arhr;
+  nvalid[0] = e.nvalid; nvalid[1] = e.nvalid_head; nvalid[2] = e.nvalid_tail;
+}
 // pyapi.c:309-366: HR/ARHR of `model` for users with a non-empty test row.
 // lists/counts (optional): top-N ids [nusers][nrcmds] and list lengths computed elsewhere
 // (the GPU scorer); when null the host scorer is used.

@@ -13,11 +13,10 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "grid_eval.hpp"
 #include "host_csr.hpp"
 
 using namespace slimamd;
-
-static int predict_policy();  // SLIM_PREDICT (below)
 
 namespace {
 
@@ -63,6 +62,18 @@ slim_csr_t* learn_from_host(int32_t nrows, const ssize_t* rowptr, const int32_t*
 }
 
 }  // namespace
+
+// Where Py_SLIM_Predict scores: SLIM_PREDICT=gpu|cpu|auto (default auto: the GPU scorer when
+// a device is present and nrcmds <= SLIMGPU_MAX_LIST -- the chunk or the wave kernel up to 128, the
+// long-list form of the chunk kernel beyond -- else the host scorer; all give identical lists).
+// A refusal of the device (above 128: model rows that do not ascend, a split table beyond 2 GB) falls
+// back to the host scorer under auto and is the call's status under gpu.
+int slimamd::predict_policy() {
+  const char* e = std::getenv("SLIM_PREDICT");
+  if (e && std::strcmp(e, "cpu") == 0) return 0;
+  if (e && std::strcmp(e, "gpu") == 0) return 2;
+  return 1;
+}
 
 extern "C" {
 
@@ -176,17 +187,8 @@ int32_t Py_SLIM_Learn(slim_t* trnhandle, int32_t* ioptions, double* doptions,
   return SLIM_OK;
 }
 
-static const char kEvalNegsNeeds[] =
-    "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGS needs the candidate evaluation in HBM (cd on one GPU, no filter, "
-    "nrcmds <= 128, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs): ";
-
-static const char kEvalExposureNeeds[] =
-    "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALEXPOSURE needs the evaluation in HBM and lists of at most 128 (cd on one "
-    "GPU, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs, no sampled "
-    "negatives): ";
-
-// Py_SLIM_Mselect is this with no filter.  With one (slim_gpu_filter.h) every pair is evaluated under it, which
-// only the evaluation in HBM can do: where that is not to be had the call fails before the first solve.
+// Py_SLIM_Mselect is this with no filter.  How the grid's pairs are learnt and evaluated, what each mode needs and what
+// is refused before the first solve is grid_eval.cpp's business; this is the loop over arrayl1 x arrayl2.
 // force_exposure / cells: Py_SLIM_MselectExposure (slim_gpu_exposure.h), slot 26 on whatever ioptions says.
 static int32_t mselect_impl(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
                             double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
@@ -197,347 +199,68 @@ static int32_t mselect_impl(slim_t* trnhandle, slim_t* tsthandle, int32_t* iopti
   const slim_csr_t* tst = as_csr(tsthandle);
   if (!trn || !tst || !trn->rowptr || !tst->rowptr) return SLIM_ERROR_INPUT;
   set_error("");
-  LearnOptions base = decode_options(ioptions, doptions);
-  const int32_t nrcmds =
-      (!ioptions || ioptions[SLIM_OPTION_NRCMDS] == -1) ? 10 : ioptions[SLIM_OPTION_NRCMDS];
-  if (base.algo != SLIM_ALGO_CD && base.algo != SLIM_ALGO_ADMM) {
-    set_error("Py_SLIM_Mselect: unknown algorithm");
-    return SLIM_ERROR_INPUT;
-  }
-  const bool admm = base.algo == SLIM_ALGO_ADMM;
-  // evaluate every stride-th user only (slot 22; -1 or 1: every user)
-  const int32_t stride = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALSTRIDE] == -1) ? 1 : ioptions[SLIM_OPTION_GPU_EVALSTRIDE];
-  if (stride < 1) {
-    set_error("Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALSTRIDE must be at least 1");
-    return SLIM_ERROR_INPUT;
-  }
-
-  // R goes to HBM once for the whole grid (the reference re-runs
-  // CreateTrainingMatrix inside every SLIM_Learn call, pyapi.c:295-297)
-  int32_t status = SLIM_ERROR;
-  if (ioptions == nullptr || ioptions[SLIM_OPTION_GPU_NGPUS] == -1)
-    if (const char* e = std::getenv("SLIM_GPU_NGPUS")) base.ngpus = std::max(1, std::atoi(e));
-  // Sampled negatives (slots 23 / 24, slim_gpu_cand.h): the candidate set is drawn once, on the device, from the
-  // eval set's users, and every pair is evaluated on it.  Whatever stands in the way is refused here, before the
-  // first solve: there is no silent fall-back to the full-catalogue figures.
-  const int32_t evalnegs = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALNEGS] == -1) ? 0 : ioptions[SLIM_OPTION_GPU_EVALNEGS];
-  const uint64_t evalseed = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALSEED] == -1)
-                                ? 1 : (uint64_t)(uint32_t)ioptions[SLIM_OPTION_GPU_EVALSEED];
-  // slot 25: the negatives are drawn in proportion to item popularity (the weighted rule of slim_gpu_sample.h)
-  const int32_t evalnegpop = (!ioptions || ioptions[SLIM_OPTION_GPU_EVALNEGPOP] == -1) ? 0 : ioptions[SLIM_OPTION_GPU_EVALNEGPOP];
-  if (evalnegpop != 0 && (evalnegpop != 1 || evalnegs <= 0)) {
-    set_error(evalnegpop != 1
-                  ? "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGPOP must be 0 or 1, not " + std::to_string(evalnegpop)
-                  : "Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALNEGPOP weights the sampled negatives and "
-                    "SLIM_OPTION_GPU_EVALNEGS is off: there is nothing to weight");
-    return SLIM_ERROR_INPUT;
-  }
-  if (evalnegs != 0) {
-    const char* res0 = std::getenv("SLIM_GPU_RESIDENT");
-    const char* evr0 = std::getenv("SLIM_GPU_EVAL_RESIDENT");
-    std::string why;
-    if (evalnegs < 0) why = "SLIM_OPTION_GPU_EVALNEGS must be at least 0, not " + std::to_string(evalnegs);
-    else if (filter) why = "a candidate filter is given: candidate rows take no filter";
-    else if (admm) why = "the ADMM solver leaves no model in HBM";
-    else if (base.ngpus > 1) why = "the grid runs on several GPUs";
-    else if (res0 && std::atoi(res0) == 0) why = "SLIM_GPU_RESIDENT=0 keeps the models on the host";
-    else if (evr0 && std::atoi(evr0) == 0) why = "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host";
-    else if (nrcmds < 1 || nrcmds > 128)
-      why = "nrcmds is " + std::to_string(nrcmds) + ": the candidate lists use the eval set's cutoffs, 1 to 128";
-    if (!why.empty()) {
-      set_error(std::string(kEvalNegsNeeds) + why);
-      return SLIM_ERROR_INPUT;
-    }
-  }
-  // Exposure (slot 26, slim_gpu_exposure.h): every pair's lists are counted where the evaluation makes them.  What
-  // stands in the way is refused here, or below once the eval set is known: before the first solve.
-  const int32_t evalexpo = force_exposure ? 1
-                           : (!ioptions || ioptions[SLIM_OPTION_GPU_EVALEXPOSURE] == -1) ? 0
-                                                                                         : ioptions[SLIM_OPTION_GPU_EVALEXPOSURE];
-  if (evalexpo != 0) {
-    const char* res0 = std::getenv("SLIM_GPU_RESIDENT");
-    const char* evr0 = std::getenv("SLIM_GPU_EVAL_RESIDENT");
-    std::string why;
-    if (evalexpo != 1) why = "SLIM_OPTION_GPU_EVALEXPOSURE must be 0 or 1, not " + std::to_string(evalexpo);
-    else if (admm) why = "the ADMM solver leaves no model in HBM";
-    else if (base.ngpus > 1) why = "the grid runs on several GPUs";
-    else if (res0 && std::atoi(res0) == 0) why = "SLIM_GPU_RESIDENT=0 keeps the models on the host";
-    else if (evr0 && std::atoi(evr0) == 0) why = "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host";
-    else if (nrcmds < 1 || nrcmds > 128)
-      why = "nrcmds is " + std::to_string(nrcmds) + ": the lists behind the evaluation have 1 to 128 places";
-    else if (evalnegs > 0)
-      why = "SLIM_OPTION_GPU_EVALNEGS is on: the exposure of sampled candidate lists is not built";
-    if (!why.empty()) {
-      set_error(std::string(kEvalExposureNeeds) + why);
-      return SLIM_ERROR_INPUT;
-    }
-  }
-  slimgpu_matrix_t* mat =
-      admm ? nullptr : multi_from_host(trn->nrows, trn->rowptr, trn->rowind, trn->rowval, base, &status);
-  if (!mat && !admm) return status;
-  // a grid of nl1 x nl2 solves over one R: the engine may pay for G = R^T R once (cd_gram.hpp)
-  if (mat) matrix_expect_solves(mat, nl1 * nl2);
-
-  const int32_t trn_ncols = max_index_plus_one(trn->rowptr[trn->nrows], trn->rowind);
-  const int32_t tst_ncols = max_index_plus_one(tst->rowptr[tst->nrows], tst->rowind);
-  const int32_t ncols = trn_ncols > tst_ncols ? trn_ncols : tst_ncols;  // pyapi.c:255-257
-  int32_t* fmarker = head_tail_split(trn->nrows, ncols, trn->rowptr, trn->rowind);
-
-  // One GPU, CD: the models of the grid stay in HBM (engine.hpp: learn_resident) -- each pair is
-  // warm-started from the previous one without an upload and scored where it lies; only its nnz is
-  // printed, so nothing of it ever crosses PCIe.  SLIM_GPU_RESIDENT=0: host models as before.
-  // Above 128 the evaluation does not need the lists: the ranks of the held-out items (slim_gpu_rank.h) give the
-  // figures at any length.  Such a grid runs resident when the ranked eval set can be made, and on host models
-  // when it cannot -- their lists of up to SLIMGPU_MAX_LIST come from the long-list scorer (slim_gpu_lists.h).
-  const char* res_env = std::getenv("SLIM_GPU_RESIDENT");
-  const bool may_reside = !admm && mat && matrix_replicas(mat).empty() && nrcmds >= 1 &&
-                          !(res_env && std::atoi(res_env) == 0);
-  bool resident = may_reside && nrcmds <= 128;
-  bool ranked = false;
-  // ... and evaluated where they lie: the test rows and the marker go to HBM once (evalset_create), a
-  // pair brings down its four sums and three counts.  SLIM_GPU_EVAL_RESIDENT=0, or a refusal (a matrix
-  // whose repeated pairs were merged), keeps the lists-through-the-host path below -- which has no
-  // subset form: a stride needs the eval set, and the call fails here, before the first solve, without it.
-  const char* evr_env = std::getenv("SLIM_GPU_EVAL_RESIDENT");
-  slimgpu_evalset_t* evalset = nullptr;
-  const int32_t nall = std::min(trn->nrows, tst->nrows);
-  std::vector<int32_t> sel;
-  if (stride > 1)
-    for (int64_t u = 0; u < nall; u += stride) sel.push_back((int32_t)u);
-  if (resident && !(evr_env && std::atoi(evr_env) == 0)) {
-    evalset = evalset_create(mat, tst, fmarker, ncols, 1, &nrcmds, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
-                             &status);
-    if (!evalset && stride == 1 && !filter && !evalexpo) set_error("");
-  } else if (may_reside && nrcmds > 128 && !(evr_env && std::atoi(evr_env) == 0)) {
-    evalset = evalset_create_ranked(mat, tst, fmarker, ncols, (int32_t)sel.size(), sel.empty() ? nullptr : sel.data(),
-                                    &status);
-    ranked = resident = evalset != nullptr;
-    if (!evalset && stride == 1 && !filter && !evalexpo) set_error("");
-  }
-  if (stride > 1 && !evalset) {
-    const std::string why = SLIMGPU_LastError();
-    set_error("Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALSTRIDE needs the evaluation in HBM (cd on one GPU, "
-              "nrcmds >= 1, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without "
-              "merged pairs; above 128 a model the chunk scorer serves)" +
-              (nrcmds < 1 ? ": nrcmds is " + std::to_string(nrcmds) : std::string()) +
-              (why.empty() ? std::string() : ": " + why));
-    std::free(fmarker);
-    matrix_free(mat);
-    return SLIM_ERROR_INPUT;
-  }
-  if (evalexpo && (!evalset || ranked)) {  // (a matrix with merged duplicates, replicas on other GPUs, ...)
-    std::string why = mat && !matrix_replicas(mat).empty() ? "the grid runs on several GPUs" : SLIMGPU_LastError();
-    if (why.empty()) why = "the eval set could not be made";
-    set_error(std::string(kEvalExposureNeeds) + why);
-    evalset_free(evalset);
-    std::free(fmarker);
-    matrix_free(mat);
-    return SLIM_ERROR_INPUT;
-  }
-  const HostFilter hflt = filter_host(filter);
-  if (filter) {  // (no silent evaluation on the raw catalogue)
-    const bool several = base.ngpus > 1 || (mat && !matrix_replicas(mat).empty());
-    int32_t mrows = 0, mcols = 0;
-    int64_t mnnz = 0;
-    if (mat) matrix_info(mat, &mrows, &mcols, &mnnz);
-    std::string why;
-    if (admm) why = "the ADMM solver leaves no model in HBM";
-    else if (several) why = "the grid runs on several GPUs";
-    else if (res_env && std::atoi(res_env) == 0) why = "SLIM_GPU_RESIDENT=0 keeps the models on the host";
-    else if (evr_env && std::atoi(evr_env) == 0) why = "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host";
-    else if (nrcmds < 1) why = "nrcmds is " + std::to_string(nrcmds);
-    else if (!evalset) {  // (a matrix with merged duplicates, ...)
-      why = SLIMGPU_LastError();
-      if (why.empty()) why = "the eval set could not be made";
-    }
-    else if (hflt.ncols != mcols)
-      why = "the filter was made for " + std::to_string(hflt.ncols) + " items, the resident models have " +
-            std::to_string(mcols);
-    if (!why.empty()) {
-      set_error("Py_SLIM_MselectFiltered: a filter needs the evaluation in HBM (cd on one GPU, SLIM_GPU_RESIDENT "
-                "and SLIM_GPU_EVAL_RESIDENT not 0, a matrix staged without merged pairs, a filter of the "
-                "models' width): " + why);
-      evalset_free(evalset);
-      std::free(fmarker);
-      matrix_free(mat);
-      return SLIM_ERROR_INPUT;
-    }
-  }
-
-  slimgpu_candset_t* cands = nullptr;
-  if (evalnegs > 0) {
-    std::string why;
-    if (!evalset || ranked) {  // (a matrix with merged duplicates, ...)
-      why = SLIMGPU_LastError();
-      if (why.empty()) why = "the eval set could not be made";
-    } else {
-      cands = evalnegpop ? evalset_sample_candidates_weighted(evalset, evalnegs, evalseed, nullptr, &status)
-                         : evalset_sample_candidates(evalset, evalnegs, evalseed, &status);
-      if (!cands) why = SLIMGPU_LastError();
-    }
-    if (!cands) {
-      set_error(std::string(kEvalNegsNeeds) + why);
-      evalset_free(evalset);
-      std::free(fmarker);
-      matrix_free(mat);
-      return SLIM_ERROR_INPUT;
-    }
-  }
+  std::vector<int32_t> io(SLIM_NOPTIONS, -1);  // (a private copy: the caller's slot 26 stays as it is)
+  if (ioptions) io.assign(ioptions, ioptions + SLIM_NOPTIONS);
+  if (force_exposure) io[SLIM_OPTION_GPU_EVALEXPOSURE] = 1;
+  slimgpu_grid grid(trn, tst, filter);
+  int32_t rc = grid.open(io.data(), doptions, 0, nl1 * nl2);
+  if (rc != SLIM_OK) return rc;
 
   std::printf("------------------------------------------------------------------\n");
   std::printf("SLIM, version %s (MI355X engine)\n", SLIM_VERSION);
   std::printf("------------------------------------------------------------------\n");
-  std::printf("  trn matrix, nrows: %d, ncols: %d, nnz: %zd\n", trn->nrows, ncols,
+  std::printf("  trn matrix, nrows: %d, ncols: %d, nnz: %zd\n", trn->nrows, grid.ncols,
               trn->rowptr[trn->nrows]);
-  std::printf("  tst matrix, nrows: %d, ncols: %d, nnz: %zd\n", tst->nrows, tst_ncols,
-              tst->rowptr[tst->nrows]);
-  std::printf("  optTol: %.2le, niters: %d\n", base.optTol, base.maxniters);
-  if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
-  if (filter) {
-    int64_t allowed = hflt.ncols;
-    if (hflt.bits) {
-      allowed = 0;
-      for (int32_t k = 0; k < hflt.ncols; ++k) allowed += (hflt.bits[k >> 5] >> (k & 31)) & 1u;
-    }
-    std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)allowed, hflt.ncols,
-                (long long)(hflt.xptr ? hflt.xptr[hflt.xusers] : 0));
-  }
-  if (cands) {
-    int64_t entries = 0;
-    candset_info(cands, nullptr, nullptr, &entries);
-    std::printf("  sampled negatives: nnegs %d, seed %llu, %s%lld candidate entries\n", evalnegs,
-                (unsigned long long)evalseed, evalnegpop ? "popularity, " : "", (long long)entries);
-  }
+  std::printf("  tst matrix, nrows: %d, ncols: %d, nnz: %zd\n", tst->nrows,
+              max_index_plus_one(tst->rowptr[tst->nrows], tst->rowind), tst->rowptr[tst->nrows]);
+  std::printf("  optTol: %.2le, niters: %d\n", grid.base.optTol, grid.base.maxniters);
+  grid.describe();
   std::printf("\nEstimating & evaluating models...\n\n");
 
   *bestHRHR = *bestARHR = *bestHRAR = *bestARAR = 0.0;
-  slim_csr_t* model = nullptr;
-  slimgpu_model* dmodel = nullptr;
-  int32_t rc = SLIM_OK;
   for (int32_t a = 0; a < nl1 && rc == SLIM_OK; ++a) {
     for (int32_t b = 0; b < nl2; ++b) {
       doptions[SLIM_OPTION_L1R] = arrayl1[a];  // the reference writes these through
       doptions[SLIM_OPTION_L2R] = arrayl2[b];  // to the caller's array (pyapi.c:288-289)
-      LearnOptions opt = base;
-      opt.l1r = arrayl1[a];
-      opt.l2r = arrayl2[b];
-      slim_csr_t* prev = model;  // warm start from the previous cell
-      // top-N of every user on the GPU (bit-identical to the host scorer), hits on the host
-      std::vector<int32_t> lists, lens;
-      std::vector<float> lsc;
-      auto host_lists = [&] {  // (not needed while the eval set serves)
-        lists.assign((size_t)trn->nrows * nrcmds, -1);
-        lens.assign((size_t)trn->nrows, 0);
-        lsc.assign((size_t)trn->nrows * nrcmds, 0.0f);
-      };
-      bool on_gpu = false, evaluated = false;
-      EvalResult ev;
-      slimgpu_exposure_t expo = {};
-      ssize_t model_nnz_now = 0;
-      if (resident) {
-        slimgpu_model* dprev = dmodel;
-        dmodel = learn_resident(mat, opt, dprev, &status);
-        model_free(dprev);
-        if (!dmodel) {
-          rc = status;
-          break;
-        }
-        model_nnz_now = (ssize_t)model_nnz(dmodel);
-        evaluated = evalset && (cands      ? model_evaluate_candidates(evalset, dmodel, cands, 1, &ev)
-                                : ranked   ? model_evaluate_ranked(evalset, dmodel, 1, &nrcmds, &ev, filter)
-                                : evalexpo ? model_evaluate_exposure(evalset, dmodel, filter, 1, &ev, nullptr, &expo)
-                                           : model_evaluate(evalset, dmodel, 1, &ev, filter)) == SLIM_OK;
-        // (no silent evaluation of everybody, without the filter, on the whole catalogue, or without the exposure)
-        if (!evaluated && (stride > 1 || filter || cands || evalexpo)) {
-          rc = SLIM_ERROR;
-          break;
-        }
-        DeviceRowView wv;
-        if (!evaluated) {
-          host_lists();
-          on_gpu = model_row_view(dmodel, &wv) == SLIM_OK &&
-                   predict_device_view(wv, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK;
-        }
-        if (!evaluated && !on_gpu) {  // (the scorer refused: the host loop needs the host model)
-          model = model_fetch(dmodel, &status);
-          if (!model) {
-            rc = status;
-            break;
-          }
-        }
-      } else {
-      // (ADMM ignores the previous model, estimate.c:38)
-      model = admm ? learn_admm(trn->nrows, trn->rowptr, trn->rowind, trn->rowval, opt, &status)
-                   : multi_learn(mat, opt, prev, &status);
-      csr_free(prev);
-      if (!model) {
-        rc = status;
-        break;
-      }
-      model_nnz_now = model->rowptr[model->nrows];
-      host_lists();
-      on_gpu = nrcmds <= 128 ? predict_device(model, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK
-                             : nrcmds <= SLIMGPU_MAX_LIST && predict_policy() != 0 &&
-                                   predict_lists(model, trn, nrcmds, lists.data(), lsc.data(), lens.data()) == SLIM_OK;
-      }
-      if (evaluated) {
-        // the figures came from the device: no lists, no host loop
-      } else if (!on_gpu) {
-        ev = evaluate(model, trn, tst, nrcmds, fmarker, ncols);
-      } else if (evaluate_device(std::min(trn->nrows, tst->nrows), nrcmds, lists.data(), lens.data(),
-                               tst, fmarker, ncols, &ev) != SLIM_OK) {  // hit counting on the GPU
-        if (resident && !model) model = model_fetch(dmodel, &status);  // (the host loop sizes by the model)
-        if (!model) {
-          rc = status;
-          break;
-        }
-        ev = evaluate(model, trn, tst, nrcmds, fmarker, ncols, lists.data(), lens.data());
-      }
+      slimgpu_grid_cell_t c;
+      rc = grid.solve(arrayl1[a], arrayl2[b], &c);
+      if (rc != SLIM_OK) break;
+      const double hr = c.metrics[0], arhr = c.metrics[3];
       std::printf("l1r: %.2le l2r: %.2le nnz: %7zd hr: %.4f hr_head: %.4f hr_tail: %.4f "
                   "arhr: %.4f time: %.2lf\n",
-                  opt.l1r, opt.l2r, model_nnz_now, ev.hr, ev.hr_head, ev.hr_tail,
-                  ev.arhr, last_stats().total_ms / 1e3);
-      if (evalexpo) {  // (the lists of the grid's nrcmds, counted where the evaluation made them)
+                  c.l1r, c.l2r, (ssize_t)c.nnz, hr, c.metrics[1], c.metrics[2], arhr, c.solve_seconds);
+      if (c.has_exposure) {  // (the lists of the grid's nrcmds, counted where the evaluation made them)
+        const slimgpu_exposure_t& expo = c.exposure;
         std::printf("  exposure@%d: coverage: %.4f tail_share: %.4f gini: %.4f avg_pop: %.2f distinct: %d slots: %lld\n",
-                    nrcmds, expo.coverage, expo.tail_share, expo.gini, expo.avg_pop, expo.distinct,
+                    grid.nrcmds, expo.coverage, expo.tail_share, expo.gini, expo.avg_pop, expo.distinct,
                     (long long)expo.slots);
         if (cells) {
-          double* c = cells + (size_t)SLIMGPU_EXPOSURE_CELL * ((size_t)a * (size_t)nl2 + (size_t)b);
-          c[0] = opt.l1r; c[1] = opt.l2r; c[2] = ev.hr; c[3] = ev.arhr;
-          c[4] = expo.coverage; c[5] = expo.tail_share; c[6] = expo.gini; c[7] = expo.avg_pop;
+          double* out = cells + (size_t)SLIMGPU_EXPOSURE_CELL * ((size_t)a * (size_t)nl2 + (size_t)b);
+          out[0] = c.l1r; out[1] = c.l2r; out[2] = hr; out[3] = arhr;
+          out[4] = expo.coverage; out[5] = expo.tail_share; out[6] = expo.gini; out[7] = expo.avg_pop;
         }
       }
-      if (resident && model) {  // (a fetched copy served the host scorer only)
-        csr_free(model);
-        model = nullptr;
-      }
-      if (ev.nvalid < 1) {  // pyapi.c:377-381
-        *bestl1HR = opt.l1r;
-        *bestl2HR = opt.l2r;
+      if (c.nvalid[0] < 1) {  // pyapi.c:377-381
+        *bestl1HR = c.l1r;
+        *bestl2HR = c.l2r;
         rc = SLIM_ERROR;
         break;
       }
-      if (ev.hr > *bestHRHR) {
-        *bestHRHR = ev.hr;
-        *bestARHR = ev.arhr;
-        *bestl1HR = opt.l1r;
-        *bestl2HR = opt.l2r;
+      if (hr > *bestHRHR) {
+        *bestHRHR = hr;
+        *bestARHR = arhr;
+        *bestl1HR = c.l1r;
+        *bestl2HR = c.l2r;
       }
-      if (ev.arhr > *bestARAR) {
-        *bestHRAR = ev.hr;
-        *bestARAR = ev.arhr;
-        *bestl1AR = opt.l1r;
-        *bestl2AR = opt.l2r;
+      if (arhr > *bestARAR) {
+        *bestHRAR = hr;
+        *bestARAR = arhr;
+        *bestl1AR = c.l1r;
+        *bestl2AR = c.l2r;
       }
     }
   }
   std::printf("\nDone.\n------------------------------------------------------------------\n");
-  csr_free(model);
-  model_free(dmodel);
-  candset_free(cands);
-  evalset_free(evalset);
-  std::free(fmarker);
-  matrix_free(mat);
   return rc;
 }
 
@@ -579,18 +302,6 @@ int32_t Py_SLIM_GetTopN_1vsk(slim_t* model, int32_t nratings, int32_t* itemids, 
   const slim_csr_t* W = as_csr(model);
   if (!W || !W->rowptr || nrcmds < 0 || nnegs < 0) return SLIM_ERROR;
   return top_n_1vsk(W, nratings, itemids, ratings, nrcmds, rids, rscores, nnegs, negitems);
-}
-
-// Where Py_SLIM_Predict scores: SLIM_PREDICT=gpu|cpu|auto (default auto: the GPU scorer when
-// a device is present and nrcmds <= SLIMGPU_MAX_LIST -- the chunk or the wave kernel up to 128, the
-// long-list form of the chunk kernel beyond -- else the host scorer; all give identical lists).
-// A refusal of the device (above 128: model rows that do not ascend, a split table beyond 2 GB) falls
-// back to the host scorer under auto and is the call's status under gpu.
-static int predict_policy() {
-  const char* e = std::getenv("SLIM_PREDICT");
-  if (e && std::strcmp(e, "cpu") == 0) return 0;
-  if (e && std::strcmp(e, "gpu") == 0) return 2;
-  return 1;
 }
 
 int32_t SLIMGPU_Predict(int32_t nrcmds, slim_t* slimhandle, slim_t* trnhandle, int32_t* output,
@@ -836,12 +547,7 @@ int32_t SLIMGPU_ModelEvaluateAtFiltered(slimgpu_evalset_t* es, const slimgpu_mod
   }
   const int32_t rc = model_evaluate(es, model, ncutoffs, ev, filter);
   if (rc != SLIM_OK) return rc;
-  for (int32_t k = 0; k < ncutoffs; ++k) {
-    double* m = metrics + 4 * k;
-    int32_t* n = nvalid + 3 * k;
-    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
-    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
-  }
+  for (int32_t k = 0; k < ncutoffs; ++k) figures_out(ev[k], metrics + 4 * k, nvalid + 3 * k);
   return SLIM_OK;
 }
 
@@ -854,9 +560,7 @@ int32_t SLIMGPU_ModelEvaluate(slimgpu_evalset_t* es, const slimgpu_model_t* mode
   const int32_t ncut = std::max(1, evalset_cutoffs(es));
   const int32_t rc = model_evaluate(es, model, ncut, ev);
   if (rc != SLIM_OK) return rc;
-  const EvalResult& e = ev[ncut - 1];
-  metrics[0] = e.hr; metrics[1] = e.hr_head; metrics[2] = e.hr_tail; metrics[3] = e.arhr;
-  nvalid[0] = e.nvalid; nvalid[1] = e.nvalid_head; nvalid[2] = e.nvalid_tail;
+  figures_out(ev[ncut - 1], metrics, nvalid);
   return SLIM_OK;
 }
 
@@ -898,12 +602,7 @@ int32_t SLIMGPU_ModelEvaluateRankedFiltered(slimgpu_evalset_t* es, const slimgpu
   EvalResult ev[SLIMGPU_MAX_RANK_CUTOFFS];
   const int32_t rc = model_evaluate_ranked(es, model, ncutoffs, cutoffs, ev, filter);
   if (rc != SLIM_OK) return rc;
-  for (int32_t k = 0; k < ncutoffs; ++k) {
-    double* m = metrics + 4 * k;
-    int32_t* n = nvalid + 3 * k;
-    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
-    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
-  }
+  for (int32_t k = 0; k < ncutoffs; ++k) figures_out(ev[k], metrics + 4 * k, nvalid + 3 * k);
   return SLIM_OK;
 }
 
@@ -1061,12 +760,7 @@ int32_t SLIMGPU_ModelEvaluateCandidates(slimgpu_evalset_t* es, const slimgpu_mod
   }
   const int32_t rc = model_evaluate_candidates(es, model, cs, ncutoffs, ev);
   if (rc != SLIM_OK) return rc;
-  for (int32_t k = 0; k < ncutoffs; ++k) {
-    double* m = metrics + 4 * k;
-    int32_t* n = nvalid + 3 * k;
-    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
-    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
-  }
+  for (int32_t k = 0; k < ncutoffs; ++k) figures_out(ev[k], metrics + 4 * k, nvalid + 3 * k);
   return SLIM_OK;
 }
 
@@ -1192,12 +886,7 @@ int32_t SLIMGPU_ModelEvaluateExposure(slimgpu_evalset_t* es, const slimgpu_model
   }
   const int32_t rc = model_evaluate_exposure(es, model, filter, ncutoffs, ev, exposure, summary);
   if (rc != SLIM_OK) return rc;
-  for (int32_t k = 0; k < ncutoffs; ++k) {
-    double* m = metrics + 4 * k;
-    int32_t* n = nvalid + 3 * k;
-    m[0] = ev[k].hr; m[1] = ev[k].hr_head; m[2] = ev[k].hr_tail; m[3] = ev[k].arhr;
-    n[0] = ev[k].nvalid; n[1] = ev[k].nvalid_head; n[2] = ev[k].nvalid_tail;
-  }
+  for (int32_t k = 0; k < ncutoffs; ++k) figures_out(ev[k], metrics + 4 * k, nvalid + 3 * k);
   return SLIM_OK;
 }
 
@@ -1362,8 +1051,7 @@ int32_t SLIMGPU_Evaluate(int32_t nusers, int32_t nrcmds, const int32_t* lists,
   const int32_t rc =
       evaluate_device(nusers, nrcmds, lists, counts, as_csr(tsthandle), fmarker, fm_ncols, &ev);
   if (rc != SLIM_OK) return rc;
-  metrics[0] = ev.hr; metrics[1] = ev.hr_head; metrics[2] = ev.hr_tail; metrics[3] = ev.arhr;
-  nvalid[0] = ev.nvalid; nvalid[1] = ev.nvalid_head; nvalid[2] = ev.nvalid_tail;
+  figures_out(ev, metrics, nvalid);
   return SLIM_OK;
 }
 
