@@ -12,6 +12,8 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <new>
 #include <string>
 #include <vector>
@@ -483,6 +485,16 @@ slimgpu_candset* sample_on_device(const char* name, slimgpu_evalset_t* es, int32
       }
       const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / (lds + 64)));
       const int groups = std::max(1, std::min<int>(nsel, V.num_cus * per_cu));
+      if (std::getenv("SLIM_GPU_TRACE")) {  // how many positions a workgroup serves one after the other
+        if (weighted)
+          std::fprintf(stderr, "[trace] k_sample_weighted: %d positions, %d workgroups, %zu bytes of LDS, %d items, "
+                               "nnegs %d, per %d\n",
+                       nsel, groups, lds, V.ncols, nnegs, (((V.ncols + 1023) >> 10) + 63) >> 6);
+        else
+          std::fprintf(stderr, "[trace] k_sample_negatives: %d positions, %d workgroups, %zu bytes of LDS, %d items, "
+                               "nnegs %d, %s\n",
+                       nsel, groups, lds, V.ncols, nnegs, dense ? "sort records" : "no sort records");
+      }
       bool timed = false;
       hipEvent_t ev0 = nullptr, ev1 = nullptr;  // (the weighted kernel's own time, for SLIMGPU_LastSampleKernelMs)
       if (weighted) {

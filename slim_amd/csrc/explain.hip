@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <new>
 #include <string>
@@ -102,6 +103,10 @@ int32_t explain_rows(const char* who, const DeviceRowView& W, HistoryView H, con
     if (nsel > 0 && entries > 0) {
       const dim3 grid((unsigned)std::min<int64_t>(nsel, (int64_t)num_cus * 8)), block(64 * kExplainWaves);
       const size_t lds = sizeof(int4) * (size_t)A.stage;
+      if (std::getenv("SLIM_GPU_TRACE"))
+        std::fprintf(stderr, "[trace] k_explain<%d>: %d positions, %d workgroups, %d staged entries, nwhy %d, %s\n",
+                     nwhy > 4 || form16_forced() ? 16 : 4, nsel, (int)grid.x, A.stage, nwhy,
+                     h_users ? "a user list" : "all users");
       if (nwhy > 4 || form16_forced())
         hipLaunchKernelGGL(k_explain<16>, grid, block, lds, stream, A);
       else

@@ -191,9 +191,23 @@ void (*pick_kernel(const ChunkPlan& P))(Args) {
                                 : chunk_kernel<Args, 8, unsigned long long>());
 }
 
+// the mode a kernel's arguments stand for, as SLIM_GPU_TRACE names it
+template <class Args>
+constexpr const char* scorer_mode() {
+  if constexpr (std::is_same_v<Args, TopN2Args>) return "chunk";
+  else if constexpr (std::is_same_v<Args, TopNEvalArgs>) return "eval";
+  else if constexpr (std::is_same_v<Args, TopNRankArgs>) return "rank";
+  else if constexpr (std::is_same_v<Args, TopNCandArgs>) return "cand";
+  else if constexpr (std::is_same_v<Args, TopNLongArgs>) return "long";
+  else return "wave";
+}
+
 // L.groups workgroups of `fn`; more than 64 KB of dynamic LDS are asked for first; a call's first launch is stamped
 template <class Args>
 void launch_scorer(void (*fn)(Args), ScorerLaunch& L, int threads, size_t lds, hipStream_t stream, const Args& A) {
+  if (std::getenv("SLIM_GPU_TRACE"))  // how many positions a workgroup serves one after the other
+    std::fprintf(stderr, "[trace] top-N scorer (%s): %d positions, %d workgroups of %d threads, %zu bytes of LDS\n",
+                 scorer_mode<Args>(), (int)A.nusers, L.groups, threads, lds);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));

@@ -60,11 +60,15 @@ class Case(object):
         if name == "wide":
             self.W = make_model(6000, 36, 44, True, seed=31)
             self.R = make_history(96, 6000, 0.05, (11,), True, seed=37)
+        elif name.startswith("crowd-"):     # tests/crowd_cases.py: few items, many users
+            ties = name == "crowd-ties"
+            self.W = make_model(400, 8, 12, ties, seed=41 if ties else 43)
+            self.R = make_history(2500, 400, 0.08, NO_HISTORY, ties, seed=47 if ties else 53)
         else:
             ties = name == "ties"
             self.W = make_model(1500, 8, 12, ties, seed=17 if ties else 7)
             self.R = make_history(300, 1500, 0.03, NO_HISTORY, ties, seed=23 if ties else 5)
-        self.binary = name != "floats"
+        self.binary = name not in ("floats", "crowd-floats")
         self.nusers, self.ncols = self.R.shape[0], self.W.shape[1]
         self.full = self.ncols
         self.hw = _scipy_to_model_handle(lib, self.W)
@@ -179,3 +183,45 @@ def cases_fixture():
 
 def same(got, want):
     return all(np.array_equal(g, w) for g, w in zip(got, want))
+
+
+# ---- figures and ranks from yardstick lists (tests/test_filtered_eval.py, tests/test_later_positions.py) -------------
+KEYS = ("hr", "hr_head", "hr_tail", "arhr")
+NKEYS = ("nvalid", "nvalid_head", "nvalid_tail")
+
+
+def figures(d):
+    return np.array([d[k] for k in KEYS]), np.array([d[k] for k in NKEYS], np.int32)
+
+
+def assert_same(got, want, what=""):
+    (mg, ng), (mw, nw) = got, want
+    print(what, "got ", mg.tolist(), ng.tolist())
+    print(what, "want", mw.tolist(), nw.tolist())
+    assert ng.tolist() == nw.tolist(), what
+    assert mg.dtype == mw.dtype == np.float64 and np.array_equal(mg, mw), what
+
+
+def evaluate_lists(lib, ids, n, T, fm):
+    """The existing SLIMGPU_Evaluate on the first n ranks of yardstick lists (one row per row of T)."""
+    n = min(n, ids.shape[1])
+    lists = np.ascontiguousarray(ids[:, :n])
+    cnt = (lists >= 0).sum(1).astype(np.int32)
+    ht = wrap(lib, T)
+    met, nv = np.zeros(4), np.zeros(3, np.int32)
+    assert lib.SLIMGPU_Evaluate(T.shape[0], n, lists.ravel(), cnt, ht, fm, fm.size, met, nv) == SLIM_OK, \
+        _lib.last_error()
+    lib.Py_csr_free(ht)
+    return met, nv
+
+
+def positions(ids, sc, T, users):
+    """(rank, score) of every test entry of `users` by looking it up in the rows of ids / sc (row q: users[q])."""
+    rank, score = [], []
+    for q, u in enumerate(users):
+        where = {int(i): r for r, i in enumerate(ids[q]) if i >= 0}
+        for z in range(T.indptr[u], T.indptr[u + 1]):
+            r = where.get(int(T.indices[z]))
+            rank.append(0 if r is None else r + 1)
+            score.append(0.0 if r is None else sc[q, r])
+    return np.array(rank, np.int32), np.array(score, np.float32)

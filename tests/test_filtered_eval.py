@@ -24,7 +24,7 @@ import scipy.sparse as sp
 
 import slim_oracle as O
 from conftest import ROOT
-from filtered_cases import P, cases_fixture, wrap
+from filtered_cases import KEYS, NKEYS, P, assert_same, cases_fixture, evaluate_lists, figures, positions, wrap
 from slim_amd import _lib
 from slim_amd.constants import SLIM_ERROR_INPUT, SLIM_OK
 from slim_amd.engine import DeviceMatrix, ItemFilter, eval_stats
@@ -33,46 +33,7 @@ pytestmark = pytest.mark.gpu
 cases = pytest.fixture(scope="module")(cases_fixture)
 NAMES = ["plain", "ties", "floats", "wide"]
 EVERY = pytest.mark.parametrize("name", NAMES)
-KEYS = ("hr", "hr_head", "hr_tail", "arhr")
-NKEYS = ("nvalid", "nvalid_head", "nvalid_tail")
 LONG_ROW_USER, WIDE_ID_USER, LONG_ROW = 4, 2, 150
-
-
-def figures(d):
-    return np.array([d[k] for k in KEYS]), np.array([d[k] for k in NKEYS], np.int32)
-
-
-def assert_same(got, want, what=""):
-    (mg, ng), (mw, nw) = got, want
-    print(what, "got ", mg.tolist(), ng.tolist())
-    print(what, "want", mw.tolist(), nw.tolist())
-    assert ng.tolist() == nw.tolist(), what
-    assert mg.dtype == mw.dtype == np.float64 and np.array_equal(mg, mw), what
-
-
-def evaluate_lists(lib, ids, n, T, fm):
-    """The existing SLIMGPU_Evaluate on the first n ranks of yardstick lists (one row per row of T)."""
-    n = min(n, ids.shape[1])
-    lists = np.ascontiguousarray(ids[:, :n])
-    cnt = (lists >= 0).sum(1).astype(np.int32)
-    ht = wrap(lib, T)
-    met, nv = np.zeros(4), np.zeros(3, np.int32)
-    assert lib.SLIMGPU_Evaluate(T.shape[0], n, lists.ravel(), cnt, ht, fm, fm.size, met, nv) == SLIM_OK, \
-        _lib.last_error()
-    lib.Py_csr_free(ht)
-    return met, nv
-
-
-def positions(ids, sc, T, users):
-    """(rank, score) of every test entry of `users` by looking it up in the rows of ids / sc (row q: users[q])."""
-    rank, score = [], []
-    for q, u in enumerate(users):
-        where = {int(i): r for r, i in enumerate(ids[q]) if i >= 0}
-        for z in range(T.indptr[u], T.indptr[u + 1]):
-            r = where.get(int(T.indices[z]))
-            rank.append(0 if r is None else r + 1)
-            score.append(0.0 if r is None else sc[q, r])
-    return np.array(rank, np.int32), np.array(score, np.float32)
 
 
 def make_test_rows(c, width):

@@ -1,6 +1,6 @@
 """Shared by tests/test_weighted_negatives*.py: THE WEIGHTED RULE of include/slim_gpu_sample.h restated in numpy FROM
-THE HEADER'S TEXT (never from the C++), with the 128-bit product in Python integers, the weight arrays of the tests,
-and the calls that make weighted sets.
+THE HEADER'S TEXT (never from the C++), with the 128-bit product in 32-bit halves (pinned to Python integers by
+tests/test_later_positions.py), the weight arrays of the tests, and the calls that make weighted sets.
 
 The yardstick is never the code under test: the rows are numpy's, and the expected figures are those of the EXISTING
 calls SLIMGPU_CandSetCreate + SLIMGPU_ModelEvaluateCandidates on numpy's rows.
@@ -57,9 +57,20 @@ def prefix(w):
     return np.concatenate([[0], np.cumsum(w.astype(U), dtype=U)]).astype(U)
 
 
-def mulhi64(keys, m):
+def mulhi64_python(keys, m):
     """The upper 64 bits of key * m, exact: Python integers."""
     return np.array([(int(k) * int(m)) >> 64 for k in np.atleast_1d(keys)], dtype=U)
+
+
+def mulhi64(keys, m):
+    """The upper 64 bits of key * m in numpy, by the schoolbook product of 32-bit halves: each of the four partial
+    products and each sum below stays under 2^64.  tests/test_later_positions.py pins it to mulhi64_python."""
+    k, m = np.atleast_1d(np.asarray(keys, U)), U(int(m))
+    lo32, s32 = U(0xFFFFFFFF), U(32)
+    k0, k1, m0, m1 = k & lo32, k >> s32, m & lo32, m >> s32
+    mid = k1 * m0 + ((k0 * m0) >> s32)                          # <= (2^32 - 1)^2 + 2^32 - 2
+    mid2 = k0 * m1 + (mid & lo32)
+    return k1 * m1 + (mid >> s32) + (mid2 >> s32)
 
 
 def weighted_negatives(seed, u, X, nnegs, w, Cw=None):
