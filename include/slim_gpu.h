@@ -315,5 +315,7 @@ const char *SLIMGPU_LastError(void);
 #include "slim_gpu_filter.h"
 /* Per-user candidate sets scored and ordered on the device: the 1-vs-k protocol at any k. */
 #include "slim_gpu_cand.h"
+/* The figures of an evaluation per user group, from the same scoring pass; a grid that selects on one group. */
+#include "slim_gpu_groups.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

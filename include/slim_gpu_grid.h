@@ -21,10 +21,13 @@
  *   SLIM_OPTION_GPU_EVALNEGPOP (25)    0 or 1; 1 needs slot 23
  *   SLIM_OPTION_GPU_EVALEXPOSURE (26)  0 or 1; 1: the evaluation in HBM, nrcmds <= 128, slot 23 off
  *   a filter                           the evaluation in HBM, a filter as wide as the staged matrix
+ *   user groups (slim_gpu_groups.h)    group ids in [-1, ngroups), 1 to 1024 groups, select_group in [-1, ngroups);
+ *                                      the evaluation in HBM.  Judged by SLIMGPU_GridSetGroups, after the open and
+ *                                      before the first solve; they combine with every mode above
  *
  * A grid with none of these (a plain grid) never fails for want of the evaluation in HBM: it falls back to top-N
- * lists on the device and hit counting on the device, then to the host loop.  A strided, filtered, sampled or
- * exposure grid never falls back to the unrestricted figures: a pair that cannot be evaluated as asked is SLIM_ERROR.
+ * lists on the device and hit counting on the device, then to the host loop.  A strided, filtered, sampled, exposure
+ * or grouped grid never falls back to the unrestricted figures: a pair that cannot be evaluated as asked is SLIM_ERROR.
  *
  * SLIM_GPU_NGPUS in the environment serves where ioptions leaves SLIM_OPTION_GPU_NGPUS at -1, as for SLIM_Learn.
  */

@@ -337,6 +337,28 @@ _GRID_SIGNATURES = {
 
 GRID_SYMBOLS = tuple(_GRID_SIGNATURES)
 
+# per-group figures of an evaluation and a grid that selects on a group (include/slim_gpu_groups.h); the arrays are
+# passed as pointers
+_GROUP_SIGNATURES = {
+    "SLIMGPU_EvalSetSetGroups": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "SLIMGPU_EvalSetSetHistoryBands": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "SLIMGPU_EvalSetClearGroups": (None, [C.c_void_p]),
+    "SLIMGPU_EvalSetGroupInfo": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "SLIMGPU_EvalSetLastGroupFigures": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "SLIMGPU_GroupPartition": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "SLIMGPU_GridSetGroups": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "SLIMGPU_GridGroupInfo": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "SLIMGPU_GridLastGroups": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "Py_SLIM_MselectGrouped": (C.c_int32, [C.c_void_p, C.c_void_p, i32_1d, f64_1d, f64_1d, f64_1d,
+                                           C.c_int32, C.c_int32] + [C.c_void_p] * 9 +
+                               [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+}
+
+GROUP_SYMBOLS = tuple(_GROUP_SIGNATURES)
+MAX_GROUPS = 1024       # SLIMGPU_MAX_GROUPS
+GROUP_CELL = 9          # SLIMGPU_GROUP_CELL: l1, l2, HR, HR_head, HR_tail, ARHR, nvalid, nvalid_head, nvalid_tail
+
 _lib = None
 
 
@@ -356,7 +378,8 @@ def load():
                               list(_FILTER_SIGNATURES.items()) + list(_FILTERED_EVAL_SIGNATURES.items()) +
                               list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items()) +
                               list(_WSAMPLE_SIGNATURES.items()) + list(_EXPLAIN_SIGNATURES.items()) +
-                              list(_EXPOSURE_SIGNATURES.items()) + list(_GRID_SIGNATURES.items())):
+                              list(_EXPOSURE_SIGNATURES.items()) + list(_GRID_SIGNATURES.items()) +
+                              list(_GROUP_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

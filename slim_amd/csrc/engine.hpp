@@ -227,6 +227,15 @@ void evalset_free(slimgpu_evalset_t* es);
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es);
 int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out,
                        slimgpu_filter* filter = nullptr);
+// slim_gpu_groups.h: while groups are set, every evaluation of the eval set also forms the rows of its groups from
+// the records it sums anyway; evalset_group_figures hands out the last evaluation's, out[(ngroups + 1) * ncutoffs]
+// with everybody's rows last.  evalset_groups: the number of groups, 0 without.
+int32_t evalset_set_groups(slimgpu_evalset_t* es, int32_t ngroups, const int32_t* group_of_user);
+int32_t evalset_set_history_bands(slimgpu_evalset_t* es, int32_t nbounds, const int32_t* bounds);
+void evalset_clear_groups(slimgpu_evalset_t* es);
+int32_t evalset_group_info(const slimgpu_evalset_t* es, int32_t* ngroups, int32_t* members);
+int32_t evalset_groups(const slimgpu_evalset_t* es);
+int32_t evalset_group_figures(const slimgpu_evalset_t* es, int32_t ncutoffs, EvalResult* out);
 // slim_gpu_cand.h: the figures of the candidate lists (score descending, then slot) of the eval set's users at its
 // cutoffs; a set of another ncols, with too few rows or with a selected row above SLIMGPU_MAX_LIST is refused
 int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_candset* cs,

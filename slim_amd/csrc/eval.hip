@@ -127,18 +127,12 @@ __global__ void k_rank_terms(int32_t nsel, const int32_t* __restrict__ users, co
   }
 }
 
-// one wavefront per cutoff: 64 positions' terms per coalesced load, added by lane order = position order
-__global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nsel, const UserTerms* __restrict__ terms,
-                                                          EvalSums* __restrict__ out) {
-  const int lane = threadIdx.x;
-  terms += (int64_t)blockIdx.x * nsel;
+// The accumulators of one cutoff in one wavefront: every lane holds a record, add() walks the first `cnt` lanes in
+// lane order and every lane keeps the same running sums.
+struct SumsInLaneOrder {
   float hr_all = 0, hr_head = 0, hr_tail = 0, arhr = 0;
   int nvalid = 0, nhead = 0, ntail = 0;
-  for (int32_t b = 0; b < nsel; b += 64) {
-    const int32_t u = b + lane;
-    UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
-    if (u < nsel) t = terms[u];
-    const int cnt = nsel - b < 64 ? nsel - b : 64;
+  __device__ __forceinline__ void add(const UserTerms& t, int cnt) {
     for (int k = 0; k < cnt; ++k) {
       const int fl = __shfl(t.flags, k);
       if (!(fl & 1)) continue;
@@ -153,11 +147,81 @@ __global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nsel, const Us
       arhr += ar;
     }
   }
-  if (lane == 0) {
-    EvalSums& o = out[blockIdx.x];
+  __device__ __forceinline__ void store(EvalSums& o) const {
     o.f[0] = hr_all; o.f[1] = hr_head; o.f[2] = hr_tail; o.f[3] = arhr;
     o.n[0] = nvalid; o.n[1] = nhead; o.n[2] = ntail;
     o.pad = 0;
+  }
+};
+
+// every position of one cutoff: 64 positions' terms per coalesced load, added by lane order = position order
+__device__ __forceinline__ SumsInLaneOrder sum_every_position(int32_t nsel, const UserTerms* __restrict__ terms,
+                                                              int lane) {
+  SumsInLaneOrder sums;
+  for (int32_t b = 0; b < nsel; b += 64) {
+    const int32_t u = b + lane;
+    UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
+    if (u < nsel) t = terms[u];
+    sums.add(t, nsel - b < 64 ? nsel - b : 64);
+  }
+  return sums;
+}
+
+// one wavefront per cutoff
+__global__ __launch_bounds__(64) void k_sum_in_user_order(int32_t nsel, const UserTerms* __restrict__ terms,
+                                                          EvalSums* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const SumsInLaneOrder sums = sum_every_position(nsel, terms + (int64_t)blockIdx.x * nsel, lane);
+  if (lane == 0) sums.store(out[blockIdx.x]);
+}
+
+// one wavefront per (cutoff, group) = (blockIdx.x, blockIdx.y), ngroups = gridDim.y - 1: the positions
+// order[offsets[g] .. offsets[g + 1]) of the group (slim_gpu_groups.h; ascending, every one in [0, nsel)), 64 gathered
+// records at a time, added by lane order = position order with the arithmetic above.  out[k * ngroups + g]; a group
+// without positions gives zeros.  The last row of blocks is k_sum_in_user_order's work, every[k], in the same launch:
+// the longest chain of the launch is the one over everybody, which ran anyway.
+__global__ __launch_bounds__(64) void k_sum_groups_in_user_order(int32_t nsel, const UserTerms* __restrict__ terms,
+                                                                 const int32_t* __restrict__ order,
+                                                                 const int64_t* __restrict__ offsets,
+                                                                 EvalSums* __restrict__ out,
+                                                                 EvalSums* __restrict__ every) {
+  const int lane = threadIdx.x;
+  const int ngroups = gridDim.y - 1;
+  terms += (int64_t)blockIdx.x * nsel;
+  if ((int)blockIdx.y == ngroups) {
+    const SumsInLaneOrder all = sum_every_position(nsel, terms, lane);
+    if (lane == 0) all.store(every[blockIdx.x]);
+    return;
+  }
+  const int64_t i0 = offsets[blockIdx.y], i1 = offsets[blockIdx.y + 1];
+  SumsInLaneOrder sums;
+  for (int64_t b = i0; b < i1; b += 64) {
+    const int64_t i = b + lane;
+    UserTerms t = {0.0, 0.0, 0.0, 0.0f, 0};
+    if (i < i1) t = terms[order[i]];
+    sums.add(t, i1 - b < 64 ? (int)(i1 - b) : 64);
+  }
+  if (lane == 0) sums.store(out[(int64_t)blockIdx.x * ngroups + blockIdx.y]);
+}
+
+// the group of every position by the length of its user's history: #{j : length >= bounds[j]} (bounds ascend; they
+// are read from LDS)
+__global__ __launch_bounds__(256) void k_history_bands(int32_t nsel, const int32_t* __restrict__ users,
+                                                       const int64_t* __restrict__ hptr, int32_t nbounds,
+                                                       const int32_t* __restrict__ bounds,
+                                                       int32_t* __restrict__ group_of_position) {
+  __shared__ int32_t s_bounds[SLIMGPU_MAX_GROUPS];
+  for (int j = threadIdx.x; j < nbounds; j += blockDim.x) s_bounds[j] = bounds[j];
+  __syncthreads();
+  for (int32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nsel; q += gridDim.x * blockDim.x) {
+    const int32_t u = users ? users[q] : q;
+    const int64_t len = hptr[u + 1] - hptr[u];
+    int lo = 0, hi = nbounds;  // the first bound above len
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_bounds[mid] <= len) lo = mid + 1; else hi = mid;
+    }
+    group_of_position[q] = lo;
   }
 }
 
@@ -288,6 +352,22 @@ void launch_rank_terms(hipStream_t stream, int num_cus, int32_t nsel, const int3
 void launch_sum_in_user_order(hipStream_t stream, int32_t nsel, int32_t ncut, const UserTerms* terms,
                               EvalSums* out) {
   hipLaunchKernelGGL(k_sum_in_user_order, dim3(ncut), dim3(64), 0, stream, nsel, terms, out);
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_sum_groups_in_user_order(hipStream_t stream, int32_t nsel, int32_t ncut, int32_t ngroups,
+                                     const UserTerms* terms, const int32_t* order, const int64_t* offsets,
+                                     EvalSums* out, EvalSums* every) {
+  hipLaunchKernelGGL(k_sum_groups_in_user_order, dim3(ncut, ngroups + 1), dim3(64), 0, stream, nsel, terms, order,
+                     offsets, out, every);
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_history_bands(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* users, const int64_t* hptr,
+                          int32_t nbounds, const int32_t* bounds, int32_t* group_of_position) {
+  const int blocks = std::max(1, std::min((nsel + 255) / 256, num_cus * 8));
+  hipLaunchKernelGGL(k_history_bands, dim3(blocks), dim3(256), 0, stream, nsel, users, hptr, nbounds, bounds,
+                     group_of_position);
   HIP_TRY(hipGetLastError());
 }
 

@@ -96,5 +96,17 @@ void launch_rank_terms(hipStream_t stream, int num_cus, int32_t nsel, const int3
 // out[k] = the accumulators of cutoff k, positions added in position order (one wavefront per cutoff)
 void launch_sum_in_user_order(hipStream_t stream, int32_t nsel, int32_t ncut, const UserTerms* terms,
                               EvalSums* out);
+// slim_gpu_groups.h: out[k * ngroups + g] = the accumulators of cutoff k over the positions order[offsets[g] ..
+// offsets[g + 1]) (device arrays; ascending inside a group, each in [0, nsel)), added in that order with the
+// arithmetic of launch_sum_in_user_order (one wavefront per cutoff and group); ngroups >= 1.  The same launch forms
+// every[k], launch_sum_in_user_order's output bit for bit, in one more wavefront per cutoff: it stands in for that
+// launch, it does not follow it.
+void launch_sum_groups_in_user_order(hipStream_t stream, int32_t nsel, int32_t ncut, int32_t ngroups,
+                                     const UserTerms* terms, const int32_t* order, const int64_t* offsets,
+                                     EvalSums* out, EvalSums* every);
+// group_of_position[q] = #{j : the history length of the user at position q >= bounds[j]} (bounds[nbounds]: a device
+// array, ascending, nbounds <= SLIMGPU_MAX_GROUPS; hptr: the staged matrix's row pointer)
+void launch_history_bands(hipStream_t stream, int num_cus, int32_t nsel, const int32_t* users, const int64_t* hptr,
+                          int32_t nbounds, const int32_t* bounds, int32_t* group_of_position);
 
 }  // namespace slimamd

@@ -214,6 +214,47 @@ int32_t slimgpu_grid::open(const int32_t* ioptions, const double* doptions, int3
   return cands ? SLIM_OK : refuse(kFeatures[0], last_error());
 }
 
+// Groups ride on the eval set: a grid without one has nothing to form them from, and is refused rather than
+// evaluated over everybody.
+int32_t slimgpu_grid::set_groups(int32_t ngroups_, const int32_t* group_of_user, int32_t select_group_) {
+  const std::string who = "SLIMGPU_GridSetGroups: ";
+  auto refuse_input = [&](const std::string& why) {
+    set_error(who + why);
+    return (int32_t)SLIM_ERROR_INPUT;
+  };
+  if (ngroups_ >= 1 && (select_group_ < -1 || select_group_ >= ngroups_))
+    return refuse_input("select_group " + std::to_string(select_group_) + " is outside [-1, " +
+                        std::to_string(ngroups_) + ")");
+  if (dmodel || model) return refuse_input("the groups are set before the first solve");
+  if (!evalset)
+    return refuse_input(
+        "groups need the evaluation in HBM (cd on one GPU, nrcmds >= 1, SLIM_GPU_RESIDENT and SLIM_GPU_EVAL_RESIDENT "
+        "not 0, a matrix staged without merged pairs)" +
+        (*last_error() ? ": " + std::string(last_error()) : std::string()));
+  // (the number of groups and the group of every user are the eval set's to judge)
+  if (const int32_t rc = evalset_set_groups(evalset, ngroups_, group_of_user); rc != SLIM_OK) return rc;
+  ngroups = ngroups_;
+  select_group = select_group_;
+  return SLIM_OK;
+}
+
+int32_t slimgpu_grid::last_groups(EvalResult* rows) const {
+  if (ngroups == 0 || !evalset) {
+    set_error("SLIMGPU_GridLastGroups: no groups are set on this grid");
+    return SLIM_ERROR_INPUT;
+  }
+  if (!group_rows_stand) {
+    set_error("SLIMGPU_GridLastGroups: the last pair was not evaluated per group");
+    return SLIM_ERROR_INPUT;
+  }
+  return evalset_group_figures(evalset, 1, rows);
+}
+
+int32_t slimgpu_grid::group_members(int32_t* members) const {
+  int32_t n = 0;
+  return evalset_group_info(evalset, &n, members);
+}
+
 void slimgpu_grid::describe() const {
   if (stride > 1) std::printf("  evaluating every %d-th user: %zu of %d\n", stride, sel.size(), nall);
   if (filter) {
@@ -226,6 +267,9 @@ void slimgpu_grid::describe() const {
     std::printf("  item filter: %lld of %d items allowed, %lld exclusion entries\n", (long long)allowed, hflt.ncols,
                 (long long)(hflt.xptr ? hflt.xptr[hflt.xusers] : 0));
   }
+  if (ngroups > 0)
+    std::printf("  user groups: %d, pairs chosen on %s\n", ngroups,
+                select_group < 0 ? "everybody" : ("group " + std::to_string(select_group)).c_str());
   if (cands) {
     int64_t entries = 0;
     candset_info(cands, nullptr, nullptr, &entries);
@@ -290,6 +334,7 @@ int32_t slimgpu_grid::solve(double l1r, double l2r, slimgpu_grid_cell_t* cell) {
   LearnOptions opt = base;
   opt.l1r = l1r;
   opt.l2r = l2r;
+  group_rows_stand = false;
   int32_t status = learn(opt);
   if (status != SLIM_OK) return status;
   *cell = slimgpu_grid_cell_t{};
@@ -299,12 +344,14 @@ int32_t slimgpu_grid::solve(double l1r, double l2r, slimgpu_grid_cell_t* cell) {
   cell->solve_seconds = last_stats().total_ms / 1e3;
   EvalResult ev;
   if (evaluate_in_hbm(&ev, &cell->exposure) != SLIM_OK) {
-    // (no silent evaluation of everybody, without the filter, on the whole catalogue, or without the exposure)
-    if (stride > 1 || filter || cands || evalexpo) return SLIM_ERROR;
+    // (no silent evaluation of everybody, without the filter, on the whole catalogue, without the exposure, or in
+    // place of the groups)
+    if (stride > 1 || filter || cands || evalexpo || ngroups > 0) return SLIM_ERROR;
     status = evaluate_lists(&ev);
     if (status != SLIM_OK) return status;
   }
   figures_out(ev, cell->metrics, cell->nvalid);
+  group_rows_stand = ngroups > 0;  // (with groups the figures can only have come from the eval set)
   cell->has_exposure = evalexpo;
   return SLIM_OK;
 }
@@ -339,6 +386,39 @@ int32_t SLIMGPU_GridSolve(slimgpu_grid_t* grid, double l1r, double l2r, slimgpu_
 }
 
 slim_t* SLIMGPU_GridModel(slimgpu_grid_t* grid, int32_t* status) { return grid->host_model(status); }
+
+int32_t SLIMGPU_GridSetGroups(slimgpu_grid_t* grid, int32_t ngroups, const int32_t* group_of_user,
+                              int32_t select_group) {
+  set_error("");
+  if (!grid || !group_of_user) {
+    set_error("SLIMGPU_GridSetGroups: bad arguments (a grid, a group for every user)");
+    return SLIM_ERROR_INPUT;
+  }
+  return grid->set_groups(ngroups, group_of_user, select_group);
+}
+
+int32_t SLIMGPU_GridGroupInfo(const slimgpu_grid_t* grid, int32_t* ngroups, int32_t* members) {
+  set_error("");
+  if (!grid || !ngroups || grid->ngroups == 0) {
+    set_error(grid && ngroups ? "SLIMGPU_GridGroupInfo: no groups are set on this grid"
+                              : "SLIMGPU_GridGroupInfo: bad arguments (a grid, ngroups)");
+    return SLIM_ERROR_INPUT;
+  }
+  *ngroups = grid->ngroups;
+  return members ? grid->group_members(members) : SLIM_OK;
+}
+
+int32_t SLIMGPU_GridLastGroups(slimgpu_grid_t* grid, double* metrics, int32_t* nvalid) {
+  set_error("");
+  if (!grid || !metrics || !nvalid) {
+    set_error("SLIMGPU_GridLastGroups: bad arguments (a grid, the outputs)");
+    return SLIM_ERROR_INPUT;
+  }
+  std::vector<EvalResult> rows((size_t)grid->ngroups + 1);
+  if (const int32_t rc = grid->last_groups(rows.data()); rc != SLIM_OK) return rc;
+  for (int32_t g = 0; g <= grid->ngroups; ++g) figures_out(rows[(size_t)g], metrics + 4 * g, nvalid + 3 * g);
+  return SLIM_OK;
+}
 
 void SLIMGPU_GridFree(slimgpu_grid_t** grid) {
   if (!grid) return;

@@ -24,6 +24,8 @@ struct slimgpu_grid {
   uint64_t evalseed = 1;
   int32_t nall = 0;          // the users an evaluation of everybody covers
   std::vector<int32_t> sel;  // stride > 1: the evaluated users
+  int32_t ngroups = 0, select_group = -1;  // slim_gpu_groups.h (0: no groups); the group the caller's loop selects on
+  bool group_rows_stand = false;           // the eval set's group rows are those of the last solved pair
   // what the grid holds between its pairs; the destructor is the only place it is freed
   slimgpu_matrix_t* mat = nullptr;  // (none for ADMM)
   int32_t ncols = 0;                // the marker's width
@@ -44,6 +46,10 @@ struct slimgpu_grid {
   // the refusal with its reason as the error text
   int32_t open(const int32_t* ioptions, const double* doptions, int32_t marker_ncols, int32_t nsolves);
   void describe() const;
+  // slim_gpu_groups.h, between open() and the first solve: the eval set forms the group rows of every pair
+  int32_t set_groups(int32_t ngroups_, const int32_t* group_of_user, int32_t select_group_);
+  int32_t last_groups(slimamd::EvalResult* rows /* [ngroups + 1] */) const;
+  int32_t group_members(int32_t* members /* [ngroups + 1] */) const;
   int32_t solve(double l1r, double l2r, slimgpu_grid_cell_t* cell);
   slim_csr_t* host_model(int32_t* status);
 

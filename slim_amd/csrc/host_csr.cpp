@@ -682,4 +682,39 @@ void exposure_summary(int32_t ncols, const uint32_t* pop, const int32_t* fmarker
   *out = s;
 }
 
+int32_t group_partition(const char* who, int32_t nsel, const int32_t* users, int32_t nall, int32_t ngroups,
+                        const int32_t* group_of_user, int32_t* order, int64_t* offsets) {
+  std::string what;
+  if (ngroups < 1 || ngroups > SLIMGPU_MAX_GROUPS)
+    what = "between 1 and " + std::to_string(SLIMGPU_MAX_GROUPS) + " groups, not " + std::to_string(ngroups);
+  else if (nsel < 0 || nall < 0 || !offsets || (nall > 0 && !group_of_user) || (nsel > 0 && !order))
+    what = "bad arguments (a group for every user, the order and the offsets)";
+  else if (!users && nsel > nall)
+    what = std::to_string(nsel) + " positions and " + std::to_string(nall) + " users";
+  for (int32_t u = 0; u < nall && what.empty(); ++u)
+    if (group_of_user[u] < -1 || group_of_user[u] >= ngroups)
+      what = "user " + std::to_string(u) + " has group " + std::to_string(group_of_user[u]) + ", outside [-1, " +
+             std::to_string(ngroups) + ")";
+  for (int32_t q = 0; users && q < nsel && what.empty(); ++q)
+    if (users[q] < 0 || users[q] >= nall)
+      what = "user " + std::to_string(users[q]) + " is outside [0, " + std::to_string(nall) + ")";
+  if (!what.empty()) {
+    set_error(std::string(who) + ": " + what);
+    return SLIM_ERROR_INPUT;
+  }
+  // a stable counting sort: the members of every group, then their places in position order
+  std::fill(offsets, offsets + ngroups + 1, (int64_t)0);
+  for (int32_t q = 0; q < nsel; ++q) {
+    const int32_t g = group_of_user[users ? users[q] : q];
+    if (g >= 0) ++offsets[g + 1];
+  }
+  for (int32_t g = 0; g < ngroups; ++g) offsets[g + 1] += offsets[g];
+  std::vector<int64_t> next(offsets, offsets + ngroups);
+  for (int32_t q = 0; q < nsel; ++q) {
+    const int32_t g = group_of_user[users ? users[q] : q];
+    if (g >= 0) order[next[(size_t)g]++] = q;
+  }
+  return SLIM_OK;
+}
+
 }  // namespace slimamd

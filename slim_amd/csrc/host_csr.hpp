@@ -166,6 +166,14 @@ void list_exposure_host(int32_t ncols, int64_t nlists, int32_t nrcmds, const int
 void exposure_summary(int32_t ncols, const uint32_t* pop, const int32_t* fmarker, int32_t fm_ncols, int64_t nlists,
                       const uint32_t* E, int64_t outside, slimgpu_exposure_t* out);
 
+// slim_gpu_groups.h on the host, the definition in code: a stable counting sort of the positions by the group of
+// their user (users == nullptr: position q is user q).  order[offsets[g] .. offsets[g + 1]) are the positions of group
+// g, ascending; positions of group -1 are not listed.  SLIM_OK, or SLIM_ERROR_INPUT with "<who>: ..." as the error
+// text and nothing written: ngroups outside [1, SLIMGPU_MAX_GROUPS], a group outside [-1, ngroups) for any user of
+// [0, nall), a user outside [0, nall).
+int32_t group_partition(const char* who, int32_t nsel, const int32_t* users, int32_t nall, int32_t ngroups,
+                        const int32_t* group_of_user, int32_t* order, int64_t* offsets);
+
 // ---- files ------------------------------------------------------------------
 bool write_binrow(const slim_csr_t* m, const char* path);   // api.c:174-177
 slim_csr_t* read_binrow(const char* path);                  // api.c:187-194

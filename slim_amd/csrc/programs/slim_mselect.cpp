@@ -11,7 +11,8 @@ int main(int argc, char** argv) {
       {"ifmt", true},    {"binarize", false}, {"optTol", true},  {"niters", true},
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
-      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"evalnegpop", false}, {"evalexposure", false}, {"gpukernel", true}, {"help", false}};
+      {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"evalnegpop", false}, {"evalexposure", false}, {"gpukernel", true}, {"help", false},
+      {"evalgroupfile", true}, {"evalhistbands", true}, {"evalselectgroup", true}};
   specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
   if (a.has("help") || a.pos.size() != 3) {
@@ -25,6 +26,13 @@ int main(int argc, char** argv) {
                 "   -evalnegpop  (with -evalnegs: draw the negatives in proportion to item popularity, not uniformly)\n"
                 "   -evalexposure  (engine extension: one more line per pair on what its lists show -- coverage, tail share,\n"
                 "   Gini, mean popularity, counted on the device; needs the evaluation in HBM, nrcmds <= 128, no -evalnegs)\n"
+                "   -evalgroupfile=file | -evalhistbands=b0,b1,..  (engine extension: every pair is also evaluated per user\n"
+                "   group, from the same scoring pass: one more line per group.  The file holds one group per user row of the\n"
+                "   train-file, 0 .. ngroups-1 or -1 for none; the bands (ascending, >= 1) group the users by the length of\n"
+                "   their training row: group g holds those that reach g of the bounds.  Needs the evaluation in HBM)\n"
+                "   -evalselectgroup=g  (with either: the best pairs are chosen on group g's figures, not on everybody's;\n"
+                "   a group without an evaluated user that has a test row ends the run at the first pair, as the library's\n"
+                "   loop does)\n"
                 "   (-nrcmds above 128 is evaluated in HBM from the ranks of the held-out items: no lists are formed)\n"
                 "   -gpukernel=i  (engine extension: slimgpu_kernel_et, 0 = the engine's choice; 6 = FSLIM in item space)\n"
                 "%s   (engine extension: every pair is evaluated under the filter; a held-out item it removes is a miss;\n"
@@ -49,6 +57,27 @@ int main(int argc, char** argv) {
   if (evalexposure && evalnegs > 0) die("-evalexposure does not combine with -evalnegs: the exposure of sampled lists is not built.");
   if (evalexposure && (nrcmds < 1 || nrcmds > 128))
     die("-evalexposure needs lists of 1 to 128 places (the lists behind the evaluation), not " + std::to_string(nrcmds) + ".");
+  if (a.has("evalgroupfile") && a.has("evalhistbands"))
+    die("The -evalgroupfile and -evalhistbands options cannot be used together.");
+  const bool grouped = a.has("evalgroupfile") || a.has("evalhistbands");
+  if (a.has("evalselectgroup") && !grouped) die("-evalselectgroup chooses on a user group: it needs -evalgroupfile or -evalhistbands.");
+  if (a.has("evalgroupfile") && !file_exists(a.str("evalgroupfile", "")))
+    die("Input file " + a.str("evalgroupfile", "") + " does not exist.");
+  std::vector<int32_t> bands;
+  if (a.has("evalhistbands")) {  // b0,b1,..: integers >= 1, strictly ascending, nothing else
+    const std::string list = a.str("evalhistbands", "");
+    const char* p = list.c_str();
+    for (bool more = true; more;) {
+      char* e;
+      const long b = std::strtol(p, &e, 10);
+      if (e == p || b < 1 || b > 0x7fffffffl || (!bands.empty() && b <= bands.back()) || (*e != ',' && *e != 0) ||
+          (int)bands.size() + 1 >= SLIMGPU_MAX_GROUPS)
+        die("Invalid -evalhistbands of " + list + ".");
+      bands.push_back((int32_t)b);
+      more = *e == ',';
+      p = e + 1;
+    }
+  }
   const bool filtered = filter_options(a);
   filter_files_exist(a);
   if (evalnegs > 0 && filtered) die("-evalnegs takes no item filter: candidate rows are scored as they are.");
@@ -56,6 +85,33 @@ int main(int argc, char** argv) {
     die("-evalnegs needs nrcmds <= 128 (the candidate lists use the eval set's cutoffs), not " + std::to_string(nrcmds) + ".");
   Csr trn = read_matrix(a.pos[0], fmt), tst = read_matrix(a.pos[1], fmt);
   if (a.has("binarize")) trn.has_val = false;
+  // the group of every user row of the training matrix: the file's, or the band of the row's length
+  std::vector<int32_t> group_of_user;
+  int32_t ngroups = 0;
+  if (a.has("evalgroupfile")) {
+    FILE* gf = std::fopen(a.str("evalgroupfile", "").c_str(), "r");
+    long g;
+    while (std::fscanf(gf, "%ld", &g) == 1) {
+      if (g < -1 || g >= SLIMGPU_MAX_GROUPS) die("bad group " + std::to_string(g) + " in " + a.str("evalgroupfile", ""));
+      group_of_user.push_back((int32_t)g);
+      ngroups = std::max(ngroups, (int32_t)g + 1);
+    }
+    if (!std::feof(gf)) die("bad group in " + a.str("evalgroupfile", ""));
+    std::fclose(gf);
+    if ((int32_t)group_of_user.size() != trn.nrows)
+      die("The -evalgroupfile holds " + std::to_string(group_of_user.size()) + " groups, the training matrix has " +
+          std::to_string(trn.nrows) + " user rows.");
+    if (ngroups < 1) die("The -evalgroupfile puts no user into a group.");
+  } else if (!bands.empty()) {
+    ngroups = (int32_t)bands.size() + 1;
+    for (int32_t u = 0; u < trn.nrows; ++u)
+      group_of_user.push_back(
+          (int32_t)(std::upper_bound(bands.begin(), bands.end(), (int32_t)(trn.ptr[u + 1] - trn.ptr[u])) - bands.begin()));
+  }
+  const int select_group = a.integer("evalselectgroup", -1);
+  if (a.has("evalselectgroup") && (select_group < 0 || select_group >= ngroups))
+    die("Invalid -evalselectgroup of " + a.str("evalselectgroup", "") + ": the groups are 0 to " +
+        std::to_string(ngroups - 1) + ".");
   const std::string sim = a.str("simtype", "cos");
   banner();
   std::printf("  trnfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[0].c_str(), trn.nrows, trn.ncols, trn.nnz());
@@ -101,6 +157,13 @@ int main(int argc, char** argv) {
   slimgpu_grid_t* grid = nullptr;
   if (SLIMGPU_GridOpen(hold, th, io, dopt, std::max(trn.ncols, tst.ncols), npairs, flt.handle, &grid) != SLIM_OK)
     die(std::string("cannot evaluate this grid: ") + SLIMGPU_LastError());
+  if (grouped && SLIMGPU_GridSetGroups(grid, ngroups, group_of_user.data(), select_group) != SLIM_OK)
+    die(std::string("cannot evaluate this grid: ") + SLIMGPU_LastError());
+  std::vector<int32_t> members((size_t)ngroups + 1, 0);  // (of the users the grid evaluates: the library's count)
+  if (grouped && SLIMGPU_GridGroupInfo(grid, &ngroups, members.data()) != SLIM_OK)
+    die(std::string("cannot evaluate this grid: ") + SLIMGPU_LastError());
+  std::vector<double> gmet(4 * ((size_t)ngroups + 1));
+  std::vector<int32_t> gnv(3 * ((size_t)ngroups + 1));
   SLIMGPU_GridDescribe(grid);
   std::printf("\nEstimating & evaluating models...\n\n");
   double best_hr = 0, best_ar = 0, bh_l1 = 0, bh_l2 = 0, ba_l1 = 0, ba_l2 = 0;
@@ -123,13 +186,26 @@ int main(int argc, char** argv) {
       while (!name.empty() && (name.back() == '\n' || name.back() == '\r')) name.pop_back();
       write_matrix(static_cast<slim_csr_t*>(model), name + ".model", fmt == Fmt::csrnv ? Fmt::csr : fmt);
     }
-    const double hr = c.metrics[0], arhr = c.metrics[3];
+    double hr = c.metrics[0], arhr = c.metrics[3];
     std::printf("l1r: %.2le l2r: %.2le nnz: %7zd hr: %.4f hr_head: %.4f hr_tail: %.4f arhr: %.4f time: %.2lf\n",
                 l1, l2, (ssize_t)c.nnz, hr, c.metrics[1], c.metrics[2], arhr, c.solve_seconds);
     if (c.has_exposure)
       std::printf("  exposure@%d: coverage: %.4f tail_share: %.4f gini: %.4f avg_pop: %.2f distinct: %d slots: %lld\n",
                   nrcmds, c.exposure.coverage, c.exposure.tail_share, c.exposure.gini, c.exposure.avg_pop,
                   c.exposure.distinct, (long long)c.exposure.slots);
+    if (grouped) {
+      if (SLIMGPU_GridLastGroups(grid, gmet.data(), gnv.data()) != SLIM_OK)
+        die(std::string("cannot read the group figures: ") + SLIMGPU_LastError());
+      for (int32_t g = 0; g < ngroups; ++g)
+        std::printf("  group %d: members: %d hr: %.4f hr_head: %.4f hr_tail: %.4f arhr: %.4f nvalid: %d\n", g, members[g],
+                    gmet[4 * g], gmet[4 * g + 1], gmet[4 * g + 2], gmet[4 * g + 3], gnv[3 * g]);
+      if (select_group >= 0) {  // the best pairs are chosen on this group; without a valid user in it, on nothing
+        if (gnv[3 * select_group] < 1)
+          die("Group " + std::to_string(select_group) + " has no evaluated user with a test row: no pair can be chosen on it.");
+        hr = gmet[4 * select_group];
+        arhr = gmet[4 * select_group + 3];
+      }
+    }
     if (hr > best_hr) { best_hr = hr; bh_l1 = l1; bh_l2 = l2; }
     if (arhr > best_ar) { best_ar = arhr; ba_l1 = l1; ba_l2 = l2; }
   }

@@ -46,6 +46,16 @@ struct slimgpu_evalset {
   // exposure call) and the host image of the counters: the summaries are formed on the host
   std::vector<int32_t> h_fm;
   std::vector<uint32_t> h_pop, h_expo;
+  // groups (slim_gpu_groups.h; ngroups == 0: none): the positions of every group (GroupPartition's order and offsets,
+  // on the device), the evaluated members, the group sums [cutoff][group] of the last evaluation with their host
+  // image, and that evaluation's cutoffs (0: none since the groups were set) and own rows
+  int32_t ngroups = 0, group_ncut = 0;
+  std::vector<int32_t> group_members;  // [ngroups + 1]; the last: every position
+  slimamd::DeviceBuffer<int32_t> d_gorder;
+  slimamd::DeviceBuffer<int64_t> d_goffsets;
+  slimamd::DeviceBuffer<slimamd::EvalSums> d_gsums;  // [SLIMGPU_MAX_RANK_CUTOFFS][ngroups]
+  std::vector<slimamd::EvalSums> h_gsums;
+  slimamd::EvalResult group_every[SLIMGPU_MAX_RANK_CUTOFFS];
   const int64_t* tbase() const { return d_tbase.get() ? d_tbase.get() : tst.ptr.get(); }
   ~slimgpu_evalset() {
     (void)hipSetDevice(device);
@@ -232,6 +242,25 @@ void close_stats(slimgpu_evalset_t* es, bool ranked, slimgpu_eval_stats_t& st,
   g_eval_stats = st;
 }
 
+// the figures of one cutoff's accumulators
+EvalResult result_of(const EvalSums& s) {
+  EvalResult r;
+  r.nvalid = s.n[0]; r.nvalid_head = s.n[1]; r.nvalid_tail = s.n[2];
+  r.hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0; r.arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
+  r.hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0; r.hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
+  return r;
+}
+
+// The sums of `ncut` cutoffs over `terms` ([ncut][nsel]) into out[0 .. ncut), positions added in position order: what
+// every evaluation ends in.  While groups are set (slim_gpu_groups.h) one launch forms them and, from the same
+// records, the group rows of these cutoffs -- k0: the place of the first among the call's.
+void queue_sums(slimgpu_evalset_t* es, hipStream_t stream, int32_t ncut, const UserTerms* terms, EvalSums* out,
+                int32_t k0 = 0) {
+  if (es->ngroups == 0) return launch_sum_in_user_order(stream, es->nsel, ncut, terms, out);
+  launch_sum_groups_in_user_order(stream, es->nsel, ncut, es->ngroups, terms, es->d_gorder.get(), es->d_goffsets.get(),
+                                  es->d_gsums.get() + (size_t)k0 * (size_t)es->ngroups, out);
+}
+
 // The end of an evaluation whose sums of `ncut` cutoffs are queued into the eval set's EvalOut (ev0 was recorded
 // before its scorer): ev1, the scorer's byte model, 8 + 32 * ncut bytes down, the sums as results, the stats.
 void finish_evaluation(slimgpu_evalset_t* es, const DeviceCsrView& R, const DeviceRowView& W, const HistoryView& H,
@@ -244,16 +273,22 @@ void finish_evaluation(slimgpu_evalset_t* es, const DeviceCsrView& R, const Devi
     HIP_TRY(hipEventRecord(es->ev1, stream));
     HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
     if (es->hist_entries > 0 && W.nnz > 0) queue_streamed_entries(stream, R.num_cus, H, W, &d_out->streamed);
-    const size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncut;
+    size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncut;
     HIP_TRY(hipMemcpyAsync(&h, d_out, down, hipMemcpyDeviceToHost, stream));
+    if (es->ngroups > 0) {  // (the group rows come down with the same synchronisation)
+      const size_t rows = sizeof(EvalSums) * (size_t)ncut * (size_t)es->ngroups;
+      HIP_TRY(hipMemcpyAsync(es->h_gsums.data(), es->d_gsums.get(), rows, hipMemcpyDeviceToHost, stream));
+      down += rows;
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     st.d2h_bytes = (int64_t)down;
+  } else if (es->ngroups > 0) {
+    std::fill(es->h_gsums.begin(), es->h_gsums.end(), EvalSums{});
   }
-  for (int32_t k = 0; k < ncut; ++k) {
-    const EvalSums& s = h.sums[k];
-    out[k].nvalid = s.n[0]; out[k].nvalid_head = s.n[1]; out[k].nvalid_tail = s.n[2];
-    out[k].hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0; out[k].arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
-    out[k].hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0; out[k].hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
+  for (int32_t k = 0; k < ncut; ++k) out[k] = result_of(h.sums[k]);
+  if (es->ngroups > 0) {
+    std::copy(out, out + ncut, es->group_every);
+    es->group_ncut = ncut;
   }
   st.w_bytes = 8.0 * (double)h.streamed;
   close_stats(es, ranked, st, t_begin);
@@ -295,6 +330,143 @@ int32_t evalset_rows(const slimgpu_evalset_t* es, EvalSetRows* out) {
 void evalset_free(slimgpu_evalset_t* es) { delete es; }
 int32_t evalset_cutoffs(const slimgpu_evalset_t* es) { return es ? es->cut.n : 0; }
 
+// ---- groups (slim_gpu_groups.h) -------------------------------------------------------------------
+namespace {
+// The groups of an eval set from a group per user (users: the eval set's list) or per position (users == nullptr):
+// partitioned by the one host routine, sent to the device, and only then put in the place of the earlier ones.
+int32_t install_groups(const char* who, slimgpu_evalset_t* es, const DeviceCsrView& R, const int32_t* users,
+                       int32_t nall, int32_t ngroups, const int32_t* group_of) {
+  const int32_t nsel = es->nsel;
+  // (sized for a number of groups in range: the partition refuses any other before it writes)
+  const size_t rows = (size_t)std::min(std::max(ngroups, 0), SLIMGPU_MAX_GROUPS) + 1;
+  std::vector<int32_t> order((size_t)std::max(nsel, 1)), members(rows);
+  std::vector<int64_t> offsets(rows);
+  if (const int32_t rc = group_partition(who, nsel, users, nall, ngroups, group_of, order.data(), offsets.data());
+      rc != SLIM_OK)
+    return rc;
+  for (int32_t g = 0; g < ngroups; ++g) members[(size_t)g] = (int32_t)(offsets[(size_t)g + 1] - offsets[(size_t)g]);
+  members[(size_t)ngroups] = nsel;
+  hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  DeviceBuffer<int32_t> d_order((size_t)std::max(nsel, 1));
+  DeviceBuffer<int64_t> d_offsets((size_t)ngroups + 1);
+  DeviceBuffer<EvalSums> d_sums((size_t)ngroups * SLIMGPU_MAX_RANK_CUTOFFS);
+  if (nsel > 0)
+    HIP_TRY(hipMemcpyAsync(d_order.get(), order.data(), sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_offsets.get(), offsets.data(), sizeof(int64_t) * ((size_t)ngroups + 1),
+                         hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream));  // (the sources are this call's; an evaluation may still read the old ones)
+  es->d_gorder = std::move(d_order);
+  es->d_goffsets = std::move(d_offsets);
+  es->d_gsums = std::move(d_sums);
+  es->h_gsums.assign((size_t)ngroups * SLIMGPU_MAX_RANK_CUTOFFS, EvalSums{});
+  es->group_members = std::move(members);
+  es->ngroups = ngroups;
+  es->group_ncut = 0;
+  return SLIM_OK;
+}
+
+// what a failure while the groups are made turns into
+int32_t groups_failure(const char* who) {
+  try {
+    throw;
+  } catch (const HipFail& e) {
+    return hip_failure(who, e);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+}
+}  // namespace
+
+int32_t evalset_set_groups(slimgpu_evalset_t* es, int32_t ngroups, const int32_t* group_of_user) {
+  const char* who = "SLIMGPU_EvalSetSetGroups";
+  DeviceCsrView R;
+  if (!es || !group_of_user || matrix_csr_view(es->mat, &R) != SLIM_OK)
+    return refuse(std::string(who) + ": bad arguments (an eval set and the array)");
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    return install_groups(who, es, R, es->listed ? es->h_users.data() : nullptr, es->nall, ngroups, group_of_user);
+  } catch (...) {
+    return groups_failure(who);
+  }
+}
+
+// the lengths are the staged matrix's, classified where they lie: 4 * nsel bytes come down once, and the positions'
+// groups go through the host partition like a caller's
+int32_t evalset_set_history_bands(slimgpu_evalset_t* es, int32_t nbounds, const int32_t* bounds) {
+  const char* who = "SLIMGPU_EvalSetSetHistoryBands";
+  DeviceCsrView R;
+  if (!es || !bounds || matrix_csr_view(es->mat, &R) != SLIM_OK)
+    return refuse(std::string(who) + ": bad arguments (an eval set and the array)");
+  if (nbounds < 1 || nbounds > SLIMGPU_MAX_GROUPS - 1)
+    return refuse(std::string(who) + ": between 1 and " + std::to_string(SLIMGPU_MAX_GROUPS - 1) + " bounds, not " +
+                  std::to_string(nbounds));
+  for (int32_t j = 0; j < nbounds; ++j) {
+    if (bounds[j] < 1)
+      return refuse(std::string(who) + ": a bound must be at least 1, not " + std::to_string(bounds[j]));
+    if (j > 0 && bounds[j] <= bounds[j - 1]) return refuse(std::string(who) + ": the bounds must ascend strictly");
+  }
+  try {
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(R.device));
+    const int32_t nsel = es->nsel;
+    std::vector<int32_t> band((size_t)std::max(nsel, 1), 0);
+    if (nsel > 0) {
+      hipStream_t stream = static_cast<hipStream_t>(R.stream);
+      DeviceBuffer<int32_t> d_bounds((size_t)nbounds), d_band((size_t)nsel);
+      HIP_TRY(hipMemcpyAsync(d_bounds.get(), bounds, sizeof(int32_t) * (size_t)nbounds, hipMemcpyHostToDevice, stream));
+      launch_history_bands(stream, R.num_cus, nsel, es->listed ? es->d_users.get() : nullptr, R.d_ptr, nbounds,
+                           d_bounds.get(), d_band.get());
+      HIP_TRY(hipMemcpyAsync(band.data(), d_band.get(), sizeof(int32_t) * (size_t)nsel, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    return install_groups(who, es, R, nullptr, nsel, nbounds + 1, band.data());
+  } catch (...) {
+    return groups_failure(who);
+  }
+}
+
+void evalset_clear_groups(slimgpu_evalset_t* es) {
+  if (!es || es->ngroups == 0) return;
+  DeviceCsrView R;
+  if (matrix_csr_view(es->mat, &R) == SLIM_OK) {  // (an evaluation in flight may still read them)
+    (void)hipSetDevice(R.device);
+    (void)hipStreamSynchronize(static_cast<hipStream_t>(R.stream));
+  }
+  es->ngroups = es->group_ncut = 0;
+  es->d_gorder = DeviceBuffer<int32_t>();
+  es->d_goffsets = DeviceBuffer<int64_t>();
+  es->d_gsums = DeviceBuffer<EvalSums>();
+  es->h_gsums.clear();
+  es->group_members.clear();
+}
+
+int32_t evalset_group_info(const slimgpu_evalset_t* es, int32_t* ngroups, int32_t* members) {
+  if (!es || !ngroups) return refuse("SLIMGPU_EvalSetGroupInfo: bad arguments (an eval set, ngroups)");
+  if (es->ngroups == 0) return refuse("SLIMGPU_EvalSetGroupInfo: no groups are set on this eval set");
+  *ngroups = es->ngroups;
+  if (members) std::copy(es->group_members.begin(), es->group_members.end(), members);
+  return SLIM_OK;
+}
+
+int32_t evalset_groups(const slimgpu_evalset_t* es) { return es ? es->ngroups : 0; }
+
+int32_t evalset_group_figures(const slimgpu_evalset_t* es, int32_t ncutoffs, EvalResult* out) {
+  const char* who = "SLIMGPU_EvalSetLastGroupFigures";
+  if (!es || !out) return refuse(std::string(who) + ": bad arguments (an eval set, the outputs)");
+  if (es->ngroups == 0) return refuse(std::string(who) + ": no groups are set on this eval set");
+  if (es->group_ncut == 0) return refuse(std::string(who) + ": no evaluation has run since the groups were set");
+  if (ncutoffs != es->group_ncut)
+    return refuse(std::string(who) + ": the last evaluation had " + std::to_string(es->group_ncut) +
+                  " cutoffs, the call asks for " + std::to_string(ncutoffs));
+  for (int32_t g = 0; g < es->ngroups; ++g)
+    for (int32_t k = 0; k < ncutoffs; ++k)
+      out[(size_t)g * ncutoffs + k] = result_of(es->h_gsums[(size_t)k * (size_t)es->ngroups + (size_t)g]);
+  std::copy(es->group_every, es->group_every + ncutoffs, out + (size_t)es->ngroups * ncutoffs);
+  return SLIM_OK;
+}
+
 int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs, EvalResult* out,
                        slimgpu_filter* filter) {
   const char* who = filter ? "SLIMGPU_ModelEvaluateAtFiltered" : "SLIMGPU_ModelEvaluate";
@@ -311,6 +483,7 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
     HIP_TRY(hipSetDevice(R.device));
     hipStream_t stream = static_cast<hipStream_t>(R.stream);
     es->ws.allocs = 0;
+    es->group_ncut = 0;  // (slim_gpu_groups.h: the group rows on hand are no longer the last evaluation's)
     const HistoryView H = history_of(R, es);
     if (es->nsel > 0) {
       const ScorerRequest rq =
@@ -319,7 +492,7 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
       const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
       HIP_TRY(hipEventRecord(es->ev0, stream));
       st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
-      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      queue_sums(es, stream, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
     }
     finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
     return SLIM_OK;
@@ -366,6 +539,7 @@ int32_t model_evaluate_exposure(slimgpu_evalset_t* es, const slimgpu_model* mode
     HIP_TRY(hipSetDevice(R.device));
     hipStream_t stream = static_cast<hipStream_t>(R.stream);
     es->ws.allocs = 0;
+    es->group_ncut = 0;  // (as in model_evaluate)
     int64_t first_down = 0;
     if (es->h_pop.size() != (size_t)ncols) {  // (the first call on this eval set)
       column_counts(es->mat, ncols, es->h_pop);
@@ -379,7 +553,7 @@ int32_t model_evaluate_exposure(slimgpu_evalset_t* es, const slimgpu_model* mode
       HIP_TRY(hipEventRecord(es->ev0, stream));
       queue_exposure_clear(stream, ncols, es->cut, es->ws);
       st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
-      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      queue_sums(es, stream, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
       queue_exposure_count(stream, R.num_cus, es->ws.oid.get(), es->ws.ocnt.get(), es->nsel, nrcmds, ncols, es->cut,
                            es->ws);
       queue_exposure_cumulate(stream, R.num_cus, ncols, es->cut, es->ws);
@@ -423,6 +597,7 @@ int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* mo
     HIP_TRY(hipSetDevice(R.device));
     hipStream_t stream = static_cast<hipStream_t>(R.stream);
     es->ws.allocs = 0;
+    es->group_ncut = 0;  // (slim_gpu_groups.h: the group rows on hand are no longer the last evaluation's)
     const HistoryView H = history_of(R, es);
     if (es->nsel > 0) {
       const CandidateRows rows = candset_on_device(cs, R.device, R.num_cus, stream, &es->ws.allocs, &st.h2d_bytes);
@@ -431,7 +606,7 @@ int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* mo
       if (st.path == kRefused) return refuse(std::string(who) + ": " + last_error());
       launch_user_terms(stream, R.num_cus, es->nsel, H.users, nrcmds, es->cut, es->ws.oid.get(), es->ws.ocnt.get(),
                         es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get());
-      launch_sum_in_user_order(stream, es->nsel, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      queue_sums(es, stream, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
     }
     st.path = kCand;
     finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
@@ -445,14 +620,16 @@ int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* mo
 namespace {
 // the checks both ranked calls share, then the scorer in rank mode on the matrix's stream: ranks and scores of
 // the eval set's test entries are in es->ws.rank / rscore when the stream has run.  SLIM_OK or a refusal.
+// evaluation: the call forms figures (model_evaluate_ranked), so the group rows on hand stop being the last ones.
 int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
-                    DeviceRowView& W, DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st) {
+                    DeviceRowView& W, DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st, bool evaluation) {
   if (const int32_t rc = check_evaluation(who, true, es, model, nullptr, W, R); rc != SLIM_OK) return rc;
   if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   (void)hipGetLastError();
   HIP_TRY(hipSetDevice(R.device));
   hipStream_t stream = static_cast<hipStream_t>(R.stream);
   es->ws.allocs = 0;
+  if (evaluation) es->group_ncut = 0;
   g_rank_prepass_ms = 0;
   st.path = kRank;
   if (es->nsel <= 0) return SLIM_OK;
@@ -476,7 +653,8 @@ int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* 
     DeviceRowView W;
     DeviceCsrView R;
     HistoryView H;
-    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st); rc != SLIM_OK) return rc;
+    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st, /*evaluation=*/false); rc != SLIM_OK)
+      return rc;
     if (es->nsel > 0) {
       hipStream_t stream = static_cast<hipStream_t>(R.stream);
       HIP_TRY(hipEventRecord(es->ev1, stream));
@@ -517,7 +695,8 @@ int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model,
     DeviceCsrView R;
     HistoryView H;
     const char* who = filter ? "SLIMGPU_ModelEvaluateRankedFiltered" : "SLIMGPU_ModelEvaluateRanked";
-    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st); rc != SLIM_OK) return rc;
+    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st, /*evaluation=*/true); rc != SLIM_OK)
+      return rc;
     if (es->nsel > 0) {
       hipStream_t stream = static_cast<hipStream_t>(R.stream);
       const size_t nterms = (size_t)SLIMGPU_MAX_CUTOFFS * (size_t)es->nsel;
@@ -531,7 +710,7 @@ int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model,
         for (int32_t k = 0; k < cut.n; ++k) cut.c[k] = cutoffs[k0 + k];
         launch_rank_terms(stream, R.num_cus, es->nsel, H.users, cut, es->ws.rank.get(), es->tbase(), es->tst.ptr.get(),
                           es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, d_terms);
-        launch_sum_in_user_order(stream, es->nsel, cut.n, d_terms, d_out->sums + k0);
+        queue_sums(es, stream, cut.n, d_terms, d_out->sums + k0, k0);
       }
     }
     finish_evaluation(es, R, W, H, ncutoffs, out, /*ranked=*/true, st, t_begin);

@@ -190,21 +190,34 @@ int32_t Py_SLIM_Learn(slim_t* trnhandle, int32_t* ioptions, double* doptions,
 // Py_SLIM_Mselect is this with no filter.  How the grid's pairs are learnt and evaluated, what each mode needs and what
 // is refused before the first solve is grid_eval.cpp's business; this is the loop over arrayl1 x arrayl2.
 // force_exposure / cells: Py_SLIM_MselectExposure (slim_gpu_exposure.h), slot 26 on whatever ioptions says.
+// groups (slim_gpu_groups.h; none: ngroups == 0): Py_SLIM_MselectGrouped, the best pairs chosen on select_group.
+struct MselectGroups {
+  int32_t ngroups = 0;
+  const int32_t* group_of_user = nullptr;
+  int32_t select_group = -1;
+  double* cells = nullptr;  // [nl1 * nl2][ngroups + 1][SLIMGPU_GROUP_CELL]
+};
 static int32_t mselect_impl(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
                             double* doptions, double* arrayl1, double* arrayl2, int32_t nl1,
                             int32_t nl2, double* bestl1HR, double* bestl2HR, double* bestHRHR,
                             double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR,
-                            double* bestARAR, slimgpu_filter_t* filter, bool force_exposure, double* cells) {
+                            double* bestARAR, slimgpu_filter_t* filter, bool force_exposure, double* cells,
+                            const MselectGroups& groups = MselectGroups()) {
   const slim_csr_t* trn = as_csr(trnhandle);
   const slim_csr_t* tst = as_csr(tsthandle);
   if (!trn || !tst || !trn->rowptr || !tst->rowptr) return SLIM_ERROR_INPUT;
   set_error("");
+  const int32_t ngroups = groups.ngroups;
   std::vector<int32_t> io(SLIM_NOPTIONS, -1);  // (a private copy: the caller's slot 26 stays as it is)
   if (ioptions) io.assign(ioptions, ioptions + SLIM_NOPTIONS);
   if (force_exposure) io[SLIM_OPTION_GPU_EVALEXPOSURE] = 1;
   slimgpu_grid grid(trn, tst, filter);
   int32_t rc = grid.open(io.data(), doptions, 0, nl1 * nl2);
+  if (rc == SLIM_OK && ngroups > 0) rc = grid.set_groups(ngroups, groups.group_of_user, groups.select_group);
   if (rc != SLIM_OK) return rc;
+  std::vector<EvalResult> rows((size_t)ngroups + 1);
+  std::vector<int32_t> members((size_t)ngroups + 1);
+  if (ngroups > 0) grid.group_members(members.data());
 
   std::printf("------------------------------------------------------------------\n");
   std::printf("SLIM, version %s (MI355X engine)\n", SLIM_VERSION);
@@ -225,7 +238,8 @@ static int32_t mselect_impl(slim_t* trnhandle, slim_t* tsthandle, int32_t* iopti
       slimgpu_grid_cell_t c;
       rc = grid.solve(arrayl1[a], arrayl2[b], &c);
       if (rc != SLIM_OK) break;
-      const double hr = c.metrics[0], arhr = c.metrics[3];
+      double hr = c.metrics[0], arhr = c.metrics[3];
+      int32_t nvalid = c.nvalid[0];
       std::printf("l1r: %.2le l2r: %.2le nnz: %7zd hr: %.4f hr_head: %.4f hr_tail: %.4f "
                   "arhr: %.4f time: %.2lf\n",
                   c.l1r, c.l2r, (ssize_t)c.nnz, hr, c.metrics[1], c.metrics[2], arhr, c.solve_seconds);
@@ -240,7 +254,27 @@ static int32_t mselect_impl(slim_t* trnhandle, slim_t* tsthandle, int32_t* iopti
           out[4] = expo.coverage; out[5] = expo.tail_share; out[6] = expo.gini; out[7] = expo.avg_pop;
         }
       }
-      if (c.nvalid[0] < 1) {  // pyapi.c:377-381
+      if (ngroups > 0) {  // (formed from the records of the pair's one scoring pass)
+        rc = grid.last_groups(rows.data());
+        if (rc != SLIM_OK) break;
+        for (int32_t g = 0; g <= ngroups; ++g) {
+          const EvalResult& r = rows[(size_t)g];
+          if (g < ngroups)
+            std::printf("  group %d: members: %d hr: %.4f hr_head: %.4f hr_tail: %.4f arhr: %.4f nvalid: %d\n", g,
+                        members[(size_t)g], r.hr, r.hr_head, r.hr_tail, r.arhr, r.nvalid);
+          if (groups.cells) {
+            double* out = groups.cells + (size_t)SLIMGPU_GROUP_CELL *
+                                             (((size_t)a * (size_t)nl2 + (size_t)b) * ((size_t)ngroups + 1) + (size_t)g);
+            out[0] = c.l1r; out[1] = c.l2r; out[2] = r.hr; out[3] = r.hr_head; out[4] = r.hr_tail; out[5] = r.arhr;
+            out[6] = r.nvalid; out[7] = r.nvalid_head; out[8] = r.nvalid_tail;
+          }
+        }
+        if (groups.select_group >= 0) {  // the pairs are chosen on this group's figures
+          const EvalResult& r = rows[(size_t)groups.select_group];
+          hr = r.hr; arhr = r.arhr; nvalid = r.nvalid;
+        }
+      }
+      if (nvalid < 1) {  // pyapi.c:377-381
         *bestl1HR = c.l1r;
         *bestl2HR = c.l2r;
         rc = SLIM_ERROR;
@@ -280,6 +314,38 @@ int32_t Py_SLIM_MselectExposure(slim_t* trnhandle, slim_t* tsthandle, int32_t* i
                                 double* bestARAR, slimgpu_filter_t* filter, double* cells) {
   return mselect_impl(trnhandle, tsthandle, ioptions, doptions, arrayl1, arrayl2, nl1, nl2, bestl1HR, bestl2HR,
                       bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR, bestARAR, filter, true, cells);
+}
+
+int32_t Py_SLIM_MselectGrouped(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions, double* doptions,
+                               double* arrayl1, double* arrayl2, int32_t nl1, int32_t nl2, double* bestl1HR,
+                               double* bestl2HR, double* bestHRHR, double* bestARHR, double* bestl1AR,
+                               double* bestl2AR, double* bestHRAR, double* bestARAR, slimgpu_filter_t* filter,
+                               int32_t ngroups, const int32_t* group_of_user, int32_t select_group, double* cells) {
+  // the group arguments are judged before anything is staged (slimgpu_grid::set_groups judges them again)
+  const char* who = "Py_SLIM_MselectGrouped";
+  const slim_csr_t* trn = as_csr(trnhandle);
+  const slim_csr_t* tst = as_csr(tsthandle);
+  if (!trn || !tst || !trn->rowptr || !tst->rowptr) return SLIM_ERROR_INPUT;
+  set_error("");
+  std::vector<int64_t> offsets((size_t)std::max(ngroups, 0) + 1);
+  if (!group_of_user) {
+    set_error(std::string(who) + ": bad arguments (a group for every user)");
+    return SLIM_ERROR_INPUT;
+  }
+  if (const int32_t rc = group_partition(who, 0, nullptr, std::min(trn->nrows, tst->nrows), ngroups, group_of_user,
+                                         nullptr, offsets.data());
+      rc != SLIM_OK)
+    return rc;
+  if (select_group < -1 || select_group >= ngroups) {
+    set_error(std::string(who) + ": select_group " + std::to_string(select_group) + " is outside [-1, " +
+              std::to_string(ngroups) + ")");
+    return SLIM_ERROR_INPUT;
+  }
+  MselectGroups groups;
+  groups.ngroups = ngroups; groups.group_of_user = group_of_user; groups.select_group = select_group;
+  groups.cells = cells;
+  return mselect_impl(trnhandle, tsthandle, ioptions, doptions, arrayl1, arrayl2, nl1, nl2, bestl1HR, bestl2HR,
+                      bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR, bestARAR, filter, false, nullptr, groups);
 }
 
 int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
@@ -888,6 +954,50 @@ int32_t SLIMGPU_ModelEvaluateExposure(slimgpu_evalset_t* es, const slimgpu_model
   if (rc != SLIM_OK) return rc;
   for (int32_t k = 0; k < ncutoffs; ++k) figures_out(ev[k], metrics + 4 * k, nvalid + 3 * k);
   return SLIM_OK;
+}
+
+// --------------------------------------------------- slim_gpu_groups.h ------
+
+int32_t SLIMGPU_EvalSetSetGroups(slimgpu_evalset_t* es, int32_t ngroups, const int32_t* group_of_user) {
+  set_error("");
+  return evalset_set_groups(es, ngroups, group_of_user);
+}
+
+int32_t SLIMGPU_EvalSetSetHistoryBands(slimgpu_evalset_t* es, int32_t nbounds, const int32_t* bounds) {
+  set_error("");
+  return evalset_set_history_bands(es, nbounds, bounds);
+}
+
+void SLIMGPU_EvalSetClearGroups(slimgpu_evalset_t* es) { evalset_clear_groups(es); }
+
+int32_t SLIMGPU_EvalSetGroupInfo(const slimgpu_evalset_t* es, int32_t* ngroups, int32_t* members) {
+  set_error("");
+  return evalset_group_info(es, ngroups, members);
+}
+
+int32_t SLIMGPU_EvalSetLastGroupFigures(slimgpu_evalset_t* es, int32_t ncutoffs, double* metrics, int32_t* nvalid) {
+  set_error("");
+  if (!metrics || !nvalid) {
+    set_error("SLIMGPU_EvalSetLastGroupFigures: bad arguments (an eval set, the outputs)");
+    return SLIM_ERROR_INPUT;
+  }
+  try {
+    // (sized for a number of cutoffs in range: any other differs from the evaluation's and is refused unwritten)
+    const int32_t ncut = std::min(std::max(ncutoffs, 1), SLIMGPU_MAX_RANK_CUTOFFS);
+    std::vector<EvalResult> rows(((size_t)evalset_groups(es) + 1) * (size_t)ncut);
+    if (const int32_t rc = evalset_group_figures(es, ncutoffs, rows.data()); rc != SLIM_OK) return rc;
+    for (size_t r = 0; r < rows.size(); ++r) figures_out(rows[r], metrics + 4 * r, nvalid + 3 * r);
+    return SLIM_OK;
+  } catch (const std::bad_alloc&) {
+    set_error("SLIMGPU_EvalSetLastGroupFigures: out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+}
+
+int32_t SLIMGPU_GroupPartition(int32_t nsel, const int32_t* users, int32_t nall, int32_t ngroups,
+                               const int32_t* group_of_user, int32_t* order, int64_t* offsets) {
+  set_error("");
+  return group_partition("SLIMGPU_GroupPartition", nsel, users, nall, ngroups, group_of_user, order, offsets);
 }
 
 // --------------------------------------------------- slim_gpu_sample.h ------

@@ -458,6 +458,30 @@ def list_exposure(ids, counts, ncols, cutoffs, pop=None, fmarker=None, lib=None)
     return E[:cut.size], _exposure_dicts(summ, cut)
 
 
+def _group_array(groups, what):
+    groups = np.asarray(groups)
+    if groups.ndim != 1 or groups.dtype.kind not in "iu":
+        raise ValueError("%s: one integer group per user" % what)
+    return np.ascontiguousarray(groups, np.int32)
+
+
+def group_partition(groups, ngroups, users=None, nsel=None, lib=None):
+    """SLIMGPU_GroupPartition, on the host: the definition of the per-group rows.  groups holds one group per user
+    (-1: none); the positions are `users` (ascending ids) or, with users None, the first nsel users (default: all).
+    Returns (order, offsets): order[offsets[g]:offsets[g + 1]] are the positions of group g, ascending."""
+    lib = lib or _lib.load()
+    groups = _group_array(groups, "group_partition")
+    users = None if users is None else np.ascontiguousarray(users, np.int32).ravel()
+    n = users.size if users is not None else (groups.size if nsel is None else int(nsel))
+    order = np.zeros(max(n, 1), np.int32)
+    offsets = np.zeros(max(int(ngroups), 0) + 1, np.int64)
+    st = lib.SLIMGPU_GroupPartition(n, _ptr(users), groups.size, int(ngroups), _ptr(groups), _ptr(order),
+                                    _ptr(offsets))
+    if st != SLIM_OK:
+        raise ValueError("SLIMGPU_GroupPartition failed (%d): %s" % (st, _lib.last_error()))
+    return order[:int(offsets[-1])], offsets
+
+
 def list_stats(lib=None):
     """Counters of the most recent PredictLists / ModelPredictLists / MatrixPredictLists on this thread."""
     st = _lib.ListStats()
@@ -587,6 +611,55 @@ class Evaluator(object):
         return [{"nrcmds": c, "hr": met[4 * k], "hr_head": met[4 * k + 1], "hr_tail": met[4 * k + 2],
                  "arhr": met[4 * k + 3], "nvalid": int(nv[3 * k]), "nvalid_head": int(nv[3 * k + 1]),
                  "nvalid_tail": int(nv[3 * k + 2])} for k, c in enumerate(self.cutoffs)]
+
+    def set_groups(self, groups, ngroups=None):
+        """SLIMGPU_EvalSetSetGroups: groups[u] in [0, ngroups) or -1 for every user row of the test matrix (by USER ID,
+        whatever the evaluated users are; ngroups None: the largest group + 1).  While set, every evaluate* call also
+        forms the figures of every group from its one scoring pass: group_figures()."""
+        groups = _group_array(groups, "set_groups")
+        if ngroups is None:
+            ngroups = int(groups.max()) + 1 if groups.size else 0
+        st = self._lib.SLIMGPU_EvalSetSetGroups(self.handle, int(ngroups), _ptr(groups))
+        if st != SLIM_OK:
+            raise ValueError("SLIMGPU_EvalSetSetGroups failed (%d): %s" % (st, _lib.last_error()))
+
+    def set_history_bands(self, bounds):
+        """SLIMGPU_EvalSetSetHistoryBands: the group of a user is the number of bounds (ascending, >= 1) its history
+        length reaches: len(bounds) + 1 groups, group 0 with the shortest histories."""
+        bounds = _group_array(np.atleast_1d(bounds), "set_history_bands")
+        st = self._lib.SLIMGPU_EvalSetSetHistoryBands(self.handle, bounds.size, _ptr(bounds))
+        if st != SLIM_OK:
+            raise ValueError("SLIMGPU_EvalSetSetHistoryBands failed (%d): %s" % (st, _lib.last_error()))
+
+    def clear_groups(self):
+        self._lib.SLIMGPU_EvalSetClearGroups(self.handle)
+
+    def group_members(self):
+        """The evaluated positions of every group, then all of them (SLIMGPU_EvalSetGroupInfo)."""
+        n = C.c_int32(0)
+        if self._lib.SLIMGPU_EvalSetGroupInfo(self.handle, C.byref(n), None) != SLIM_OK:
+            raise RuntimeError("SLIMGPU_EvalSetGroupInfo failed: %s" % _lib.last_error())
+        members = np.zeros(n.value + 1, np.int32)
+        self._lib.SLIMGPU_EvalSetGroupInfo(self.handle, C.byref(n), _ptr(members))
+        return members
+
+    def group_figures(self, cutoffs=None):
+        """SLIMGPU_EvalSetLastGroupFigures: the rows of the most recent evaluate* call per group -- one list per group,
+        everybody last, of the dicts evaluate_at() returns plus "members".  cutoffs: those of the call when it was
+        evaluate_ranked (default: the eval set's; evaluate() has them all)."""
+        cut = self.cutoffs if cutoffs is None else tuple(int(c) for c in np.atleast_1d(cutoffs))
+        members = self.group_members()
+        n, rows = len(cut), members.size
+        met = np.zeros(4 * max(n, 1) * rows, np.float64)
+        nv = np.zeros(3 * max(n, 1) * rows, np.int32)
+        st = self._lib.SLIMGPU_EvalSetLastGroupFigures(self.handle, n, _ptr(met), _ptr(nv))
+        if st != SLIM_OK:
+            raise RuntimeError("SLIMGPU_EvalSetLastGroupFigures failed (%d): %s" % (st, _lib.last_error()))
+        met, nv = met.reshape(rows, -1, 4), nv.reshape(rows, -1, 3)
+        return [[{"nrcmds": c, "hr": met[g, k, 0], "hr_head": met[g, k, 1], "hr_tail": met[g, k, 2],
+                  "arhr": met[g, k, 3], "nvalid": int(nv[g, k, 0]), "nvalid_head": int(nv[g, k, 1]),
+                  "nvalid_tail": int(nv[g, k, 2]), "members": int(members[g])} for k, c in enumerate(cut)]
+                for g in range(rows)]
 
     def sample_candidates(self, nnegs, seed=1, weights=None):
         """SLIMGPU_EvalSetSampleCandidates: the 1-vs-k CandidateSet of this eval set's users, made on the device --

@@ -286,6 +286,46 @@ def _candidate_filter(lib, item2id, nitems, ncols, data, allowed_items, blocked_
     return ItemFilter(ncols, allowed, blocked, rows, lib=lib)
 
 
+def _user_groups(lib, trndata, groups, history_bands):
+    """(group per user row of trndata as int32, ngroups) of mselect's groups / history_bands; (None, 0) without."""
+    if groups is not None and history_bands is not None:
+        raise TypeError("Please provide at most one of groups and history_bands.")
+    if groups is None and history_bands is None:
+        return None, 0
+    if history_bands is not None:
+        bounds = np.asarray(history_bands)
+        if (bounds.ndim != 1 or bounds.size < 1 or bounds.dtype.kind not in "iu" or bounds.min() < 1 or
+                (np.diff(bounds) <= 0).any() or bounds.size >= _lib.MAX_GROUPS):
+            raise TypeError("history_bands must be ascending integers, each at least 1.")
+        nnz = C.c_int(0)
+        lib.Py_csr_stat(trndata.handle, C.byref(nnz))
+        ptr = np.zeros(trndata.nUsers + 1, dtype=np.int32)
+        ind = np.zeros(max(nnz.value, 1), dtype=np.int32)
+        val = np.ones(max(nnz.value, 1), dtype=np.float32)
+        lib.Py_csr_export(trndata.handle, ptr, ind, val)
+        return (np.ascontiguousarray(np.searchsorted(bounds, np.diff(ptr), side="right"), np.int32),
+                int(bounds.size) + 1)
+    if isinstance(groups, dict):
+        out = np.full(trndata.nUsers, -1, np.int32)
+        known = trndata.user2id
+        for user, g in groups.items():
+            if not isinstance(g, (int, np.integer)):
+                raise TypeError("groups must map user ids to integer groups.")
+            row = known.get(user, -1) if isinstance(known, dict) else (user if 0 <= user < trndata.nUsers else -1)
+            if row >= 0:
+                out[row] = g
+    else:
+        out = np.asarray(groups)
+        if out.ndim != 1 or out.dtype.kind not in "iu" or out.size != trndata.nUsers:
+            raise TypeError("groups must hold one integer group per user row of trndata (%d)." % trndata.nUsers)
+        out = np.ascontiguousarray(out, np.int32)
+    if out.size and (out.min() < -1 or out.max() >= _lib.MAX_GROUPS):
+        raise TypeError("a group must be -1 (none) or 0 to %d." % (_lib.MAX_GROUPS - 1))
+    if not out.size or out.max() < 0:
+        raise TypeError("groups puts no user into a group.")
+    return out, int(out.max()) + 1
+
+
 # ---------------------------------------------------------------------------
 # SLIM
 # ---------------------------------------------------------------------------
@@ -326,8 +366,19 @@ class SLIM(object):
         print("Learning takes %.3f secs." % elapsed)
 
     def mselect(self, params, trndata, tstdata, arrayl1, arrayl2, nrcmds, allowed_items=None, blocked_items=None,
-                exclude=None, nnegs=0, negseed=1, negpop=False, exposure=False):
-        """exposure=True (or params["gpu_evalexposure"] = 1): besides HR / ARHR every pair reports what its lists show
+                exclude=None, nnegs=0, negseed=1, negpop=False, exposure=False, groups=None, history_bands=None,
+                select_group=None):
+        """groups / history_bands (at most one; include/slim_gpu_groups.h): every pair is also evaluated per user group,
+        from the same scoring pass.  groups: an integer array over trndata's user rows (0 .. ngroups-1, or -1 for no
+        group), or a dict {ORIGINAL user id: group} mapped through trndata's user map -- users the map does not know
+        are ignored, users the dict does not name are in no group.  history_bands: ascending bounds >= 1; the group of
+        a user is the number of bounds the length of its training row reaches.  One more line is printed per group
+        and the table stays on the object as last_groups: one list per pair, in the order solved, of one dict per
+        group and a last one for everybody (group -1) with l1, l2, hr, hr_head, hr_tail, arhr, nvalid, nvalid_head,
+        nvalid_tail.  select_group=g: the best pairs are chosen on group g's figures.  It needs the evaluation in HBM,
+        combines with the filter arguments, nnegs and params["gpu_evalexposure"], and not with exposure=True (the
+        exposure table is everybody's).
+        exposure=True (or params["gpu_evalexposure"] = 1): besides HR / ARHR every pair reports what its lists show
         (include/slim_gpu_exposure.h) -- catalogue coverage, tail share, Gini and mean popularity of the top-nrcmds
         lists, counted on the device where the evaluation makes them.  One more line is printed per pair and the
         table stays on the object as last_exposure: one dict per pair, in the order solved, with l1, l2, hr, arhr,
@@ -351,6 +402,14 @@ class SLIM(object):
         assert type(tstdata) == SLIMatrix, "tstdata must be a SLIMatrix object."
         if allowed_items is not None and blocked_items is not None:
             raise TypeError("Please provide at most one of allowed_items and blocked_items.")
+        group_of_user, ngroups = _user_groups(self._lib, trndata, groups, history_bands)
+        if group_of_user is None and select_group is not None:
+            raise TypeError("select_group chooses on a user group: give groups or history_bands.")
+        if group_of_user is not None and exposure:
+            raise TypeError("exposure=True does not combine with groups: the exposure table is everybody's.")
+        if select_group is not None and not (isinstance(select_group, (int, np.integer)) and
+                                             0 <= select_group < ngroups):
+            raise TypeError("select_group must be a group, 0 to %d." % (ngroups - 1))
         assert type(arrayl1) in [list, np.ndarray], "Please provide a list of l1 values."
         assert type(arrayl2) in [list, np.ndarray], "Please provide a list of l2 values."
         view = _prepare(params)
@@ -371,8 +430,23 @@ class SLIM(object):
                 len(arrayl1), len(arrayl2)) + tuple(C.byref(b) for b in best)
         t0 = time.time()
         self.last_exposure = None
+        self.last_groups = None
         cells = np.zeros((len(arrayl1) * len(arrayl2), _lib.EXPOSURE_CELL), np.float64) if exposure else None
-        if exposure and allowed_items is None and blocked_items is None and exclude is None:
+        if group_of_user is not None:
+            cells = np.zeros((len(arrayl1) * len(arrayl2), ngroups + 1, _lib.GROUP_CELL), np.float64)
+            flt = None
+            if not (allowed_items is None and blocked_items is None and exclude is None):
+                ncols = max(int(C.cast(trndata.handle, C.POINTER(_lib.CsrView)).contents.ncols), 1)
+                flt = _candidate_filter(self._lib, trndata.item2id, trndata.nItems, ncols, trndata, allowed_items,
+                                        blocked_items, exclude)
+            try:
+                rc = self._lib.Py_SLIM_MselectGrouped(*(grid + (
+                    None if flt is None else flt.handle, ngroups, group_of_user.ctypes.data_as(C.c_void_p),
+                    -1 if select_group is None else int(select_group), cells.ctypes.data_as(C.c_void_p))))
+            finally:
+                if flt is not None:
+                    flt.close()
+        elif exposure and allowed_items is None and blocked_items is None and exclude is None:
             rc = self._lib.Py_SLIM_MselectExposure(*(grid + (None, cells.ctypes.data_as(C.c_void_p))))
         elif allowed_items is None and blocked_items is None and exclude is None:
             rc = self._lib.Py_SLIM_Mselect(*grid)
@@ -399,6 +473,12 @@ class SLIM(object):
         print("The best AR is achieved by, l1: %.4f, l2:%.4f, HR:%.4f, AR:%.4f."
               % (l1ar, l2ar, hrar, arar))
         self.mselect_result = dict(bestHR=(l1hr, l2hr, hrhr, arhr), bestAR=(l1ar, l2ar, hrar, arar))
+        if group_of_user is not None:
+            names = ("l1", "l2", "hr", "hr_head", "hr_tail", "arhr")
+            counts = ("nvalid", "nvalid_head", "nvalid_tail")
+            self.last_groups = [[dict(dict(zip(names, (float(v) for v in row[:6]))),
+                                      group=g if g < ngroups else -1, **dict(zip(counts, (int(v) for v in row[6:]))))
+                                 for g, row in enumerate(pair)] for pair in cells]
         if exposure:
             names = ("l1", "l2", "hr", "arhr", "coverage", "tail_share", "gini", "avg_pop")
             self.last_exposure = [dict(zip(names, (float(v) for v in row))) for row in cells]
