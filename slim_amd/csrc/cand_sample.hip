@@ -15,12 +15,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 
+#include "call_frame.hpp"
 #include "host_csr.hpp"
-#include "host_stage.hpp"
-#include "scorer.hpp"
 
 namespace slimamd {
 namespace {
@@ -407,24 +407,19 @@ slimgpu_candset* sample_on_device(const char* name, slimgpu_evalset_t* es, int32
                "and takes at most " + std::to_string(SLIMGPU_SAMPLE_MAX_NCOLS) + " (SLIMGPU_CandSetSample" + (weighted ? "Weighted" : "") + " serves)");
   uint64_t T = 0;  // the weights' sum
   std::vector<uint32_t> popularity;
-  try {
+  slimgpu_candset* cs = nullptr;
+  *status = guarded(name, [&]() -> int32_t {
     if (weighted && !weights) {  // the column counts of the resident matrix, from its column view's pointer
       std::vector<int64_t> cp((size_t)V.ncols + 1, 0);
       if (matrix_get_column_view(V.mat, cp.data(), nullptr, nullptr, nullptr) != SLIM_OK)
-        return bad("the resident matrix has no column view");
+        return refuse(who + "the resident matrix has no column view");
       popularity.resize((size_t)V.ncols);
       for (int32_t i = 0; i < V.ncols; ++i) popularity[i] = (uint32_t)(cp[(size_t)i + 1] - cp[i]);
       weights = popularity.data();
     }
-  } catch (const std::bad_alloc&) {
-    set_error(who + "out of host memory");
-    *status = SLIM_ERROR_MEMORY;
-    return nullptr;
-  }
-  if (weighted)
-    for (int32_t i = 0; i < V.ncols; ++i) T += weights[i];
-  if (weighted && T == 0) return bad("the weights sum to 0 (T = 0): nothing can be drawn");
-  try {
+    if (weighted)
+      for (int32_t i = 0; i < V.ncols; ++i) T += weights[i];
+    if (weighted && T == 0) return refuse(who + "the weights sum to 0 (T = 0): nothing can be drawn");
     (void)hipGetLastError();
     HIP_TRY(hipSetDevice(V.device));
     hipStream_t stream = V.stream;
@@ -496,27 +491,17 @@ slimgpu_candset* sample_on_device(const char* name, slimgpu_evalset_t* es, int32
                        nsel, groups, lds, V.ncols, nnegs, dense ? "sort records" : "no sort records");
       }
       bool timed = false;
-      hipEvent_t ev0 = nullptr, ev1 = nullptr;  // (the weighted kernel's own time, for SLIMGPU_LastSampleKernelMs)
+      // the weighted kernel's own time, for SLIMGPU_LastSampleKernelMs: a record that fails leaves the call untimed
+      std::optional<EventPair> ev;
       if (weighted) {
-        HIP_TRY(hipEventCreate(&ev0));
-        if (hipEventCreate(&ev1) != hipSuccess) {
-          (void)hipEventDestroy(ev0);
-          throw HipFail{hipErrorOutOfMemory, "hipEventCreate"};
-        }
+        ev.emplace();
         g_weighted_kernel_ms = 0.0;  // (never the figure of an earlier call: 0 when this one cannot be timed)
-        timed = hipEventRecord(ev0, stream) == hipSuccess;
+        timed = hipEventRecord(ev->ev0, stream) == hipSuccess;
         hipLaunchKernelGGL(k_sample_weighted, dim3(groups), dim3(64), lds, stream, A, C, T);
-        timed = hipEventRecord(ev1, stream) == hipSuccess && timed;
+        timed = hipEventRecord(ev->ev1, stream) == hipSuccess && timed;
       } else {
         hipLaunchKernelGGL(k_sample_negatives, dim3(groups), dim3(64), lds, stream, A);
       }
-      struct Events {  // destroyed on every way out
-        hipEvent_t a, b;
-        ~Events() {
-          if (a) (void)hipEventDestroy(a);
-          if (b) (void)hipEventDestroy(b);
-        }
-      } events{ev0, ev1};
       HIP_TRY(hipGetLastError());
       const unsigned flat = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)nsel + 255) / 256, (int64_t)V.num_cus * 16));
       HIP_TRY(hipMemsetAsync(len.get(), 0, sizeof(int64_t) * ((size_t)nall + 1), stream));
@@ -543,24 +528,16 @@ slimgpu_candset* sample_on_device(const char* name, slimgpu_evalset_t* es, int32
       HIP_TRY(hipStreamSynchronize(stream));  // (negs and nneg go with this block)
       if (weighted && timed) {
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_weighted_kernel_ms = ms;
+        if (hipEventElapsedTime(&ms, ev->ev0, ev->ev1) == hipSuccess) g_weighted_kernel_ms = ms;
       }
     } else {
       d_cind = DeviceBuffer<int32_t>(0);
       HIP_TRY(hipMemsetAsync(d_cptr.get(), 0, sizeof(int64_t) * ((size_t)nall + 1), stream));
     }
-    slimgpu_candset* cs = candset_adopt(V.ncols, std::move(h_cptr), std::move(d_cptr), std::move(d_cind), V.device,
-                                        V.num_cus, stream);
-    *status = SLIM_OK;
-    return cs;
-  } catch (const HipFail& e) {
-    *status = hip_failure(name, e);
-    return nullptr;
-  } catch (const std::bad_alloc&) {
-    set_error(who + "out of host memory");
-    *status = SLIM_ERROR_MEMORY;
-    return nullptr;
-  }
+    cs = candset_adopt(V.ncols, std::move(h_cptr), std::move(d_cptr), std::move(d_cind), V.device, V.num_cus, stream);
+    return SLIM_OK;
+  });
+  return cs;
 }
 }  // namespace
 

@@ -12,13 +12,13 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "call_frame.hpp"
 #include "host_csr.hpp"
-#include "host_stage.hpp"
-#include "scorer.hpp"
 
 struct slimgpu_candset {
   int32_t ncols = 0, nusers = 0;
@@ -102,19 +102,16 @@ slimgpu_candset* candset_create(int32_t ncols, int32_t nusers, const int64_t* cp
     if (cptr[u + 1] - cptr[u] > INT32_MAX) return bad("the row of user " + std::to_string(u) + " has 2^31 entries or more");
   }
   if (cptr[nusers] > 0 && !cind) return bad("candidate rows without cind");
-  try {
-    slimgpu_candset* cs = new slimgpu_candset;
+  std::unique_ptr<slimgpu_candset> cs;
+  *status = guarded("SLIMGPU_CandSetCreate", [&]() -> int32_t {
+    cs.reset(new slimgpu_candset);
     cs->ncols = ncols;
     cs->nusers = nusers;
     cs->cptr.assign(cptr, cptr + nusers + 1);
     cs->cind.assign(cind, cind + cptr[nusers]);
-    *status = SLIM_OK;
-    return cs;
-  } catch (const std::bad_alloc&) {
-    set_error("SLIMGPU_CandSetCreate: out of host memory");
-    *status = SLIM_ERROR_MEMORY;
-    return nullptr;
-  }
+    return SLIM_OK;
+  });
+  return *status == SLIM_OK ? cs.release() : nullptr;
 }
 
 void candset_free(slimgpu_candset* cs) { delete cs; }
@@ -252,21 +249,16 @@ CandidateRows candset_on_device(slimgpu_candset* cs, int device, int num_cus, hi
 
 slimgpu_candset* candset_adopt(int32_t ncols, std::vector<int64_t>&& h_cptr, DeviceBuffer<int64_t>&& d_cptr,
                                DeviceBuffer<int32_t>&& d_cind, int device, int num_cus, hipStream_t stream) {
-  slimgpu_candset* cs = new slimgpu_candset;
-  try {
-    cs->ncols = ncols;
-    cs->nusers = (int32_t)h_cptr.size() - 1;
-    cs->cptr = std::move(h_cptr);
-    cs->host_ids = cs->cptr[cs->nusers] == 0;
-    cs->d_cptr = std::move(d_cptr);
-    cs->d_cind = std::move(d_cind);
-    candset_index(cs, num_cus, stream, nullptr);
-    cs->device = device;
-    return cs;
-  } catch (...) {
-    delete cs;
-    throw;
-  }
+  std::unique_ptr<slimgpu_candset> cs(new slimgpu_candset);  // (a failure passes through and frees it)
+  cs->ncols = ncols;
+  cs->nusers = (int32_t)h_cptr.size() - 1;
+  cs->cptr = std::move(h_cptr);
+  cs->host_ids = cs->cptr[cs->nusers] == 0;
+  cs->d_cptr = std::move(d_cptr);
+  cs->d_cind = std::move(d_cind);
+  candset_index(cs.get(), num_cus, stream, nullptr);
+  cs->device = device;
+  return cs.release();
 }
 
 void candset_need_ids(slimgpu_candset* cs) {
@@ -283,15 +275,10 @@ void candset_need_ids(slimgpu_candset* cs) {
 }
 
 int32_t candset_fetch_ids(const char* who, slimgpu_candset* cs) {
-  try {
+  return guarded(who, [&]() -> int32_t {
     candset_need_ids(cs);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 
 ExplainWorkspace& candset_explain_workspace(slimgpu_candset* cs) { return cs->why; }
@@ -344,36 +331,19 @@ int32_t score_rows(const char* who, const DeviceRowView& W, const HistoryView& H
                    slimgpu_candset* cs, int device, int num_cus, hipStream_t stream, ScorerWorkspace& ws,
                    int32_t nrcmds, float* slot_scores, int32_t* output, float* scores, int32_t* counts,
                    slimgpu_eval_stats_t& st) {
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t rc = SLIM_OK;
-  try {
-    const CandidateRows rows = candset_on_device(cs, device, num_cus, stream, &ws.allocs, &st.h2d_bytes);
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, stream));
-    st.path = queue_candidates(W, H, rows, nrcmds, num_cus, stream, ws);
-    if (st.path == kRefused) {
-      set_error(std::string(who) + ": " + std::string(last_error()));
-      rc = SLIM_ERROR_INPUT;
-    } else {
-      HIP_TRY(hipEventRecord(ev1, stream));
-      size_t down = 0;
-      if (slot_scores) down += fetch_slot_scores(ws, cs, H.nusers, h_users, stream, slot_scores);
-      if (nrcmds > 0) down += fetch_lists(ws, H.nusers, nrcmds, stream, output, scores, counts);
-      HIP_TRY(hipStreamSynchronize(stream));
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-      st.kernel_ms = ms;
-      st.d2h_bytes += (int64_t)down;
-    }
-  } catch (...) {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    throw;
-  }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  return rc;
+  const CandidateRows rows = candset_on_device(cs, device, num_cus, stream, &ws.allocs, &st.h2d_bytes);
+  EventPair ev;
+  ev.begin(stream);
+  st.path = queue_candidates(W, H, rows, nrcmds, num_cus, stream, ws);
+  if (st.path == kRefused) return refuse(std::string(who) + ": " + std::string(last_error()));
+  ev.end(stream);
+  size_t down = 0;
+  if (slot_scores) down += fetch_slot_scores(ws, cs, H.nusers, h_users, stream, slot_scores);
+  if (nrcmds > 0) down += fetch_lists(ws, H.nusers, nrcmds, stream, output, scores, counts);
+  HIP_TRY(hipStreamSynchronize(stream));
+  st.kernel_ms = ev.ms();
+  st.d2h_bytes += (int64_t)down;
+  return SLIM_OK;
 }
 }  // namespace
 
@@ -387,39 +357,22 @@ int32_t score_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_can
     return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    int ndev = 0, device = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
-    HIP_TRY(hipGetDevice(&device));
+  return guarded(who, [&]() -> int32_t {
+    const int device = open_current_device();
     const int num_cus = cu_count();
     if (nusers > 0) {
-      const StagedCsr w = stage_csr(W, W->nrows, /*values=*/true, /*stream=*/nullptr);
-      const StagedCsr h = stage_csr(trn, nusers, /*values=*/true, /*stream=*/nullptr);
-      DeviceRowView V;
-      V.nrows = W->nrows; V.ncols = W->ncols; V.nnz = w.nnz; V.max_row = w.max_row;
-      V.d_ptr = w.ptr.get(); V.d_ind = w.ind.get(); V.d_val = w.val.get();
-      V.rows_sorted = V.nnz > 0 && rows_ascend_strictly(num_cus, V.nrows, V.d_ptr, V.d_ind);
-      HistoryView H;
-      H.nusers = nusers; H.max_hist = h.max_row;
-      H.ptr = h.ptr.get(); H.ind = h.ind.get(); H.val = h.val.get();
+      const StagedPair P = stage_pair(W, trn, num_cus);
       ScorerWorkspace ws;
-      const int32_t rc = score_rows(who, V, H, nullptr, cs, device, num_cus, /*stream=*/nullptr, ws, nrcmds,
+      const int32_t rc = score_rows(who, P.W, P.H, nullptr, cs, device, num_cus, /*stream=*/nullptr, ws, nrcmds,
                                     slot_scores, output, scores, counts, st);
       if (rc != SLIM_OK) return rc;
       st.device_allocs = ws.allocs;
-      st.w_rows_read = h.nnz;
+      st.w_rows_read = P.h.nnz;
     }
     st.total_ms = ms_since(t_begin);
     last_eval_stats() = st;
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 
 int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs, int32_t nusers,
@@ -436,24 +389,13 @@ int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* ma
   if (const int32_t rc = candset_check(who, cs, W.ncols, nu, users, nrcmds, output, scores); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  return guarded(who, [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
     if (nu > 0) {
       ScorerWorkspace ws;
-      DeviceBuffer<int32_t> d_users;
-      ++ws.allocs;  // (the longest history's length)
-      if (users) {
-        d_users = DeviceBuffer<int32_t>((size_t)nu);
-        ++ws.allocs;
-        HIP_TRY(hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)nu, hipMemcpyHostToDevice, stream));
-        st.h2d_bytes += (int64_t)(sizeof(int32_t) * (size_t)nu);
-      }
-      const HistoryView H = resident_history(R, nu, d_users.get(),
-                                             longest_history(stream, R.num_cus, nu, d_users.get(), R.d_ptr, nullptr));
-      const int32_t rc = score_rows(who, W, H, users, cs, R.device, R.num_cus, stream, ws, nrcmds, slot_scores, output,
-                                    scores, counts, st);
+      const StagedUsers U = stage_users(R, nu, users, stream, &ws.allocs, &st.h2d_bytes);
+      const int32_t rc = score_rows(who, W, U.H, users, cs, R.device, R.num_cus, stream, ws, nrcmds, slot_scores,
+                                    output, scores, counts, st);
       if (rc != SLIM_OK) return rc;
       st.d2h_bytes += (int64_t)sizeof(int32_t);
       st.device_allocs = ws.allocs;
@@ -462,11 +404,6 @@ int32_t matrix_score_candidates(const slimgpu_model* model, slimgpu_matrix_t* ma
     st.total_ms = ms_since(t_begin);
     last_eval_stats() = st;
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 }  // namespace slimamd

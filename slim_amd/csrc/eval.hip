@@ -19,11 +19,11 @@
 #include <string>
 #include <vector>
 
+#include "call_frame.hpp"
 #include "engine.hpp"
 #include "eval_terms.hpp"
 #include "hip_check.hpp"
 #include "host_csr.hpp"
-#include "host_stage.hpp"
 
 namespace slimamd {
 
@@ -381,7 +381,7 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
   nusers = std::min(nusers, tst->nrows);
   *out = EvalResult();
   if (nusers <= 0) return SLIM_OK;
-  try {
+  return guarded("SLIMGPU_Evaluate", [&]() -> int32_t {
     (void)hipGetLastError();
     DeviceBuffer<int32_t> d_lists((size_t)nusers * nrcmds), d_counts((size_t)nusers),
         d_fm((size_t)std::max(fm_ncols, 1));
@@ -397,19 +397,9 @@ int32_t evaluate_device(int32_t nusers, int32_t nrcmds, const int32_t* lists, co
     launch_sum_in_user_order(nullptr, nusers, 1, d_terms.get(), d_sums.get());
     EvalSums h;
     HIP_TRY(hipMemcpy(&h, d_sums.get(), sizeof(h), hipMemcpyDeviceToHost));
-    const float* f = h.f;
-    const int32_t* n = h.n;
-    out->nvalid = n[0];
-    out->nvalid_head = n[1];
-    out->nvalid_tail = n[2];
-    out->hr = n[0] > 0 ? f[0] / n[0] : 0;
-    out->hr_head = n[1] > 0 ? f[1] / n[1] : 0;
-    out->hr_tail = n[2] > 0 ? f[2] / n[2] : 0;
-    out->arhr = n[0] > 0 ? f[3] / n[0] : 0;
+    *out = result_of(h);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure("SLIMGPU_Evaluate", e);
-  }
+  });
 }
 
 int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds,
@@ -422,21 +412,17 @@ int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t
   }
   const int32_t nusers = hist->nrows;
   if (nusers <= 0) return SLIM_ERROR;
-  try {
+  return guarded("SLIMGPU_Predict1vsK", [&]() -> int32_t {
     (void)hipGetLastError();
-    const StagedCsr w = stage_csr(W, W->nrows, /*values=*/true, /*stream=*/nullptr);
-    const StagedCsr h = stage_csr(hist, nusers, /*values=*/true, /*stream=*/nullptr);
+    const int cus = cu_count();
+    const StagedPair P = stage_pair(W, hist, cus);  // (a model without entries has no row out of order)
+    if (P.W.nnz > 0 && !P.W.rows_sorted) return refuse("SLIMGPU_Predict1vsK: model rows are not ascending by item id");
     DeviceBuffer<int32_t> d_neg((size_t)nusers * nnegs), d_oid((size_t)nusers * nrcmds);
     DeviceBuffer<float> d_osc((size_t)nusers * nrcmds);
     upload(d_neg, negitems, (size_t)nusers * nnegs);
-    const int cus = cu_count();
-    if (!rows_ascend_strictly(cus, W->nrows, w.ptr.get(), w.ind.get())) {
-      set_error("SLIMGPU_Predict1vsK: model rows are not ascending by item id");
-      return SLIM_ERROR_INPUT;
-    }
     hipLaunchKernelGGL(k_topn_1vsk, dim3(std::max(1, std::min(nusers, cus * 16))), dim3(64), 0, 0,
-                       nusers, W->nrows, W->ncols, nrcmds, nnegs, w.ptr.get(), w.ind.get(), w.val.get(), h.ptr.get(),
-                       h.ind.get(), h.val.get(), d_neg.get(), d_oid.get(), d_osc.get());
+                       nusers, W->nrows, W->ncols, nrcmds, nnegs, P.W.d_ptr, P.W.d_ind, P.W.d_val, P.H.ptr,
+                       P.H.ind, P.H.val, d_neg.get(), d_oid.get(), d_osc.get());
     HIP_TRY(hipGetLastError());
     const int32_t n = std::min(nnegs, nrcmds);
     std::vector<int32_t> h_id((size_t)nusers * nrcmds);
@@ -449,9 +435,7 @@ int32_t predict_1vsk_device(const slim_csr_t* W, const slim_csr_t* hist, int32_t
         scores[(int64_t)u * nrcmds + r] = h_sc[(size_t)u * nrcmds + r];
       }
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure("SLIMGPU_Predict1vsK", e);
-  }
+  });
 }
 
 }  // namespace slimamd

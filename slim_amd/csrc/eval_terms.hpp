@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "../../include/slim_gpu_eval.h"
+#include "host_csr.hpp"
 
 namespace slimamd {
 
@@ -57,6 +58,14 @@ struct EvalSums {       // the accumulators of one cutoff
   int32_t n[3];         // nvalid, nvalid_head, nvalid_tail
   int32_t pad;
 };
+// the figures of one cutoff's accumulators
+inline EvalResult result_of(const EvalSums& s) {
+  EvalResult r;
+  r.nvalid = s.n[0]; r.nvalid_head = s.n[1]; r.nvalid_tail = s.n[2];
+  r.hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0; r.arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
+  r.hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0; r.hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
+  return r;
+}
 
 // the hits of one user, walked in rank order (both scorers' epilogues)
 struct HitWalk {

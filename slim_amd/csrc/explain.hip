@@ -15,10 +15,9 @@
 #include <string>
 #include <vector>
 
+#include "call_frame.hpp"
 #include "explain_kernels.hpp"
 #include "host_csr.hpp"
-#include "host_stage.hpp"
-#include "scorer.hpp"
 
 namespace slimamd {
 namespace {
@@ -58,104 +57,91 @@ int32_t explain_rows(const char* who, const DeviceRowView& W, HistoryView H, con
     entries += cptr[u + 1] - cptr[u];
   }
   const bool places = why_items != nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t rc = SLIM_OK;
-  try {
-    int set_allocs = 0;
-    const CandidateRows rows = candset_on_device(cs, device, num_cus, stream, &set_allocs, &st.h2d_bytes);
-    ExplainWorkspace& E = candset_explain_workspace(cs);
-    E.allocs = 0;
-    // no slicing: the outputs of all selected rows stand in device memory at once
-    const size_t want = (size_t)entries * (places ? 8 * (size_t)nwhy + 4 : 4);
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (want > (free_b + E.held()) / 2) {
-      set_error(w + ": the outputs of " + std::to_string(entries) + " candidate entries at nwhy = " +
-                std::to_string(nwhy) + " need " + std::to_string(want) + " bytes of device memory, more than half of "
-                "the " + std::to_string(free_b + E.held()) + " that are free: pass user sub-lists");
-      return SLIM_ERROR_MEMORY;
-    }
-    ExplainArgs A = {};
-    A.wrows = W.nrows; A.wptr = W.d_ptr; A.wind = W.d_ind; A.wval = W.d_val;
-    A.npos = nsel; A.hptr = H.ptr; A.hind = H.ind; A.hval = H.val;
-    A.cptr = rows.cptr; A.lptr = rows.lptr; A.pairs = rows.pairs;
-    A.nwhy = nwhy;
-    A.stage = stage_entries();
-    if (h_users) {
-      int32_t* d_users = E.need(E.users, (size_t)nsel);
-      HIP_TRY(hipMemcpyAsync(d_users, h_users, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
-      st.h2d_bytes += (int64_t)(sizeof(int32_t) * (size_t)nsel);
-      int64_t* d_obase = E.need(E.obase, (size_t)nsel + 1);
-      hipLaunchKernelGGL(k_explain_base, dim3(1), dim3(256), 0, stream, nsel, d_users, rows.cptr, d_obase);
-      HIP_TRY(hipGetLastError());
-      A.users = d_users;
-      A.obase = d_obase;
-    }
-    A.support = E.need(E.support, (size_t)entries);
-    if (places) {
-      A.items = E.need(E.items, (size_t)entries * nwhy);
-      A.terms = E.need(E.terms, (size_t)entries * nwhy);
-    }
-    HIP_TRY(hipMemsetAsync(A.support, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(entries, 1), stream));
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, stream));
-    if (nsel > 0 && entries > 0) {
-      const dim3 grid((unsigned)std::min<int64_t>(nsel, (int64_t)num_cus * 8)), block(64 * kExplainWaves);
-      const size_t lds = sizeof(int4) * (size_t)A.stage;
-      if (std::getenv("SLIM_GPU_TRACE"))
-        std::fprintf(stderr, "[trace] k_explain<%d>: %d positions, %d workgroups, %d staged entries, nwhy %d, %s\n",
-                     nwhy > 4 || form16_forced() ? 16 : 4, nsel, (int)grid.x, A.stage, nwhy,
-                     h_users ? "a user list" : "all users");
-      if (nwhy > 4 || form16_forced())
-        hipLaunchKernelGGL(k_explain<16>, grid, block, lds, stream, A);
-      else
-        hipLaunchKernelGGL(k_explain<4>, grid, block, lds, stream, A);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(ev1, stream));
-    size_t down = 0;
-    auto fetch = [&](auto& image, const auto* d, size_t n) {
-      if (image.size() < n) image.resize(n);
-      if (n == 0) return;
-      HIP_TRY(hipMemcpyAsync(image.data(), d, sizeof(*d) * n, hipMemcpyDeviceToHost, stream));
-      down += sizeof(*d) * n;
-    };
-    fetch(E.h_support, A.support, (size_t)entries);
-    if (places) {
-      fetch(E.h_items, A.items, (size_t)entries * nwhy);
-      fetch(E.h_terms, A.terms, (size_t)entries * nwhy);
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    st.kernel_ms = ms;
-    st.d2h_bytes += (int64_t)down;
-    st.path = kExplain;
-    st.device_allocs = set_allocs + E.allocs;
-    // out of the images: the rows of the positions stand side by side there, in the caller's arrays at cptr[user]
-    int64_t ob = 0;
-    for (int32_t q = 0; q < nsel; ++q) {
-      const int32_t u = h_users ? h_users[q] : q;
-      const int64_t e0 = cptr[u], len = cptr[u + 1] - e0;
-      for (int64_t j = 0; j < len; ++j) {
-        const int32_t n = E.h_support[ob + j];
-        if (support) support[e0 + j] = n;
-        if (!places) continue;
-        const int64_t m = std::min<int64_t>(n, nwhy);
-        std::copy_n(E.h_items.data() + (ob + j) * nwhy, m, why_items + (e0 + j) * nwhy);
-        std::copy_n(E.h_terms.data() + (ob + j) * nwhy, m, why_terms + (e0 + j) * nwhy);
-      }
-      ob += len;
-    }
-  } catch (...) {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    throw;
+  int set_allocs = 0;
+  const CandidateRows rows = candset_on_device(cs, device, num_cus, stream, &set_allocs, &st.h2d_bytes);
+  ExplainWorkspace& E = candset_explain_workspace(cs);
+  E.allocs = 0;
+  // no slicing: the outputs of all selected rows stand in device memory at once
+  const size_t want = (size_t)entries * (places ? 8 * (size_t)nwhy + 4 : 4);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (want > (free_b + E.held()) / 2) {
+    set_error(w + ": the outputs of " + std::to_string(entries) + " candidate entries at nwhy = " +
+              std::to_string(nwhy) + " need " + std::to_string(want) + " bytes of device memory, more than half of "
+              "the " + std::to_string(free_b + E.held()) + " that are free: pass user sub-lists");
+    return SLIM_ERROR_MEMORY;
   }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  return rc;
+  ExplainArgs A = {};
+  A.wrows = W.nrows; A.wptr = W.d_ptr; A.wind = W.d_ind; A.wval = W.d_val;
+  A.npos = nsel; A.hptr = H.ptr; A.hind = H.ind; A.hval = H.val;
+  A.cptr = rows.cptr; A.lptr = rows.lptr; A.pairs = rows.pairs;
+  A.nwhy = nwhy;
+  A.stage = stage_entries();
+  if (h_users) {
+    int32_t* d_users = E.need(E.users, (size_t)nsel);
+    HIP_TRY(hipMemcpyAsync(d_users, h_users, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, stream));
+    st.h2d_bytes += (int64_t)(sizeof(int32_t) * (size_t)nsel);
+    int64_t* d_obase = E.need(E.obase, (size_t)nsel + 1);
+    hipLaunchKernelGGL(k_explain_base, dim3(1), dim3(256), 0, stream, nsel, d_users, rows.cptr, d_obase);
+    HIP_TRY(hipGetLastError());
+    A.users = d_users;
+    A.obase = d_obase;
+  }
+  A.support = E.need(E.support, (size_t)entries);
+  if (places) {
+    A.items = E.need(E.items, (size_t)entries * nwhy);
+    A.terms = E.need(E.terms, (size_t)entries * nwhy);
+  }
+  HIP_TRY(hipMemsetAsync(A.support, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(entries, 1), stream));
+  EventPair ev;
+  ev.begin(stream);
+  if (nsel > 0 && entries > 0) {
+    const dim3 grid((unsigned)std::min<int64_t>(nsel, (int64_t)num_cus * 8)), block(64 * kExplainWaves);
+    const size_t lds = sizeof(int4) * (size_t)A.stage;
+    if (std::getenv("SLIM_GPU_TRACE"))
+      std::fprintf(stderr, "[trace] k_explain<%d>: %d positions, %d workgroups, %d staged entries, nwhy %d, %s\n",
+                   nwhy > 4 || form16_forced() ? 16 : 4, nsel, (int)grid.x, A.stage, nwhy,
+                   h_users ? "a user list" : "all users");
+    if (nwhy > 4 || form16_forced())
+      hipLaunchKernelGGL(k_explain<16>, grid, block, lds, stream, A);
+    else
+      hipLaunchKernelGGL(k_explain<4>, grid, block, lds, stream, A);
+    HIP_TRY(hipGetLastError());
+  }
+  ev.end(stream);
+  size_t down = 0;
+  auto fetch = [&](auto& image, const auto* d, size_t n) {
+    if (image.size() < n) image.resize(n);
+    if (n == 0) return;
+    HIP_TRY(hipMemcpyAsync(image.data(), d, sizeof(*d) * n, hipMemcpyDeviceToHost, stream));
+    down += sizeof(*d) * n;
+  };
+  fetch(E.h_support, A.support, (size_t)entries);
+  if (places) {
+    fetch(E.h_items, A.items, (size_t)entries * nwhy);
+    fetch(E.h_terms, A.terms, (size_t)entries * nwhy);
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  st.kernel_ms = ev.ms();
+  st.d2h_bytes += (int64_t)down;
+  st.path = kExplain;
+  st.device_allocs = set_allocs + E.allocs;
+  // out of the images: the rows of the positions stand side by side there, in the caller's arrays at cptr[user]
+  int64_t ob = 0;
+  for (int32_t q = 0; q < nsel; ++q) {
+    const int32_t u = h_users ? h_users[q] : q;
+    const int64_t e0 = cptr[u], len = cptr[u + 1] - e0;
+    for (int64_t j = 0; j < len; ++j) {
+      const int32_t n = E.h_support[ob + j];
+      if (support) support[e0 + j] = n;
+      if (!places) continue;
+      const int64_t m = std::min<int64_t>(n, nwhy);
+      std::copy_n(E.h_items.data() + (ob + j) * nwhy, m, why_items + (e0 + j) * nwhy);
+      std::copy_n(E.h_terms.data() + (ob + j) * nwhy, m, why_terms + (e0 + j) * nwhy);
+    }
+    ob += len;
+  }
+  return SLIM_OK;
 }
 }  // namespace
 
@@ -180,37 +166,20 @@ int32_t explain_candidates(const slim_csr_t* W, const slim_csr_t* trn, slimgpu_c
     return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    int ndev = 0, device = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
-    HIP_TRY(hipGetDevice(&device));
+  return guarded(who, [&]() -> int32_t {
+    const int device = open_current_device();
     const int num_cus = cu_count();
     if (nusers > 0) {
-      const StagedCsr w = stage_csr(W, W->nrows, /*values=*/true, /*stream=*/nullptr);
-      const StagedCsr h = stage_csr(trn, nusers, /*values=*/true, /*stream=*/nullptr);
-      DeviceRowView V;
-      V.nrows = W->nrows; V.ncols = W->ncols; V.nnz = w.nnz; V.max_row = w.max_row;
-      V.d_ptr = w.ptr.get(); V.d_ind = w.ind.get(); V.d_val = w.val.get();
-      V.rows_sorted = V.nnz > 0 && rows_ascend_strictly(num_cus, V.nrows, V.d_ptr, V.d_ind);
-      HistoryView H;
-      H.nusers = nusers; H.max_hist = h.max_row;
-      H.ptr = h.ptr.get(); H.ind = h.ind.get(); H.val = h.val.get();
-      const int32_t rc = explain_rows(who, V, H, nullptr, cs, device, num_cus, /*stream=*/nullptr, nwhy, why_items,
+      const StagedPair P = stage_pair(W, trn, num_cus);
+      const int32_t rc = explain_rows(who, P.W, P.H, nullptr, cs, device, num_cus, /*stream=*/nullptr, nwhy, why_items,
                                       why_terms, support, st);
       if (rc != SLIM_OK) return rc;
-      st.w_rows_read = h.nnz;
+      st.w_rows_read = P.h.nnz;
     }
     st.total_ms = ms_since(t_begin);
     last_eval_stats() = st;
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 
 int32_t matrix_explain_candidates(const slimgpu_model* model, slimgpu_matrix_t* mat, slimgpu_candset* cs,
@@ -228,10 +197,8 @@ int32_t matrix_explain_candidates(const slimgpu_model* model, slimgpu_matrix_t* 
   if (const int32_t rc = candset_check(who, cs, W.ncols, nu, users, 0, nullptr, nullptr); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  return guarded(who, [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
     if (nu > 0) {
       // (a history of any length below 2^31 - 1 is served: only a matrix that could hold a longer one is measured)
       const int64_t max_hist = R.nnz < INT32_MAX ? 0 : longest_history(stream, R.num_cus, R.nrows, nullptr, R.d_ptr, nullptr);
@@ -244,11 +211,6 @@ int32_t matrix_explain_candidates(const slimgpu_model* model, slimgpu_matrix_t* 
     st.total_ms = ms_since(t_begin);
     last_eval_stats() = st;
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 }  // namespace slimamd

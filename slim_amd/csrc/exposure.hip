@@ -21,9 +21,8 @@
 #include <string>
 #include <vector>
 
+#include "call_frame.hpp"
 #include "host_csr.hpp"
-#include "host_stage.hpp"
-#include "scorer.hpp"
 
 namespace slimamd {
 namespace {
@@ -218,10 +217,8 @@ int32_t matrix_list_exposure(slimgpu_matrix_t* mat, const int32_t* fmarker, int3
   Cutoffs cut = {};
   cut.n = ncutoffs;
   for (int32_t k = 0; k < ncutoffs; ++k) cut.c[k] = cutoffs[k];
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  return guarded(who, [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
     std::vector<int64_t> cp((size_t)R.ncols + 1);
     if (matrix_get_column_view(mat, cp.data(), nullptr, nullptr, nullptr) != SLIM_OK) return SLIM_ERROR;
     std::vector<uint32_t> pop((size_t)R.ncols);
@@ -245,11 +242,6 @@ int32_t matrix_list_exposure(slimgpu_matrix_t* mat, const int32_t* fmarker, int3
     fetch_exposure(stream, R.ncols, cut, ws, h_E, pop.data(), fmarker, fm_ncols, nlists, /*engine_lists=*/false, exposure,
                    summary);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 }  // namespace slimamd

@@ -1,5 +1,6 @@
 // host_stage.hpp -- what the scorers' host code (topn.hip, resident_eval.hip, eval.hip) shares: the rows of a host CSR staged
-// in device memory, the report of a HIP failure, the CU count of the current device.
+// in device memory, the report of a HIP failure, the CU count of the current device.  What an entry point is
+// framed by (the error boundary, the event pair, the staged users and the staged host pair) is call_frame.hpp's.
 #pragma once
 
 #include <algorithm>

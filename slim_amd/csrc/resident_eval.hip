@@ -6,16 +6,26 @@
 // k_sum_in_user_order adds them; 8 + 32 bytes per cutoff come down.  The evaluated users are the matrix's
 // first rows or a sorted list of them (positions, eval_terms.hpp); several list lengths are served by the
 // one scoring pass of the longest.  Everything is queued through the scorer's one launch path (scorer.hpp).
+// Every entry point is its checks and its own middle inside the shared frame (call_frame.hpp); the calls on an
+// eval set stand in EvalCall below, where what holds for every evaluation is written once.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 
-#include "host_stage.hpp"
-#include "scorer.hpp"
+#include "call_frame.hpp"
+
+namespace slimamd {
+struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoffs bytes
+  unsigned long long streamed;  // entries of the model rows streamed
+  EvalSums sums[SLIMGPU_MAX_RANK_CUTOFFS];
+};
+}  // namespace slimamd
 
 // What an evaluation needs besides the model (slim_gpu_eval.h: SLIMGPU_EvalSetCreate).  Owns its buffers;
 // borrows the matrix.
@@ -32,7 +42,7 @@ struct slimgpu_evalset {
   slimamd::DeviceBuffer<int32_t> d_fm, d_users;
   std::vector<int32_t> h_users;  // the listed users on the host: a candidate set's rows are checked against them
   slimamd::DeviceBuffer<slimamd::UserTerms> d_terms;  // [cut.n][nsel]
-  slimamd::DeviceBuffer<unsigned long long> d_out;    // EvalOut
+  slimamd::DeviceBuffer<slimamd::EvalOut> d_out;
   slimamd::ScorerWorkspace ws;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // ranks of the held-out items (slim_gpu_rank.h): the test entries of the evaluated users and the longest of
@@ -68,12 +78,6 @@ namespace slimamd {
 namespace {
 thread_local slimgpu_eval_stats_t g_eval_stats;
 thread_local double g_rank_prepass_ms = 0;
-
-struct EvalOut {  // what one evaluation brings down: the first 8 + 32 * ncutoffs bytes
-  unsigned long long streamed;  // entries of the model rows streamed
-  EvalSums sums[SLIMGPU_MAX_RANK_CUTOFFS];
-};
-
 }  // namespace
 
 // the matrix and the model of one call: one device, one width, rows that are the caller's
@@ -142,12 +146,10 @@ slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* 
   const int32_t nall = std::min(R.nrows, tst->nrows);  // pyapi.c:309
   if (check_user_list("SLIMGPU_EvalSetCreate", nusers, users, nall) != SLIM_OK) return fail(SLIM_ERROR_INPUT);
   const int32_t nrcmds = ranked ? 1 : cut.c[cut.n - 1];
-  slimgpu_evalset* es = nullptr;
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
-    es = new slimgpu_evalset();
+  std::unique_ptr<slimgpu_evalset> es;  // (a failure frees what was made)
+  const int32_t st = guarded("SLIMGPU_EvalSetCreate", [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
+    es.reset(new slimgpu_evalset());
     es->mat = mat; es->device = R.device; es->cut = cut; es->fm_ncols = fm_ncols;
     es->listed = users != nullptr;
     es->nsel = users ? nusers : nall;
@@ -157,7 +159,7 @@ slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* 
     es->d_fm = DeviceBuffer<int32_t>((size_t)fm_ncols);
     es->h_fm.assign(fmarker, fmarker + fm_ncols);
     es->d_terms = DeviceBuffer<UserTerms>((size_t)cut.n * (size_t)nsel);
-    es->d_out = DeviceBuffer<unsigned long long>(sizeof(EvalOut) / sizeof(unsigned long long));
+    es->d_out = DeviceBuffer<EvalOut>(1);
     if (fm_ncols > 0)
       HIP_TRY(hipMemcpyAsync(es->d_fm.get(), fmarker, sizeof(int32_t) * (size_t)fm_ncols, hipMemcpyHostToDevice, stream));
     if (users) {  // (pageable source: the copy has left the caller's array when the call returns)
@@ -193,19 +195,15 @@ slimgpu_evalset_t* evalset_create_impl(slimgpu_matrix_t* mat, const slim_csr_t* 
     DeviceRowView worst;
     worst.nrows = worst.ncols = R.ncols;
     worst.rows_sorted = true;
-    reserve_scorer(es->ws, choose_scorer(worst, history_of(R, es), ListsRequest{nrcmds}, /*force_key64=*/true), R.ncols,
-                   std::max(R.ncols, 1), nsel, R.num_cus, /*lists=*/false);
+    reserve_scorer(es->ws, choose_scorer(worst, history_of(R, es.get()), ListsRequest{nrcmds}, /*force_key64=*/true),
+                   R.ncols, std::max(R.ncols, 1), nsel, R.num_cus, /*lists=*/false);
+    // (the eval set's four events live as long as it does: an evaluation creates none)
     for (hipEvent_t* e : {&es->ev0, &es->ev1, &es->evk0, &es->evk1}) HIP_TRY(hipEventCreate(e));
-    if (status) *status = SLIM_OK;
-    return es;
-  } catch (const HipFail& e) {
-    delete es;
-    return fail(hip_failure("SLIMGPU_EvalSetCreate", e));
-  } catch (const std::bad_alloc&) {
-    delete es;
-    set_error("SLIMGPU_EvalSetCreate: out of host memory");
-    return fail(SLIM_ERROR_MEMORY);
-  }
+    return SLIM_OK;
+  });
+  if (st != SLIM_OK) return fail(st);
+  if (status) *status = SLIM_OK;
+  return es.release();
 }
 
 // The checks that every evaluation shares, in their order: the caller's own arguments (args_ok) and the handles,
@@ -223,33 +221,78 @@ int32_t check_evaluation(const char* who, bool args_ok, slimgpu_evalset_t* es, c
   return SLIM_OK;
 }
 
-// What every call of an eval set leaves in last_eval_stats() once its stream has run, with the time of the
-// scorer and what followed it (ev0 .. ev1) and, for a ranked call, of the pre-pass.
-void close_stats(slimgpu_evalset_t* es, bool ranked, slimgpu_eval_stats_t& st,
-                 const std::chrono::steady_clock::time_point& t_begin) {
-  float ms = 0;
-  if (es->nsel > 0) {
-    HIP_TRY(hipEventElapsedTime(&ms, es->ev0, es->ev1));
-    st.kernel_ms = ms;
-    if (ranked && es->entries > 0) {
-      HIP_TRY(hipEventElapsedTime(&ms, es->evk0, es->evk1));
-      g_rank_prepass_ms = ms;
-    }
-  }
-  st.device_allocs = es->ws.allocs;
-  st.w_rows_read = es->hist_entries;
-  st.total_ms = ms_since(t_begin);
-  g_eval_stats = st;
-}
+// The frame of a call on an eval set once its checks have passed (constructed inside guarded): the clock and the
+// stats record, the device and the stream, the workspace's allocation count restarted, the histories.  A call that
+// forms figures hands in its outputs (out[0 .. ncut)): they are zeroed, and the group rows on hand (slim_gpu_groups.h)
+// stop being readable until finish() has put this call's in their place -- what holds for every evaluation is
+// written here, once.  A call without figures (model_ranks: out == nullptr) leaves the group rows alone.
+struct EvalCall {
+  slimgpu_evalset_t* const es;
+  const DeviceCsrView& R;
+  const DeviceRowView& W;
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  slimgpu_eval_stats_t st = {};
+  hipStream_t stream = nullptr;
+  HistoryView H;
 
-// the figures of one cutoff's accumulators
-EvalResult result_of(const EvalSums& s) {
-  EvalResult r;
-  r.nvalid = s.n[0]; r.nvalid_head = s.n[1]; r.nvalid_tail = s.n[2];
-  r.hr = s.n[0] > 0 ? s.f[0] / s.n[0] : 0; r.arhr = s.n[0] > 0 ? s.f[3] / s.n[0] : 0;
-  r.hr_head = s.n[1] > 0 ? s.f[1] / s.n[1] : 0; r.hr_tail = s.n[2] > 0 ? s.f[2] / s.n[2] : 0;
-  return r;
-}
+  EvalCall(slimgpu_evalset_t* es_, const DeviceCsrView& R_, const DeviceRowView& W_, int32_t ncut, EvalResult* out)
+      : es(es_), R(R_), W(W_) {
+    for (int32_t k = 0; out && k < ncut; ++k) out[k] = EvalResult();
+    stream = open_device(R);
+    es->ws.allocs = 0;
+    if (out) es->group_ncut = 0;
+    H = history_of(R, es);
+  }
+  EvalSums* sums() const { return es->d_out.get()->sums; }  // where the call's sums are queued (queue_sums)
+
+  // What every call of an eval set leaves in last_eval_stats() once its stream has run, with the time of the
+  // scorer and what followed it (ev0 .. ev1) and, for a ranked call, of the pre-pass.
+  void close(bool ranked) {
+    float ms = 0;
+    if (es->nsel > 0) {
+      HIP_TRY(hipEventElapsedTime(&ms, es->ev0, es->ev1));
+      st.kernel_ms = ms;
+      if (ranked && es->entries > 0) {
+        HIP_TRY(hipEventElapsedTime(&ms, es->evk0, es->evk1));
+        g_rank_prepass_ms = ms;
+      }
+    }
+    st.device_allocs = es->ws.allocs;
+    st.w_rows_read = es->hist_entries;
+    st.total_ms = ms_since(t_begin);
+    g_eval_stats = st;
+  }
+
+  // The end of an evaluation whose sums of `ncut` cutoffs are queued into sums() (ev0 was recorded before its
+  // scorer): ev1, the scorer's byte model, 8 + 32 * ncut bytes down, the sums as results, the stats.
+  void finish(int32_t ncut, EvalResult* out, bool ranked) {
+    EvalOut h = {};
+    if (es->nsel > 0) {
+      EvalOut* d_out = es->d_out.get();
+      HIP_TRY(hipEventRecord(es->ev1, stream));
+      HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
+      if (es->hist_entries > 0 && W.nnz > 0) queue_streamed_entries(stream, R.num_cus, H, W, &d_out->streamed);
+      size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncut;
+      HIP_TRY(hipMemcpyAsync(&h, d_out, down, hipMemcpyDeviceToHost, stream));
+      if (es->ngroups > 0) {  // (the group rows come down with the same synchronisation)
+        const size_t rows = sizeof(EvalSums) * (size_t)ncut * (size_t)es->ngroups;
+        HIP_TRY(hipMemcpyAsync(es->h_gsums.data(), es->d_gsums.get(), rows, hipMemcpyDeviceToHost, stream));
+        down += rows;
+      }
+      HIP_TRY(hipStreamSynchronize(stream));
+      st.d2h_bytes = (int64_t)down;
+    } else if (es->ngroups > 0) {
+      std::fill(es->h_gsums.begin(), es->h_gsums.end(), EvalSums{});
+    }
+    for (int32_t k = 0; k < ncut; ++k) out[k] = result_of(h.sums[k]);
+    if (es->ngroups > 0) {
+      std::copy(out, out + ncut, es->group_every);
+      es->group_ncut = ncut;
+    }
+    st.w_bytes = 8.0 * (double)h.streamed;
+    close(ranked);
+  }
+};
 
 // The sums of `ncut` cutoffs over `terms` ([ncut][nsel]) into out[0 .. ncut), positions added in position order: what
 // every evaluation ends in.  While groups are set (slim_gpu_groups.h) one launch forms them and, from the same
@@ -259,39 +302,6 @@ void queue_sums(slimgpu_evalset_t* es, hipStream_t stream, int32_t ncut, const U
   if (es->ngroups == 0) return launch_sum_in_user_order(stream, es->nsel, ncut, terms, out);
   launch_sum_groups_in_user_order(stream, es->nsel, ncut, es->ngroups, terms, es->d_gorder.get(), es->d_goffsets.get(),
                                   es->d_gsums.get() + (size_t)k0 * (size_t)es->ngroups, out);
-}
-
-// The end of an evaluation whose sums of `ncut` cutoffs are queued into the eval set's EvalOut (ev0 was recorded
-// before its scorer): ev1, the scorer's byte model, 8 + 32 * ncut bytes down, the sums as results, the stats.
-void finish_evaluation(slimgpu_evalset_t* es, const DeviceCsrView& R, const DeviceRowView& W, const HistoryView& H,
-                       int32_t ncut, EvalResult* out, bool ranked, slimgpu_eval_stats_t& st,
-                       const std::chrono::steady_clock::time_point& t_begin) {
-  EvalOut h = {};
-  if (es->nsel > 0) {
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
-    EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
-    HIP_TRY(hipEventRecord(es->ev1, stream));
-    HIP_TRY(hipMemsetAsync(&d_out->streamed, 0, sizeof(unsigned long long), stream));
-    if (es->hist_entries > 0 && W.nnz > 0) queue_streamed_entries(stream, R.num_cus, H, W, &d_out->streamed);
-    size_t down = sizeof(unsigned long long) + sizeof(EvalSums) * (size_t)ncut;
-    HIP_TRY(hipMemcpyAsync(&h, d_out, down, hipMemcpyDeviceToHost, stream));
-    if (es->ngroups > 0) {  // (the group rows come down with the same synchronisation)
-      const size_t rows = sizeof(EvalSums) * (size_t)ncut * (size_t)es->ngroups;
-      HIP_TRY(hipMemcpyAsync(es->h_gsums.data(), es->d_gsums.get(), rows, hipMemcpyDeviceToHost, stream));
-      down += rows;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    st.d2h_bytes = (int64_t)down;
-  } else if (es->ngroups > 0) {
-    std::fill(es->h_gsums.begin(), es->h_gsums.end(), EvalSums{});
-  }
-  for (int32_t k = 0; k < ncut; ++k) out[k] = result_of(h.sums[k]);
-  if (es->ngroups > 0) {
-    std::copy(out, out + ncut, es->group_every);
-    es->group_ncut = ncut;
-  }
-  st.w_bytes = 8.0 * (double)h.streamed;
-  close_stats(es, ranked, st, t_begin);
 }
 }  // namespace
 
@@ -364,18 +374,6 @@ int32_t install_groups(const char* who, slimgpu_evalset_t* es, const DeviceCsrVi
   es->group_ncut = 0;
   return SLIM_OK;
 }
-
-// what a failure while the groups are made turns into
-int32_t groups_failure(const char* who) {
-  try {
-    throw;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
-}
 }  // namespace
 
 int32_t evalset_set_groups(slimgpu_evalset_t* es, int32_t ngroups, const int32_t* group_of_user) {
@@ -383,13 +381,10 @@ int32_t evalset_set_groups(slimgpu_evalset_t* es, int32_t ngroups, const int32_t
   DeviceCsrView R;
   if (!es || !group_of_user || matrix_csr_view(es->mat, &R) != SLIM_OK)
     return refuse(std::string(who) + ": bad arguments (an eval set and the array)");
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
+  return guarded(who, [&]() -> int32_t {
+    open_device(R);
     return install_groups(who, es, R, es->listed ? es->h_users.data() : nullptr, es->nall, ngroups, group_of_user);
-  } catch (...) {
-    return groups_failure(who);
-  }
+  });
 }
 
 // the lengths are the staged matrix's, classified where they lie: 4 * nsel bytes come down once, and the positions'
@@ -407,13 +402,11 @@ int32_t evalset_set_history_bands(slimgpu_evalset_t* es, int32_t nbounds, const 
       return refuse(std::string(who) + ": a bound must be at least 1, not " + std::to_string(bounds[j]));
     if (j > 0 && bounds[j] <= bounds[j - 1]) return refuse(std::string(who) + ": the bounds must ascend strictly");
   }
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
+  return guarded(who, [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
     const int32_t nsel = es->nsel;
     std::vector<int32_t> band((size_t)std::max(nsel, 1), 0);
     if (nsel > 0) {
-      hipStream_t stream = static_cast<hipStream_t>(R.stream);
       DeviceBuffer<int32_t> d_bounds((size_t)nbounds), d_band((size_t)nsel);
       HIP_TRY(hipMemcpyAsync(d_bounds.get(), bounds, sizeof(int32_t) * (size_t)nbounds, hipMemcpyHostToDevice, stream));
       launch_history_bands(stream, R.num_cus, nsel, es->listed ? es->d_users.get() : nullptr, R.d_ptr, nbounds,
@@ -422,9 +415,7 @@ int32_t evalset_set_history_bands(slimgpu_evalset_t* es, int32_t nbounds, const 
       HIP_TRY(hipStreamSynchronize(stream));
     }
     return install_groups(who, es, R, nullptr, nsel, nbounds + 1, band.data());
-  } catch (...) {
-    return groups_failure(who);
-  }
+  });
 }
 
 void evalset_clear_groups(slimgpu_evalset_t* es) {
@@ -475,30 +466,20 @@ int32_t model_evaluate(slimgpu_evalset_t* es, const slimgpu_model* model, int32_
   if (const int32_t rc = check_evaluation(who, out != nullptr, es, model, &ncutoffs, W, R); rc != SLIM_OK) return rc;
   if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   const int32_t ncut = es->cut.n;
-  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
-  const auto t_begin = std::chrono::steady_clock::now();
-  slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
-    es->ws.allocs = 0;
-    es->group_ncut = 0;  // (slim_gpu_groups.h: the group rows on hand are no longer the last evaluation's)
-    const HistoryView H = history_of(R, es);
+  return guarded(who, [&]() -> int32_t {
+    EvalCall c(es, R, W, ncut, out);
     if (es->nsel > 0) {
       const ScorerRequest rq =
           EvalTargets{es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get(), es->cut};
       // (the filter's device copy is made by its first call on this device; later ones allocate and send nothing)
-      const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
-      HIP_TRY(hipEventRecord(es->ev0, stream));
-      st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
-      queue_sums(es, stream, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      const CandidateFilter F = filter_on_device(filter, R.device, c.stream, &es->ws.allocs, &c.st.h2d_bytes);
+      HIP_TRY(hipEventRecord(es->ev0, c.stream));
+      c.st.path = queue_scorer(W, c.H, choose_scorer(W, c.H, rq), rq, R.num_cus, c.stream, es->ws, F).path;
+      queue_sums(es, c.stream, ncut, es->d_terms.get(), c.sums());
     }
-    finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
+    c.finish(ncut, out, /*ranked=*/false);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  }
+  });
 }
 
 namespace {
@@ -531,45 +512,33 @@ int32_t model_evaluate_exposure(slimgpu_evalset_t* es, const slimgpu_model* mode
   if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   if (const int32_t rc = check_exposure_width(who, R, W); rc != SLIM_OK) return rc;
   const int32_t ncut = es->cut.n, nrcmds = es->cut.c[ncut - 1], ncols = R.ncols;
-  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
-  const auto t_begin = std::chrono::steady_clock::now();
-  slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
-    es->ws.allocs = 0;
-    es->group_ncut = 0;  // (as in model_evaluate)
+  return guarded(who, [&]() -> int32_t {
+    EvalCall c(es, R, W, ncut, out);
+    hipStream_t stream = c.stream;
     int64_t first_down = 0;
     if (es->h_pop.size() != (size_t)ncols) {  // (the first call on this eval set)
       column_counts(es->mat, ncols, es->h_pop);
       first_down = (int64_t)sizeof(int64_t) * ((int64_t)ncols + 1);
     }
-    const HistoryView H = history_of(R, es);
     if (es->nsel > 0) {
       const ScorerRequest rq = EvalTargets{es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols,
                                            es->d_terms.get(), es->cut, /*keep_lists=*/true};
-      const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
+      const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &c.st.h2d_bytes);
       HIP_TRY(hipEventRecord(es->ev0, stream));
       queue_exposure_clear(stream, ncols, es->cut, es->ws);
-      st.path = queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path;
-      queue_sums(es, stream, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      c.st.path = queue_scorer(W, c.H, choose_scorer(W, c.H, rq), rq, R.num_cus, stream, es->ws, F).path;
+      queue_sums(es, stream, ncut, es->d_terms.get(), c.sums());
       queue_exposure_count(stream, R.num_cus, es->ws.oid.get(), es->ws.ocnt.get(), es->nsel, nrcmds, ncols, es->cut,
                            es->ws);
       queue_exposure_cumulate(stream, R.num_cus, ncols, es->cut, es->ws);
     }
-    finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
+    c.finish(ncut, out, /*ranked=*/false);
     const size_t down = fetch_exposure(stream, ncols, es->cut, es->ws, es->h_expo, es->h_pop.data(), es->h_fm.data(),
                                        es->fm_ncols, es->nsel, /*engine_lists=*/true, exposure, summary);
     g_eval_stats.d2h_bytes += (int64_t)down + first_down;
-    g_eval_stats.total_ms = ms_since(t_begin);
+    g_eval_stats.total_ms = ms_since(c.t_begin);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 
 // The evaluation of candidate lists (slim_gpu_cand.h): the scorer writes the slot scores of the users' candidate
@@ -589,56 +558,44 @@ int32_t model_evaluate_candidates(slimgpu_evalset_t* es, const slimgpu_model* mo
   if (const int32_t rc = candset_check(who, cs, W.ncols, es->nsel, h_users, nrcmds, &lists_wanted, &scores_wanted);
       rc != SLIM_OK)
     return rc;
-  for (int32_t k = 0; k < ncut; ++k) out[k] = EvalResult();
-  const auto t_begin = std::chrono::steady_clock::now();
-  slimgpu_eval_stats_t st = {};
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
-    es->ws.allocs = 0;
-    es->group_ncut = 0;  // (slim_gpu_groups.h: the group rows on hand are no longer the last evaluation's)
-    const HistoryView H = history_of(R, es);
+  return guarded(who, [&]() -> int32_t {
+    EvalCall c(es, R, W, ncut, out);
+    hipStream_t stream = c.stream;
     if (es->nsel > 0) {
-      const CandidateRows rows = candset_on_device(cs, R.device, R.num_cus, stream, &es->ws.allocs, &st.h2d_bytes);
+      const CandidateRows rows = candset_on_device(cs, R.device, R.num_cus, stream, &es->ws.allocs, &c.st.h2d_bytes);
       HIP_TRY(hipEventRecord(es->ev0, stream));
-      st.path = queue_candidates(W, H, rows, nrcmds, R.num_cus, stream, es->ws);
-      if (st.path == kRefused) return refuse(std::string(who) + ": " + last_error());
-      launch_user_terms(stream, R.num_cus, es->nsel, H.users, nrcmds, es->cut, es->ws.oid.get(), es->ws.ocnt.get(),
+      if (queue_candidates(W, c.H, rows, nrcmds, R.num_cus, stream, es->ws) == kRefused)
+        return refuse(std::string(who) + ": " + last_error());
+      launch_user_terms(stream, R.num_cus, es->nsel, c.H.users, nrcmds, es->cut, es->ws.oid.get(), es->ws.ocnt.get(),
                         es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, es->d_terms.get());
-      queue_sums(es, stream, ncut, es->d_terms.get(), reinterpret_cast<EvalOut*>(es->d_out.get())->sums);
+      queue_sums(es, stream, ncut, es->d_terms.get(), c.sums());
     }
-    st.path = kCand;
-    finish_evaluation(es, R, W, H, ncut, out, /*ranked=*/false, st, t_begin);
+    c.st.path = kCand;
+    c.finish(ncut, out, /*ranked=*/false);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(who, e);
-  }
+  });
 }
 
 // ---- the rank of every held-out item (slim_gpu_rank.h) ------------------------------------------
 namespace {
-// the checks both ranked calls share, then the scorer in rank mode on the matrix's stream: ranks and scores of
-// the eval set's test entries are in es->ws.rank / rscore when the stream has run.  SLIM_OK or a refusal.
-// evaluation: the call forms figures (model_evaluate_ranked), so the group rows on hand stop being the last ones.
-int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
-                    DeviceRowView& W, DeviceCsrView& R, HistoryView& H, slimgpu_eval_stats_t& st, bool evaluation) {
+// the checks both ranked calls share
+int32_t check_ranked(const char* who, slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
+                     DeviceRowView& W, DeviceCsrView& R) {
   if (const int32_t rc = check_evaluation(who, true, es, model, nullptr, W, R); rc != SLIM_OK) return rc;
-  if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
-  (void)hipGetLastError();
-  HIP_TRY(hipSetDevice(R.device));
-  hipStream_t stream = static_cast<hipStream_t>(R.stream);
-  es->ws.allocs = 0;
-  if (evaluation) es->group_ncut = 0;
+  return filter_check(who, filter, W.ncols);
+}
+// the scorer in rank mode on the call's stream: ranks and scores of the eval set's test entries are in es->ws.rank /
+// rscore when the stream has run.  SLIM_OK or a refusal.
+int32_t queue_ranks(const char* who, EvalCall& c, slimgpu_filter* filter) {
+  slimgpu_evalset_t* es = c.es;
   g_rank_prepass_ms = 0;
-  st.path = kRank;
+  c.st.path = kRank;
   if (es->nsel <= 0) return SLIM_OK;
-  H = history_of(R, es);
   const ScorerRequest rq = RankTargets{es->tst.ptr.get(), es->tst.ind.get(), es->tbase(),
                                        es->entries,       es->max_test,      es->evk0,    es->evk1};
-  const CandidateFilter F = filter_on_device(filter, R.device, stream, &es->ws.allocs, &st.h2d_bytes);
-  HIP_TRY(hipEventRecord(es->ev0, stream));
-  if (queue_scorer(W, H, choose_scorer(W, H, rq), rq, R.num_cus, stream, es->ws, F).path != kRank)
+  const CandidateFilter F = filter_on_device(filter, c.R.device, c.stream, &es->ws.allocs, &c.st.h2d_bytes);
+  HIP_TRY(hipEventRecord(es->ev0, c.stream));
+  if (queue_scorer(c.W, c.H, choose_scorer(c.W, c.H, rq), rq, c.R.num_cus, c.stream, es->ws, F).path != kRank)
     return refuse(std::string(who) + ": " + last_error());
   return SLIM_OK;
 }
@@ -647,33 +604,28 @@ int32_t queue_ranks(const char* who, slimgpu_evalset_t* es, const slimgpu_model*
 int32_t model_ranks(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t* ranks, float* scores,
                     slimgpu_filter* filter) {
   const char* who = filter ? "SLIMGPU_ModelRanksFiltered" : "SLIMGPU_ModelRanks";
-  const auto t_begin = std::chrono::steady_clock::now();
-  slimgpu_eval_stats_t st = {};
-  try {
-    DeviceRowView W;
-    DeviceCsrView R;
-    HistoryView H;
-    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st, /*evaluation=*/false); rc != SLIM_OK)
-      return rc;
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (const int32_t rc = check_ranked(who, es, model, filter, W, R); rc != SLIM_OK) return rc;
+  return guarded(who, [&]() -> int32_t {
+    EvalCall c(es, R, W, 0, nullptr);  // (no figures: the group rows stay the last evaluation's)
+    if (const int32_t rc = queue_ranks(who, c, filter); rc != SLIM_OK) return rc;
     if (es->nsel > 0) {
-      hipStream_t stream = static_cast<hipStream_t>(R.stream);
-      HIP_TRY(hipEventRecord(es->ev1, stream));
+      HIP_TRY(hipEventRecord(es->ev1, c.stream));
       const size_t n = (size_t)es->entries;
       if (ranks && n) {
-        HIP_TRY(hipMemcpyAsync(ranks, es->ws.rank.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-        st.d2h_bytes += (int64_t)(sizeof(int32_t) * n);
+        HIP_TRY(hipMemcpyAsync(ranks, es->ws.rank.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost, c.stream));
+        c.st.d2h_bytes += (int64_t)(sizeof(int32_t) * n);
       }
       if (scores && n) {
-        HIP_TRY(hipMemcpyAsync(scores, es->ws.rscore.get(), sizeof(float) * n, hipMemcpyDeviceToHost, stream));
-        st.d2h_bytes += (int64_t)(sizeof(float) * n);
+        HIP_TRY(hipMemcpyAsync(scores, es->ws.rscore.get(), sizeof(float) * n, hipMemcpyDeviceToHost, c.stream));
+        c.st.d2h_bytes += (int64_t)(sizeof(float) * n);
       }
-      HIP_TRY(hipStreamSynchronize(stream));
+      HIP_TRY(hipStreamSynchronize(c.stream));
     }
-    close_stats(es, /*ranked=*/true, st, t_begin);
+    c.close(/*ranked=*/true);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure("SLIMGPU_ModelRanks", e);
-  }
+  });
 }
 
 int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model, int32_t ncutoffs,
@@ -688,36 +640,30 @@ int32_t model_evaluate_ranked(slimgpu_evalset_t* es, const slimgpu_model* model,
       return refuse("SLIMGPU_ModelEvaluateRanked: the cutoffs must ascend strictly");
     out[k] = EvalResult();
   }
-  const auto t_begin = std::chrono::steady_clock::now();
-  slimgpu_eval_stats_t st = {};
-  try {
-    DeviceRowView W;
-    DeviceCsrView R;
-    HistoryView H;
-    const char* who = filter ? "SLIMGPU_ModelEvaluateRankedFiltered" : "SLIMGPU_ModelEvaluateRanked";
-    if (const int32_t rc = queue_ranks(who, es, model, filter, W, R, H, st, /*evaluation=*/true); rc != SLIM_OK)
-      return rc;
+  const char* who = filter ? "SLIMGPU_ModelEvaluateRankedFiltered" : "SLIMGPU_ModelEvaluateRanked";
+  DeviceRowView W;
+  DeviceCsrView R;
+  if (const int32_t rc = check_ranked(who, es, model, filter, W, R); rc != SLIM_OK) return rc;
+  return guarded(who, [&]() -> int32_t {
+    EvalCall c(es, R, W, ncutoffs, out);
+    if (const int32_t rc = queue_ranks(who, c, filter); rc != SLIM_OK) return rc;
     if (es->nsel > 0) {
-      hipStream_t stream = static_cast<hipStream_t>(R.stream);
       const size_t nterms = (size_t)SLIMGPU_MAX_CUTOFFS * (size_t)es->nsel;
       if (es->d_rterms.bytes() < sizeof(UserTerms) * nterms) ++es->ws.allocs;
       UserTerms* d_terms = es->d_rterms.reserve(nterms);
-      EvalOut* d_out = reinterpret_cast<EvalOut*>(es->d_out.get());
       // the terms workspace holds 8 records per position: the cutoffs in slices of SLIMGPU_MAX_CUTOFFS
       for (int32_t k0 = 0; k0 < ncutoffs; k0 += SLIMGPU_MAX_CUTOFFS) {
         Cutoffs cut = {};
         cut.n = std::min<int32_t>(SLIMGPU_MAX_CUTOFFS, ncutoffs - k0);
         for (int32_t k = 0; k < cut.n; ++k) cut.c[k] = cutoffs[k0 + k];
-        launch_rank_terms(stream, R.num_cus, es->nsel, H.users, cut, es->ws.rank.get(), es->tbase(), es->tst.ptr.get(),
-                          es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, d_terms);
-        queue_sums(es, stream, cut.n, d_terms, d_out->sums + k0, k0);
+        launch_rank_terms(c.stream, R.num_cus, es->nsel, c.H.users, cut, es->ws.rank.get(), es->tbase(),
+                          es->tst.ptr.get(), es->tst.ind.get(), es->d_fm.get(), es->fm_ncols, d_terms);
+        queue_sums(es, c.stream, cut.n, d_terms, c.sums() + k0, k0);
       }
     }
-    finish_evaluation(es, R, W, H, ncutoffs, out, /*ranked=*/true, st, t_begin);
+    c.finish(ncutoffs, out, /*ranked=*/true);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure("SLIMGPU_ModelEvaluateRanked", e);
-  }
+  });
 }
 
 namespace {
@@ -737,63 +683,38 @@ int32_t matrix_predict_impl(const char* who, int32_t max_n, int32_t nrcmds, cons
   if (const int32_t rc = filter_check(who, filter, W.ncols); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t rc = SLIM_OK;
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  return guarded(who, [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
     const int32_t nu = users ? nusers : R.nrows;
     if (nu > 0) {
       ScorerWorkspace ws;
-      DeviceBuffer<int32_t> d_users;
-      ++ws.allocs;  // (the longest history's length)
-      if (users) {  // (pageable source: the copy has left the caller's array before the scorer is queued)
-        d_users = DeviceBuffer<int32_t>((size_t)nu);
-        ++ws.allocs;
-        HIP_TRY(hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)nu, hipMemcpyHostToDevice, stream));
-      }
-      const HistoryView H = resident_history(R, nu, d_users.get(),
-                                             longest_history(stream, R.num_cus, nu, d_users.get(), R.d_ptr, nullptr));
+      const StagedUsers U = stage_users(R, nu, users, stream, &ws.allocs);
       const ScorerRequest rq = long_ok ? ScorerRequest(LongListsRequest{nrcmds}) : ScorerRequest(ListsRequest{nrcmds});
-      const ScorerChoice C = choose_scorer(W, H, rq);
+      const ScorerChoice C = choose_scorer(W, U.H, rq);
       const CandidateFilter F = filter_on_device(filter, R.device, stream, &ws.allocs);
-      HIP_TRY(hipEventCreate(&ev0));
-      HIP_TRY(hipEventCreate(&ev1));
-      HIP_TRY(hipEventRecord(ev0, stream));
+      EventPair ev;
+      ev.begin(stream);
       size_t down = 0;  // only the lists come down (and the longest history's length before them)
       if (long_ok) {    // (kernel_ms then spans the slices and their copies)
-        st.path = score_lists(W, H, C, R.num_cus, stream, ws, output, scores, counts, &down, F);
-        if (st.path == kRefused) {
-          set_error(std::string(who) + ": " + std::string(last_error()));
-          rc = SLIM_ERROR_INPUT;
-        }
-        HIP_TRY(hipEventRecord(ev1, stream));
+        st.path = score_lists(W, U.H, C, R.num_cus, stream, ws, output, scores, counts, &down, F);
+        if (st.path == kRefused) return refuse(std::string(who) + ": " + std::string(last_error()));
+        ev.end(stream);
         HIP_TRY(hipStreamSynchronize(stream));
       } else {
-        st.path = queue_scorer(W, H, C, rq, R.num_cus, stream, ws).path;
-        HIP_TRY(hipEventRecord(ev1, stream));
+        st.path = queue_scorer(W, U.H, C, rq, R.num_cus, stream, ws).path;
+        ev.end(stream);
         down = fetch_lists(ws, nu, nrcmds, stream, output, scores, nullptr);
       }
       st.d2h_bytes = (int64_t)(down + sizeof(int32_t));
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-      st.kernel_ms = ms;
+      st.kernel_ms = ev.ms();
       st.device_allocs = ws.allocs;
       st.w_rows_read = R.nnz;
     }
     st.total_ms = ms_since(t_begin);
-    if (rc == SLIM_OK) g_eval_stats = st;
-    if (rc == SLIM_OK && long_ok && nu <= 0) last_list_stats() = slimgpu_list_stats_t{};
-  } catch (const HipFail& e) {
-    rc = hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    rc = SLIM_ERROR_MEMORY;
-  }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  return rc;
+    g_eval_stats = st;
+    if (long_ok && nu <= 0) last_list_stats() = slimgpu_list_stats_t{};
+    return SLIM_OK;
+  });
 }
 }  // namespace
 
@@ -809,7 +730,8 @@ int32_t matrix_predict_lists(int32_t nrcmds, const slimgpu_model* model, slimgpu
                              scores, counts, filter);
 }
 
-// matrix_predict_lists with the lists counted where they are made (score_exposure): only the counters come down
+// matrix_predict_lists with the lists counted where they are made (score_exposure): only the counters come down.
+// The two stand in the same frame and share no more than that: this one has checks of its own and no lists to fetch.
 int32_t matrix_predict_exposure(slimgpu_matrix_t* mat, const slimgpu_model* model, int32_t nrcmds, int32_t nusers,
                                 const int32_t* users, slimgpu_filter* filter, const int32_t* fmarker, int32_t fm_ncols,
                                 int32_t ncutoffs, const int32_t* cutoffs, uint32_t* exposure,
@@ -831,63 +753,36 @@ int32_t matrix_predict_exposure(slimgpu_matrix_t* mat, const slimgpu_model* mode
   for (int32_t k = 0; k < ncutoffs; ++k) cut.c[k] = cutoffs[k];
   const auto t_begin = std::chrono::steady_clock::now();
   slimgpu_eval_stats_t st = {};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t rc = SLIM_OK;
-  try {
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(R.device));
-    hipStream_t stream = static_cast<hipStream_t>(R.stream);
+  return guarded(who, [&]() -> int32_t {
+    hipStream_t stream = open_device(R);
     const int32_t nu = users ? nusers : R.nrows;
     std::vector<uint32_t> pop, h_E;
     column_counts(mat, R.ncols, pop);
     ScorerWorkspace ws;
-    DeviceBuffer<int32_t> d_users;
+    StagedUsers U;
+    std::optional<EventPair> ev;  // (without a user nothing is queued and nothing timed)
     if (nu > 0) {
-      ++ws.allocs;  // (the longest history's length)
-      if (users) {  // (pageable source: the copy has left the caller's array before the scorer is queued)
-        d_users = DeviceBuffer<int32_t>((size_t)nu);
-        ++ws.allocs;
-        HIP_TRY(hipMemcpyAsync(d_users.get(), users, sizeof(int32_t) * (size_t)nu, hipMemcpyHostToDevice, stream));
-      }
-      const HistoryView H = resident_history(R, nu, d_users.get(),
-                                             longest_history(stream, R.num_cus, nu, d_users.get(), R.d_ptr, nullptr));
-      const ScorerChoice C = choose_scorer(W, H, ScorerRequest(LongListsRequest{nrcmds}));
+      U = stage_users(R, nu, users, stream, &ws.allocs);
+      const ScorerChoice C = choose_scorer(W, U.H, ScorerRequest(LongListsRequest{nrcmds}));
       const CandidateFilter F = filter_on_device(filter, R.device, stream, &ws.allocs);
-      HIP_TRY(hipEventCreate(&ev0));
-      HIP_TRY(hipEventCreate(&ev1));
-      HIP_TRY(hipEventRecord(ev0, stream));
-      st.path = score_exposure(W, H, C, R.num_cus, stream, ws, cut, F);
-      if (st.path == kRefused) {
-        set_error(std::string(who) + ": " + std::string(last_error()));
-        rc = SLIM_ERROR_INPUT;
-      } else {
-        HIP_TRY(hipEventRecord(ev1, stream));
-      }
+      ev.emplace().begin(stream);
+      st.path = score_exposure(W, U.H, C, R.num_cus, stream, ws, cut, F);
+      if (st.path == kRefused) return refuse(std::string(who) + ": " + std::string(last_error()));
+      ev->end(stream);
     }
-    if (rc == SLIM_OK) {
-      st.d2h_bytes = (int64_t)fetch_exposure(stream, R.ncols, cut, ws, h_E, pop.data(), fmarker, fm_ncols, nu,
-                                             /*engine_lists=*/true, exposure, summary) +
-                     (int64_t)sizeof(int64_t) * ((int64_t)R.ncols + 1) + (nu > 0 ? (int64_t)sizeof(int32_t) : 0);
-      if (nu > 0) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        st.kernel_ms = ms;
-        st.w_rows_read = R.nnz;
-      } else {
-        last_list_stats() = slimgpu_list_stats_t{};
-      }
-      st.device_allocs = ws.allocs;
-      st.total_ms = ms_since(t_begin);
-      g_eval_stats = st;
+    st.d2h_bytes = (int64_t)fetch_exposure(stream, R.ncols, cut, ws, h_E, pop.data(), fmarker, fm_ncols, nu,
+                                           /*engine_lists=*/true, exposure, summary) +
+                   (int64_t)sizeof(int64_t) * ((int64_t)R.ncols + 1) + (nu > 0 ? (int64_t)sizeof(int32_t) : 0);
+    if (nu > 0) {
+      st.kernel_ms = ev->ms();
+      st.w_rows_read = R.nnz;
+    } else {
+      last_list_stats() = slimgpu_list_stats_t{};
     }
-  } catch (const HipFail& e) {
-    rc = hip_failure(who, e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    rc = SLIM_ERROR_MEMORY;
-  }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  return rc;
+    st.device_allocs = ws.allocs;
+    st.total_ms = ms_since(t_begin);
+    g_eval_stats = st;
+    return SLIM_OK;
+  });
 }
 }  // namespace slimamd

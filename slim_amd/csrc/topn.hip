@@ -1,7 +1,8 @@
 // topn.hip -- the top-N scorers' host side (the kernels: topn_kernels.hpp): the chunk kernel's plan, the choice
 // of the kernel, the launch path, and the entry points that score a host history -- predict_device /
 // predict_device_view and their forms for lists of up to SLIMGPU_MAX_LIST (predict_lists / predict_lists_view).
-// Every entry point, here and in resident_eval.hip, stages what it lacks on the device (host_stage.hpp),
+// Every entry point, here and in resident_eval.hip, stands in the shared frame (call_frame.hpp: the error boundary,
+// the staged host pair), stages what it lacks on the device (host_stage.hpp),
 // describes the model and the histories as views, lets choose_scorer decide once and goes through queue_scorer
 // (scorer.hpp), the one place that builds the split table, fills the kernel arguments and launches.
 #include <hip/hip_runtime.h>
@@ -15,8 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "host_stage.hpp"
-#include "scorer.hpp"
+#include "call_frame.hpp"
 #include "topn_kernels.hpp"
 
 namespace slimamd {
@@ -434,38 +434,58 @@ int32_t long_slice_users(int32_t nusers, int32_t nrcmds) {
 
 slimgpu_list_stats_t& last_list_stats() { return g_list_stats; }
 
+namespace {
+// The lists of every position of H, on the path of C (choose_scorer's for a LongListsRequest), into ws.oid / osc /
+// ocnt; each(S, s0) follows every launch and consumes them: S the positions just scored, s0 the place of the first
+// among H's.  Up to 128 this is one launch over H.  On the long-list path the users go through in slices on the one
+// stream -- a slice is consumed before the next overwrites it -- and the slab counters of all slices add up in
+// ws.lstats (fetch_long_stats).  ls.slices: the launches.  false: nothing serves (set_error says why, nothing queued).
+template <class Each>
+bool score_slices(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& C, int num_cus, hipStream_t stream,
+                  ScorerWorkspace& ws, const CandidateFilter& F, slimgpu_list_stats_t& ls, Each&& each) {
+  const ScorerRequest rq = LongListsRequest{C.nrcmds};
+  if (C.path != kLong) {
+    if (queue_scorer(W, H, C, rq, num_cus, stream, ws, F).path == kRefused) return false;
+    each(H, 0);
+    ls.slices = 1;
+    return true;
+  }
+  ws.need(ws.lstats, 8);
+  HIP_TRY(hipMemsetAsync(ws.lstats.get(), 0, 8 * sizeof(unsigned long long), stream));
+  const int32_t step = long_slice_users(H.nusers, C.nrcmds);
+  for (int32_t s0 = 0; s0 < H.nusers; s0 += step) {
+    HistoryView S = H;
+    S.nusers = std::min(step, H.nusers - s0);
+    if (H.users) S.users = H.users + s0; else S.user0 = H.user0 + s0;
+    queue_scorer(W, S, C, rq, num_cus, stream, ws, F);  // (the exclusion rows go by user id: S names the users)
+    each(S, s0);
+    ++ls.slices;
+  }
+  return true;
+}
+// the slab counters of a long-list call brought down (the stream drained) and decoded; returns the bytes
+size_t fetch_long_stats(const ScorerWorkspace& ws, hipStream_t stream, slimgpu_list_stats_t& ls) {
+  unsigned long long h[5] = {};
+  HIP_TRY(hipMemcpyAsync(h, ws.lstats.get(), sizeof(h), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  ls.candidates = (int64_t)h[0]; ls.contenders = (int64_t)h[1]; ls.refine_passes = (int64_t)h[2];
+  ls.lds_sorts = (int64_t)h[3]; ls.key_refines = (int64_t)h[4];
+  return sizeof(h);
+}
+}  // namespace
+
 ScorerPath score_lists(const DeviceRowView& W, const HistoryView& H, const ScorerChoice& C, int num_cus,
                        hipStream_t stream, ScorerWorkspace& ws, int32_t* output, float* scores, int32_t* counts,
                        size_t* down, const CandidateFilter& F) {
   slimgpu_list_stats_t ls = {};
-  const int32_t nrcmds = C.nrcmds;
-  const ScorerRequest rq = LongListsRequest{nrcmds};
+  const int64_t nrcmds = C.nrcmds;
   size_t bytes = 0;
-  if (C.path != kLong) {
-    const ScorerLaunch L = queue_scorer(W, H, C, rq, num_cus, stream, ws, F);
-    if (L.path == kRefused) return kRefused;
-    bytes = fetch_lists(ws, H.nusers, nrcmds, stream, output, scores, counts);
-    ls.slices = 1;
-  } else {
-    ws.need(ws.lstats, 8);
-    HIP_TRY(hipMemsetAsync(ws.lstats.get(), 0, 8 * sizeof(unsigned long long), stream));
-    const int32_t step = long_slice_users(H.nusers, nrcmds);
-    for (int32_t s0 = 0; s0 < H.nusers; s0 += step) {
-      HistoryView S = H;
-      S.nusers = std::min(step, H.nusers - s0);
-      if (H.users) S.users = H.users + s0; else S.user0 = H.user0 + s0;
-      queue_scorer(W, S, C, rq, num_cus, stream, ws, F);  // (the exclusion rows go by user id: S names the users)
-      bytes += fetch_lists(ws, S.nusers, nrcmds, stream, output + (int64_t)s0 * nrcmds, scores + (int64_t)s0 * nrcmds,
-                           counts ? counts + s0 : nullptr);
-      ++ls.slices;
-    }
-    unsigned long long h[5] = {};
-    HIP_TRY(hipMemcpyAsync(h, ws.lstats.get(), sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    bytes += sizeof(h);
-    ls.candidates = (int64_t)h[0]; ls.contenders = (int64_t)h[1]; ls.refine_passes = (int64_t)h[2];
-    ls.lds_sorts = (int64_t)h[3]; ls.key_refines = (int64_t)h[4];
-  }
+  const bool served = score_slices(W, H, C, num_cus, stream, ws, F, ls, [&](const HistoryView& S, int32_t s0) {
+    bytes += fetch_lists(ws, S.nusers, C.nrcmds, stream, output + s0 * nrcmds, scores + s0 * nrcmds,
+                         counts ? counts + s0 : nullptr);
+  });
+  if (!served) return kRefused;
+  if (C.path == kLong) bytes += fetch_long_stats(ws, stream, ls);
   ls.path = C.path;
   if (down) *down = bytes;
   g_list_stats = ls;
@@ -479,31 +499,13 @@ ScorerPath score_exposure(const DeviceRowView& W, const HistoryView& H, const Sc
     return kRefused;
   }
   slimgpu_list_stats_t ls = {};
-  const int32_t nrcmds = C.nrcmds, ncols = std::max(W.ncols, 1);
-  const ScorerRequest rq = LongListsRequest{nrcmds};
+  const int32_t ncols = std::max(W.ncols, 1);
   queue_exposure_clear(stream, ncols, cut, ws);
-  if (C.path != kLong) {
-    queue_scorer(W, H, C, rq, num_cus, stream, ws, F);
-    queue_exposure_count(stream, num_cus, ws.oid.get(), ws.ocnt.get(), H.nusers, nrcmds, ncols, cut, ws);
-    ls.slices = 1;
-  } else {
-    ws.need(ws.lstats, 8);
-    HIP_TRY(hipMemsetAsync(ws.lstats.get(), 0, 8 * sizeof(unsigned long long), stream));
-    const int32_t step = long_slice_users(H.nusers, nrcmds);
-    for (int32_t s0 = 0; s0 < H.nusers; s0 += step) {  // (one stream: a slice is counted before the next overwrites it)
-      HistoryView S = H;
-      S.nusers = std::min(step, H.nusers - s0);
-      if (H.users) S.users = H.users + s0; else S.user0 = H.user0 + s0;
-      queue_scorer(W, S, C, rq, num_cus, stream, ws, F);
-      queue_exposure_count(stream, num_cus, ws.oid.get(), ws.ocnt.get(), S.nusers, nrcmds, ncols, cut, ws);
-      ++ls.slices;
-    }
-    unsigned long long h[5] = {};
-    HIP_TRY(hipMemcpyAsync(h, ws.lstats.get(), sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    ls.candidates = (int64_t)h[0]; ls.contenders = (int64_t)h[1]; ls.refine_passes = (int64_t)h[2];
-    ls.lds_sorts = (int64_t)h[3]; ls.key_refines = (int64_t)h[4];
-  }
+  // (score_slices cannot refuse here: queue_scorer refuses a refused choice only, and that was judged above)
+  (void)score_slices(W, H, C, num_cus, stream, ws, F, ls, [&](const HistoryView& S, int32_t) {
+    queue_exposure_count(stream, num_cus, ws.oid.get(), ws.ocnt.get(), S.nusers, C.nrcmds, ncols, cut, ws);
+  });
+  if (C.path == kLong) fetch_long_stats(ws, stream, ls);
   queue_exposure_cumulate(stream, num_cus, ncols, cut, ws);
   ls.path = C.path;
   g_list_stats = ls;
@@ -537,19 +539,14 @@ int32_t predict_view_impl(const DeviceRowView& W, const slim_csr_t* hist, int32_
   const int32_t nusers = hist->nrows;
   if (const int32_t rc = filter_check("SLIMGPU_PredictLists", filter, W.ncols); rc != SLIM_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
-  try {
-    (void)hipGetLastError();  // a failure of an earlier call must not be reported by this one
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
+  return guarded(predict_name(long_ok), [&]() -> int32_t {
+    open_current_device();
     if (W.device >= 0) HIP_TRY(hipSetDevice(W.device));
     const int num_cus = cu_count();
     const StagedCsr h = stage_csr(hist, nusers, /*values=*/true, /*stream=*/nullptr);
-    HistoryView H;
-    H.nusers = nusers; H.max_hist = h.max_row;
-    H.ptr = h.ptr.get(); H.ind = h.ind.get(); H.val = h.val.get();
+    const HistoryView H = staged_history(h, nusers);
     DeviceRowView V = W;
-    if (!V.rows_sorted && V.nnz > 0) V.rows_sorted = rows_ascend_strictly(num_cus, V.nrows, V.d_ptr, V.d_ind);
+    decide_row_order(V, num_cus);
     const ScorerRequest rq = long_ok ? ScorerRequest(LongListsRequest{nrcmds}) : ScorerRequest(ListsRequest{nrcmds});
     const ScorerChoice C = choose_scorer(V, H, rq);
     if (C.chunk_pin_missed)
@@ -572,31 +569,18 @@ int32_t predict_view_impl(const DeviceRowView& W, const slim_csr_t* hist, int32_
                    std::chrono::duration<double, std::milli>(L.launched - t_begin).count());
     fetch_lists(ws, nusers, nrcmds, nullptr, output, scores, counts);
     return SLIM_OK;
-  } catch (const HipFail& e) {
-    return hip_failure(predict_name(long_ok), e);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(predict_name(long_ok)) + ": out of host memory");
-    return SLIM_ERROR_MEMORY;
-  }
+  });
 }
 
 // predict_device (long_ok false) and predict_lists: the model staged, then as above
 int32_t predict_impl(const slim_csr_t* W, const slim_csr_t* hist, int32_t nrcmds, int32_t* output, float* scores,
                      int32_t* counts, bool long_ok, slimgpu_filter* filter = nullptr) {
   if (const int32_t rc = filter_check("SLIMGPU_PredictLists", filter, W->ncols); rc != SLIM_OK) return rc;
-  try {
-    (void)hipGetLastError();
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw HipFail{hipErrorNoDevice, "hipGetDeviceCount"};
+  return guarded(predict_name(long_ok), [&]() -> int32_t {
+    open_current_device();
     const StagedCsr w = stage_csr(W, W->nrows, /*values=*/true, /*stream=*/nullptr);
-    DeviceRowView v;
-    v.nrows = W->nrows; v.ncols = W->ncols; v.nnz = w.nnz; v.max_row = w.max_row;
-    v.d_ptr = w.ptr.get(); v.d_ind = w.ind.get(); v.d_val = w.val.get();
-    return predict_view_impl(v, hist, nrcmds, output, scores, counts, long_ok, filter);
-  } catch (const HipFail& e) {
-    return hip_failure(predict_name(long_ok), e);
-  }
+    return predict_view_impl(staged_row_view(W, w), hist, nrcmds, output, scores, counts, long_ok, filter);
+  });
 }
 }  // namespace
 
