@@ -317,5 +317,7 @@ const char *SLIMGPU_LastError(void);
 #include "slim_gpu_cand.h"
 /* The figures of an evaluation per user group, from the same scoring pass; a grid that selects on one group. */
 #include "slim_gpu_groups.h"
+/* One matrix split into train and test by a published rule, on the host or where the staged matrix lies. */
+#include "slim_gpu_split.h"
 
 #endif /* SLIM_AMD_SLIM_GPU_H_ */

@@ -74,7 +74,7 @@ int32_t SLIMGPU_MatrixPredict(int32_t nrcmds, const slimgpu_model_t *model,
 typedef struct slimgpu_eval_stats_t {
   int32_t path;          /* 1 fused chunk kernel, 2 wave kernel + k_user_terms, 3 ranks (slim_gpu_rank.h),
                             4 long lists (slim_gpu_lists.h), 5 candidate rows (slim_gpu_cand.h),
-                            6 explanations (slim_gpu_explain.h) */
+                            6 explanations (slim_gpu_explain.h), 7 a split (slim_gpu_split.h) */
   int32_t device_allocs; /* device allocations made by this call               */
   int64_t h2d_bytes, d2h_bytes;
   double kernel_ms, total_ms;

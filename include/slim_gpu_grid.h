@@ -57,6 +57,7 @@ typedef struct slimgpu_grid_cell_t {
    refusal *grid is left as it was */
 int32_t SLIMGPU_GridOpen(slim_t *trnhandle, slim_t *tsthandle, int32_t *ioptions, double *doptions, int32_t ncols,
                          int32_t nsolves, slimgpu_filter_t *filter, slimgpu_grid_t **grid);
+/* (SLIMGPU_GridOpenOn, the same grid over a training matrix that is staged already: slim_gpu_split.h) */
 /* the header lines of the modes in use, to stdout: "  evaluating every K-th user ...", "  item filter ...",
    "  sampled negatives ..." */
 void SLIMGPU_GridDescribe(const slimgpu_grid_t *grid);

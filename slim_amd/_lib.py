@@ -359,6 +359,32 @@ GROUP_SYMBOLS = tuple(_GROUP_SIGNATURES)
 MAX_GROUPS = 1024       # SLIMGPU_MAX_GROUPS
 GROUP_CELL = 9          # SLIMGPU_GROUP_CELL: l1, l2, HR, HR_head, HR_tail, ARHR, nvalid, nvalid_head, nvalid_tail
 
+
+class Split(C.Structure):
+    """slimgpu_split_t (include/slim_gpu_split.h): the parameters of a train / test split."""
+    _fields_ = [("mode", C.c_int32), ("nfolds", C.c_int32), ("fold", C.c_int32), ("nheld", C.c_int32),
+                ("minkeep", C.c_int32), ("seed", C.c_uint64)]
+
+
+# one matrix split into train and test, on the host or where the staged matrix lies (include/slim_gpu_split.h), and
+# the grid on a staged matrix and cross-validated over such folds
+_SPLIT_SIGNATURES = {
+    "SLIMGPU_SplitHost": (C.c_int32, [C.c_void_p, C.POINTER(Split), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "SLIMGPU_MatrixSplit": (C.c_int32, [C.c_void_p, C.POINTER(Split), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "SLIMGPU_GridOpenOn": (C.c_int32, [C.c_void_p, C.c_void_p, i32_1d, f64_1d, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.POINTER(C.c_void_p)]),
+    "Py_SLIM_MselectCV": (C.c_int32, [C.c_void_p, i32_1d, f64_1d, f64_1d, f64_1d, C.c_int32, C.c_int32,
+                                      C.POINTER(Split), C.c_void_p] + [C.c_void_p] * 9),
+    "SLIMGPU_MselectCVPairs": (C.c_int32, [C.c_void_p, i32_1d, f64_1d, C.c_int32, f64_1d, f64_1d, C.POINTER(Split),
+                                           C.c_void_p, f64_1d, C.c_void_p]),
+}
+
+SPLIT_SYMBOLS = tuple(_SPLIT_SIGNATURES)
+SPLIT_LEAVE_OUT, SPLIT_FOLDS = 0, 1     # SLIMGPU_SPLIT_LEAVE_OUT, SLIMGPU_SPLIT_FOLDS
+SPLIT_MAX_HELD = 128                    # SLIMGPU_SPLIT_MAX_HELD
+EVAL_PATH_SPLIT = 7                     # SLIMGPU_EVAL_PATH_SPLIT
+CV_CELL = 11                            # SLIMGPU_CV_CELL: fold, l1, l2, HR, HR_head, HR_tail, ARHR, 3 nvalid, nnz
+
 _lib = None
 
 
@@ -379,7 +405,7 @@ def load():
                               list(_CAND_SIGNATURES.items()) + list(_SAMPLE_SIGNATURES.items()) +
                               list(_WSAMPLE_SIGNATURES.items()) + list(_EXPLAIN_SIGNATURES.items()) +
                               list(_EXPOSURE_SIGNATURES.items()) + list(_GRID_SIGNATURES.items()) +
-                              list(_GROUP_SIGNATURES.items())):
+                              list(_GROUP_SIGNATURES.items()) + list(_SPLIT_SIGNATURES.items())):
         if os.environ.get("SLIM_AMD_LIB") and not hasattr(lib, name):
             continue  # an older build used for an A/B run may lack the newest entry points
         fn = getattr(lib, name)  # AttributeError here = ABI drift, fail loudly

@@ -260,6 +260,9 @@ int32_t matrix_predict_exposure(slimgpu_matrix_t* mat, const slimgpu_model* mode
 int32_t model_evaluate_exposure(slimgpu_evalset_t* es, const slimgpu_model* model, slimgpu_filter* filter,
                                 int32_t ncutoffs, EvalResult* out, uint32_t* exposure, slimgpu_exposure_t* summary);
 slimgpu_eval_stats_t& last_eval_stats();
+// split.hip (slim_gpu_split.h): the train half staged on the source's device (the new handle owns its arrays), the
+// test half as a host matrix (csr_free releases it).  SLIM_ERROR_INPUT with the outputs untouched on a refusal.
+int32_t matrix_split(slimgpu_matrix_t* src, const slimgpu_split_t* split, slimgpu_matrix_t** trn, slim_csr_t** tst);
 // facts of a row view, for the scorers: d_facts[0] = entries of its longest row, d_facts[1] = 1 when the
 // ids of some row do not ascend strictly (both preset to 0 by the caller).  Queues one kernel on
 // `stream` (a hipStream_t); throws HipFail when the launch fails.

@@ -112,7 +112,23 @@ bool env_is_0(const char* name) {
   return e && std::atoi(e) == 0;
 }
 
+// where the models of a grid live: the number of GPUs and the two switches of the environment, read here alone
+void read_route(const int32_t* ioptions, LearnOptions* base, bool* keep_on_host, bool* eval_on_host) {
+  // (SLIM_GPU_NGPUS for callers that cannot set the slot: the unchanged reference CLIs and Python wrapper)
+  if (slot(ioptions, SLIM_OPTION_GPU_NGPUS, -1) == -1)
+    if (const char* e = std::getenv("SLIM_GPU_NGPUS")) base->ngpus = std::max(1, std::atoi(e));
+  *keep_on_host = env_is_0("SLIM_GPU_RESIDENT");
+  *eval_on_host = env_is_0("SLIM_GPU_EVAL_RESIDENT");
+}
+
 }  // namespace
+
+bool grid_can_open_on(const int32_t* ioptions, const double* doptions) {
+  LearnOptions base = decode_options(ioptions, doptions);
+  bool keep_on_host = false, eval_on_host = false;
+  read_route(ioptions, &base, &keep_on_host, &eval_on_host);
+  return base.algo == SLIM_ALGO_CD && base.ngpus <= 1 && !keep_on_host && !eval_on_host;
+}
 
 slimgpu_grid::~slimgpu_grid() {
   csr_free(model);
@@ -137,11 +153,7 @@ int32_t slimgpu_grid::decode(const int32_t* ioptions, const double* doptions) {
     set_error("Py_SLIM_Mselect: SLIM_OPTION_GPU_EVALSTRIDE must be at least 1");
     return SLIM_ERROR_INPUT;
   }
-  // (SLIM_GPU_NGPUS for callers that cannot set the slot: the unchanged reference CLIs and Python wrapper)
-  if (slot(ioptions, SLIM_OPTION_GPU_NGPUS, -1) == -1)
-    if (const char* e = std::getenv("SLIM_GPU_NGPUS")) base.ngpus = std::max(1, std::atoi(e));
-  keep_on_host = env_is_0("SLIM_GPU_RESIDENT");
-  eval_on_host = env_is_0("SLIM_GPU_EVAL_RESIDENT");
+  read_route(ioptions, &base, &keep_on_host, &eval_on_host);
   // sampled negatives (slim_gpu_cand.h), drawn uniformly or by item popularity (slim_gpu_sample.h); exposure
   evalnegs = slot(ioptions, SLIM_OPTION_GPU_EVALNEGS, 0);
   evalseed = (uint64_t)(uint32_t)slot(ioptions, SLIM_OPTION_GPU_EVALSEED, 1);
@@ -154,7 +166,9 @@ int32_t slimgpu_grid::decode(const int32_t* ioptions, const double* doptions) {
                     "SLIM_OPTION_GPU_EVALNEGS is off: there is nothing to weight");
     return SLIM_ERROR_INPUT;
   }
-  nall = std::min(trn->nrows, tst->nrows);
+  int32_t trn_rows = trn ? trn->nrows : 0;
+  if (!trn) matrix_info(mat, &trn_rows, nullptr, nullptr);
+  nall = std::min(trn_rows, tst->nrows);
   if (stride > 1)
     for (int64_t u = 0; u < nall; u += stride) sel.push_back((int32_t)u);
   return SLIM_OK;
@@ -207,11 +221,65 @@ int32_t slimgpu_grid::open(const int32_t* ioptions, const double* doptions, int3
   fmarker = head_tail_split(trn->nrows, ncols, trn->rowptr, trn->rowind);
   if (mat) make_evalset();
   status = check_needs(true);
-  if (status != SLIM_OK || evalnegs <= 0) return status;
-  // the candidate set is drawn once, on the device, from the eval set's users; every pair is evaluated on it
+  return status != SLIM_OK ? status : sample_candidates();
+}
+
+// the candidate set is drawn once, on the device, from the eval set's users; every pair is evaluated on it
+int32_t slimgpu_grid::sample_candidates() {
+  if (evalnegs <= 0) return SLIM_OK;
+  int32_t status = SLIM_ERROR;
   cands = evalnegpop ? evalset_sample_candidates_weighted(evalset, evalnegs, evalseed, nullptr, &status)
                      : evalset_sample_candidates(evalset, evalnegs, evalseed, &status);
   return cands ? SLIM_OK : refuse(kFeatures[0], last_error());
+}
+
+// A grid on a matrix that is staged already (a train half made by SLIMGPU_MatrixSplit): nothing of the training rows
+// is on the host, so the models stay in HBM and are evaluated there, or the grid is refused.  The marker is formed
+// from the matrix's column pointer: head_tail_split reads the entry count of every item and the count of all entries,
+// and the pointer holds both.
+int32_t slimgpu_grid::open_on(slimgpu_matrix_t* staged, const int32_t* ioptions, const double* doptions,
+                              int32_t marker_ncols, int32_t nsolves) {
+  const std::string who = "SLIMGPU_GridOpenOn: ";
+  auto refuse_on = [&](const std::string& why) {
+    mat = nullptr;  // (the matrix stays the caller's)
+    set_error(who + why);
+    return (int32_t)SLIM_ERROR_INPUT;
+  };
+  mat = staged;
+  int32_t status = decode(ioptions, doptions);
+  if (status == SLIM_OK) status = check_needs(false);
+  if (status != SLIM_OK) {
+    mat = nullptr;
+    return status;
+  }
+  const char* on_device = "a grid on a staged matrix keeps its models in HBM and evaluates them there: ";
+  if (admm) return refuse_on(std::string(on_device) + "the ADMM solver leaves no model in HBM");
+  if (several_gpus(*this) || !matrix_replicas(mat).empty()) return refuse_on(std::string(on_device) + kSeveral);
+  if (keep_on_host) return refuse_on(std::string(on_device) + "SLIM_GPU_RESIDENT=0 keeps the models on the host");
+  if (eval_on_host) return refuse_on(std::string(on_device) + "SLIM_GPU_EVAL_RESIDENT=0 evaluates through the host");
+  if (nrcmds < 1) return refuse_on(std::string(on_device) + nrcmds_is(*this));
+  int32_t mrows = 0, mcols = 0;
+  int64_t mnnz = 0;
+  matrix_info(mat, &mrows, &mcols, &mnnz);
+  ncols = marker_ncols > 0 ? marker_ncols : std::max(mcols, max_index_plus_one(tst->rowptr[tst->nrows], tst->rowind));
+  std::vector<int64_t> cp((size_t)mcols + 1, 0), pop((size_t)ncols, 0);
+  if (matrix_get_column_view(mat, cp.data(), nullptr, nullptr, nullptr) != SLIM_OK)
+    return refuse_on("the staged matrix has no column view");
+  for (int32_t i = 0; i < std::min(ncols, mcols); ++i) pop[(size_t)i] = cp[(size_t)i + 1] - cp[(size_t)i];
+  fmarker = head_tail_from_counts(ncols, pop, mnnz);
+  make_evalset();
+  if (!evalset)
+    return refuse_on(std::string(on_device) +
+                     (*last_error() ? std::string(last_error()) : std::string("the eval set could not be made")));
+  status = check_needs(true);
+  if (status == SLIM_OK) status = sample_candidates();
+  if (status != SLIM_OK) {
+    mat = nullptr;
+    return status;
+  }
+  // (behind the last refusal: a matrix that goes back to the caller goes back as it came)
+  matrix_expect_solves(mat, nsolves);
+  return SLIM_OK;
 }
 
 // Groups ride on the eval set: a grid without one has nothing to form them from, and is refused rather than
@@ -309,6 +377,7 @@ int32_t slimgpu_grid::evaluate_in_hbm(EvalResult* ev, slimgpu_exposure_t* expo) 
 // A plain grid without the eval set: top-N of every user on the GPU (bit-identical to the host scorer) and the hits
 // counted there; where the device refuses either, the host loop, which needs the host model.
 int32_t slimgpu_grid::evaluate_lists(EvalResult* ev) {
+  if (!trn) return SLIM_ERROR;  // (a grid on a staged matrix has no host rows to score: it is evaluated in HBM)
   std::vector<int32_t> lists((size_t)trn->nrows * nrcmds, -1), lens((size_t)trn->nrows, 0);
   std::vector<float> lsc((size_t)trn->nrows * nrcmds, 0.0f);
   bool on_gpu;
@@ -374,6 +443,18 @@ int32_t SLIMGPU_GridOpen(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions
   set_error("");
   slimgpu_grid* g = new slimgpu_grid(trn, tst, filter);
   const int32_t status = g->open(ioptions, doptions, ncols, nsolves);
+  if (status == SLIM_OK) *grid = g;
+  else delete g;
+  return status;
+}
+
+int32_t SLIMGPU_GridOpenOn(slimgpu_matrix_t* trn, slim_t* tsthandle, int32_t* ioptions, double* doptions,
+                           int32_t ncols, int32_t nsolves, slimgpu_filter_t* filter, slimgpu_grid_t** grid) {
+  const slim_csr_t* tst = static_cast<slim_csr_t*>(tsthandle);
+  if (!trn || !tst || !tst->rowptr || !grid) return SLIM_ERROR_INPUT;
+  set_error("");
+  slimgpu_grid* g = new slimgpu_grid(nullptr, tst, filter);
+  const int32_t status = g->open_on(trn, ioptions, doptions, ncols, nsolves);
   if (status == SLIM_OK) *grid = g;
   else delete g;
   return status;

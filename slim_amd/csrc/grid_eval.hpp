@@ -13,9 +13,14 @@ namespace slimamd {
 int predict_policy();  // SLIM_PREDICT (slim_abi.cpp)
 }
 
+// Whether a grid with these options keeps its models in HBM and evaluates them there (cd, one GPU, SLIM_GPU_RESIDENT
+// and SLIM_GPU_EVAL_RESIDENT not 0): the grids that SLIMGPU_GridOpenOn can serve.  Py_SLIM_MselectCV picks its route
+// by it.
+bool grid_can_open_on(const int32_t* ioptions, const double* doptions);
+
 struct slimgpu_grid {
   // the request, decoded once by open()
-  const slim_csr_t* trn = nullptr;  // (borrowed, as is the filter)
+  const slim_csr_t* trn = nullptr;  // (borrowed, as is the filter; none for a grid opened on a staged matrix)
   const slim_csr_t* tst = nullptr;
   slimgpu_filter_t* filter = nullptr;
   slimamd::LearnOptions base;
@@ -45,6 +50,10 @@ struct slimgpu_grid {
   // the plan: everything is decided, staged and sampled here, before the first solve.  SLIM_OK, or the status of
   // the refusal with its reason as the error text
   int32_t open(const int32_t* ioptions, const double* doptions, int32_t marker_ncols, int32_t nsolves);
+  // SLIMGPU_GridOpenOn: the same plan over a matrix that is staged already (trn == nullptr).  The grid owns `staged`
+  // once this returns SLIM_OK; on a refusal it stays the caller's
+  int32_t open_on(slimgpu_matrix_t* staged, const int32_t* ioptions, const double* doptions, int32_t marker_ncols,
+                  int32_t nsolves);
   void describe() const;
   // slim_gpu_groups.h, between open() and the first solve: the eval set forms the group rows of every pair
   int32_t set_groups(int32_t ngroups_, const int32_t* group_of_user, int32_t select_group_);
@@ -57,6 +66,7 @@ struct slimgpu_grid {
   int32_t decode(const int32_t* ioptions, const double* doptions);
   int32_t check_needs(bool staged);
   void make_evalset();
+  int32_t sample_candidates();
   int32_t learn(const slimamd::LearnOptions& opt);
   int32_t evaluate_in_hbm(slimamd::EvalResult* ev, slimgpu_exposure_t* expo);
   int32_t evaluate_lists(slimamd::EvalResult* ev);

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <numeric>
 #include <thread>
 
@@ -444,16 +445,20 @@ void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr
 
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,
                          const int32_t* rowind) {
-  int32_t* mark = xmalloc<int32_t>(ncols);
   std::vector<int64_t> pop(ncols, 0);
   for (ssize_t k = 0; k < rowptr[nrows]; ++k)
     if (rowind[k] >= 0 && rowind[k] < ncols) ++pop[rowind[k]];
+  return head_tail_from_counts(ncols, pop, rowptr[nrows]);
+}
+
+int32_t* head_tail_from_counts(int32_t ncols, const std::vector<int64_t>& pop, int64_t nnz) {
+  int32_t* mark = xmalloc<int32_t>(ncols);
   std::vector<int32_t> by_pop(ncols);
   std::iota(by_pop.begin(), by_pop.end(), 0);
   std::stable_sort(by_pop.begin(), by_pop.end(),
                    [&](int32_t a, int32_t b) { return pop[a] > pop[b]; });
   std::fill(mark, mark + ncols, 1);
-  int64_t budget = rowptr[nrows] / 2;
+  int64_t budget = nnz / 2;
   for (int32_t c = 0; c < ncols && budget > 0; ++c) {
     mark[by_pop[c]] = 0;
     budget -= pop[by_pop[c]];
@@ -717,4 +722,142 @@ int32_t group_partition(const char* who, int32_t nsel, const int32_t* users, int
   return SLIM_OK;
 }
 
+// ---- slim_gpu_split.h ---------------------------------------------------------
+int32_t split_check(const char* who, const slimgpu_split_t* s) {
+  std::string what;
+  if (!s) {
+    what = "bad arguments (the split's parameters)";
+  } else {
+    const bool leave = s->mode == SLIMGPU_SPLIT_LEAVE_OUT, folds = s->mode == SLIMGPU_SPLIT_FOLDS;
+    if (!leave && !folds)
+      what = "mode must be SLIMGPU_SPLIT_LEAVE_OUT (0) or SLIMGPU_SPLIT_FOLDS (1), not " + std::to_string(s->mode);
+    else if (s->nfolds < (folds ? 2 : 1))
+      what = std::string("nfolds must be at least ") + (folds ? "2 in folds mode" : "1") + ", not " +
+             std::to_string(s->nfolds);
+    else if (s->fold < 0 || s->fold >= s->nfolds)
+      what = "fold " + std::to_string(s->fold) + " is outside [0, " + std::to_string(s->nfolds) + ")";
+    else if (s->minkeep < 1)
+      what = "minkeep must be at least 1, not " + std::to_string(s->minkeep);
+    else if (leave && s->nheld < 1)
+      what = "nheld must be at least 1, not " + std::to_string(s->nheld);
+    else if (leave && (int64_t)s->nfolds * s->nheld > SLIMGPU_SPLIT_MAX_HELD)
+      what = "nfolds * nheld is " + std::to_string((int64_t)s->nfolds * s->nheld) + ", above " +
+             std::to_string(SLIMGPU_SPLIT_MAX_HELD) + ": the selection keeps that many smallest keys per row";
+  }
+  if (what.empty()) return SLIM_OK;
+  set_error(std::string(who) + ": " + what);
+  return SLIM_ERROR_INPUT;
+}
+
+int32_t split_host(const slim_csr_t* data, const slimgpu_split_t& s, slim_csr_t** trn, slim_csr_t** tst) {
+  const int32_t nrows = data->nrows;
+  const ssize_t* ptr = data->rowptr;
+  const int32_t* ind = data->rowind;
+  const float* val = data->rowval;
+  const int64_t nnz = ptr[nrows];
+  for (int64_t k = 0; k < nnz; ++k)
+    if (ind[k] < 0) {
+      set_error("SLIMGPU_SplitHost: entry " + std::to_string(k) + " has item id " + std::to_string(ind[k]) +
+                ", below 0");
+      return SLIM_ERROR_INPUT;
+    }
+  const bool leave = s.mode == SLIMGPU_SPLIT_LEAVE_OUT;
+  const uint64_t F = (uint64_t)s.nfolds, f = (uint64_t)s.fold;
+  const int64_t h = s.nheld, m = s.minkeep;
+  std::vector<uint8_t> held((size_t)nnz, 0);
+  std::vector<ssize_t> tptr((size_t)nrows + 1, 0);
+  struct Rec {
+    uint64_t key;
+    int32_t item;
+    int64_t pos;
+    bool operator<(const Rec& o) const {
+      return key != o.key ? key < o.key : item != o.item ? item < o.item : pos < o.pos;
+    }
+  };
+  std::vector<Rec> recs;
+  for (int32_t u = 0; u < nrows; ++u) {
+    const int64_t r0 = ptr[u], L = ptr[u + 1] - r0;
+    const uint64_t base = sample_base(s.seed, (uint64_t)u);
+    int64_t out = 0;
+    if (leave) {
+      if (L >= (int64_t)F * h + m) {
+        recs.clear();
+        for (int64_t p = 0; p < L; ++p) recs.push_back({sample_key(base, (uint64_t)ind[r0 + p]), ind[r0 + p], p});
+        const int64_t lo = (int64_t)f * h, hi = lo + h;  // ranks [lo, hi)
+        std::partial_sort(recs.begin(), recs.begin() + hi, recs.end());
+        for (int64_t r = lo; r < hi; ++r) held[(size_t)(r0 + recs[(size_t)r].pos)] = 1;
+        out = h;
+      }
+    } else {
+      int64_t inside = 0;
+      for (int64_t p = 0; p < L; ++p)
+        inside += sample_mulhi64(sample_key(base, (uint64_t)ind[r0 + p]), F) == f;
+      if (inside >= 1 && L - inside >= m) {
+        for (int64_t p = 0; p < L; ++p)
+          held[(size_t)(r0 + p)] = sample_mulhi64(sample_key(base, (uint64_t)ind[r0 + p]), F) == f;
+        out = inside;
+      }
+    }
+    tptr[(size_t)u + 1] = tptr[(size_t)u] + out;
+  }
+  const int64_t nt = tptr[(size_t)nrows], nk = nnz - nt;
+  slim_csr_t* halves[2] = {csr_new(), csr_new()};  // train, test
+  bool ok = halves[0] && halves[1];
+  for (int w = 0; w < 2 && ok; ++w) {
+    slim_csr_t* o = halves[w];
+    const int64_t n = w ? nt : nk;
+    o->nrows = nrows;
+    o->rowptr = xmalloc<ssize_t>((size_t)nrows + 1);
+    o->rowind = xmalloc<int32_t>((size_t)n);
+    o->rowval = val ? xmalloc<float>((size_t)n) : nullptr;
+    ok = o->rowptr && o->rowind && (!val || o->rowval);
+  }
+  if (!ok) {
+    csr_free(halves[0]);
+    csr_free(halves[1]);
+    set_error("SLIMGPU_SplitHost: out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+  int64_t at[2] = {0, 0};
+  for (int32_t u = 0; u < nrows; ++u) {
+    halves[0]->rowptr[u] = at[0];
+    halves[1]->rowptr[u] = at[1];
+    for (int64_t k = ptr[u]; k < ptr[u + 1]; ++k) {
+      const int w = held[(size_t)k];
+      halves[w]->rowind[at[w]] = ind[k];
+      if (val) halves[w]->rowval[at[w]] = val[k];
+      ++at[w];
+    }
+  }
+  for (int w = 0; w < 2; ++w) {
+    halves[w]->rowptr[nrows] = at[w];
+    halves[w]->ncols = max_index_plus_one(at[w], halves[w]->rowind);
+  }
+  *trn = halves[0];
+  *tst = halves[1];
+  return SLIM_OK;
+}
+
 }  // namespace slimamd
+
+extern "C" int32_t SLIMGPU_SplitHost(slim_t* data, const slimgpu_split_t* split, slim_t** trn, slim_t** tst) {
+  using namespace slimamd;
+  set_error("");
+  const slim_csr_t* d = static_cast<const slim_csr_t*>(data);
+  if (!d || !d->rowptr || d->nrows < 0 || (d->rowptr[d->nrows] > 0 && !d->rowind) || !trn || !tst) {
+    set_error("SLIMGPU_SplitHost: bad arguments (a matrix with a row view, the two outputs)");
+    return SLIM_ERROR_INPUT;
+  }
+  if (const int32_t rc = split_check("SLIMGPU_SplitHost", split); rc != SLIM_OK) return rc;
+  slim_csr_t *a = nullptr, *b = nullptr;
+  try {
+    const int32_t rc = split_host(d, *split, &a, &b);
+    if (rc != SLIM_OK) return rc;
+  } catch (const std::bad_alloc&) {
+    set_error("SLIMGPU_SplitHost: out of host memory");
+    return SLIM_ERROR_MEMORY;
+  }
+  *trn = a;
+  *tst = b;
+  return SLIM_OK;
+}

@@ -133,6 +133,9 @@ void sample_candidates_host(int32_t ncols, const slim_csr_t* trn, const slim_csr
 // api.c:215-245.  malloc'd marker array (0 head / 1 tail).
 int32_t* head_tail_split(int32_t nrows, int32_t ncols, const ssize_t* rowptr,
                          const int32_t* rowind);
+// its second half: the marker from the entry count of every item (pop[ncols]) and the count of all entries, which is
+// all that head_tail_split reads of the rows (a staged matrix has both in its column pointer)
+int32_t* head_tail_from_counts(int32_t ncols, const std::vector<int64_t>& pop, int64_t nnz);
 
 struct EvalResult {
   float hr = 0, hr_head = 0, hr_tail = 0, arhr = 0;
@@ -173,6 +176,12 @@ void exposure_summary(int32_t ncols, const uint32_t* pop, const int32_t* fmarker
 // [0, nall), a user outside [0, nall).
 int32_t group_partition(const char* who, int32_t nsel, const int32_t* users, int32_t nall, int32_t ngroups,
                         const int32_t* group_of_user, int32_t* order, int64_t* offsets);
+
+// slim_gpu_split.h on the host.  split_check: the parameters alone (SLIM_OK, or SLIM_ERROR_INPUT with "<who>: ..." as
+// the error text).  split_host: the definition in code, one thread; *trn and *tst are matrices as csr_from_rows makes
+// them and are written only on SLIM_OK.  The device kernels (split.hip) hash with the same helpers.
+int32_t split_check(const char* who, const slimgpu_split_t* s);
+int32_t split_host(const slim_csr_t* data, const slimgpu_split_t& s, slim_csr_t** trn, slim_csr_t** tst);
 
 // ---- files ------------------------------------------------------------------
 bool write_binrow(const slim_csr_t* m, const char* path);   // api.c:174-177

@@ -1,7 +1,8 @@
 // slim_mselect -- model selection over the (l1, l2) pairs of an l12 file, warm-starting
 // every model from the previous one; R is staged in HBM once for the whole grid.
 // Usage and options as /root/reference/src/programs/slim_mselect.c and cmdline_mselect.c
-// (slim_mselect [options] train-file test-file l12-file).
+// (slim_mselect [options] train-file test-file l12-file).  With -cvfolds=F there is ONE data file: the library holds
+// items out itself and runs the pairs once per fold (include/slim_gpu_split.h: slim_mselect -cvfolds=F data-file l12-file).
 #include "cli_common.hpp"
 #include "../../../include/slim_gpu_grid.h"
 using namespace slimcli;
@@ -12,11 +13,25 @@ int main(int argc, char** argv) {
       {"nnbrs", true},   {"simtype", true},   {"algo", true},    {"nthreads", true},
       {"nrcmds", true},  {"dbglvl", true},    {"nomodels", false}, {"ngpus", true},
       {"evalstride", true}, {"evalnegs", true}, {"evalseed", true}, {"evalnegpop", false}, {"evalexposure", false}, {"gpukernel", true}, {"help", false},
-      {"evalgroupfile", true}, {"evalhistbands", true}, {"evalselectgroup", true}};
+      {"evalgroupfile", true}, {"evalhistbands", true}, {"evalselectgroup", true},
+      {"cvfolds", true}, {"cvmode", true}, {"cvheld", true}, {"cvminkeep", true}, {"cvseed", true}};
   specs.insert(specs.end(), std::begin(kFilterSpecs), std::end(kFilterSpecs));
   Args a = parse_args(argc, argv, specs);
-  if (a.has("help") || a.pos.size() != 3) {
+  const bool cv = a.has("cvfolds");
+  if (cv && !a.has("help") && a.pos.size() == 3)
+    die("-cvfolds holds items out of ONE data file: slim_mselect -cvfolds=F [options] data-file l12-file (two files, not "
+        "three).");
+  for (const char* k : {"cvmode", "cvheld", "cvminkeep", "cvseed"})
+    if (a.has(k) && !cv) die(std::string("-") + k + " describes the folds of -cvfolds: it needs -cvfolds.");
+  if (a.has("help") || a.pos.size() != (cv ? 2u : 3u)) {
     std::printf("\n Usage: slim_mselect [options] train-file test-file l12-file\n"
+                "        slim_mselect -cvfolds=F [options] data-file l12-file\n"
+                "   -cvfolds=F [-cvmode=leaveout|folds] [-cvheld=h] [-cvminkeep=m] [-cvseed=s]  (engine extension: one\n"
+                "   interactions file; the library holds items out itself, reproducibly from the seed (default 1), and runs\n"
+                "   the pairs once per fold; a pair is judged by the mean of its fold figures.  leaveout (default): every\n"
+                "   user with at least F * h + m entries holds out h (default 1) in each fold, F * h <= 128; folds: every\n"
+                "   entry belongs to one of F >= 2 folds; m (default 1): entries a user's train row must keep.  No model\n"
+                "   files are written, and the group options do not combine with it)\n"
                 "   -ifmt=csr|csrnv|cluto|ijv  -binarize  -optTol=f  -niters=i  -nnbrs=i  -simtype=s\n"
                 "   -nrcmds=i  -nthreads=i  -dbglvl=i  -nomodels (do not write '<l1 l2>.model' files)\n"
                 "   -ngpus=i   (engine extension: R replicated on i GPUs, every model sharded over them)\n"
@@ -83,7 +98,23 @@ int main(int argc, char** argv) {
   if (evalnegs > 0 && filtered) die("-evalnegs takes no item filter: candidate rows are scored as they are.");
   if (evalnegs > 0 && nrcmds > 128)
     die("-evalnegs needs nrcmds <= 128 (the candidate lists use the eval set's cutoffs), not " + std::to_string(nrcmds) + ".");
-  Csr trn = read_matrix(a.pos[0], fmt), tst = read_matrix(a.pos[1], fmt);
+  if (cv && grouped) die("-cvfolds does not combine with -evalgroupfile / -evalhistbands: groups inside a cross-validated grid are not built.");
+  slimgpu_split_t split = {};
+  if (cv) {
+    const std::string mode = a.str("cvmode", "leaveout");
+    if (mode != "leaveout" && mode != "folds") die("Invalid -cvmode of " + mode + ": leaveout or folds.");
+    split.mode = mode == "folds" ? SLIMGPU_SPLIT_FOLDS : SLIMGPU_SPLIT_LEAVE_OUT;
+    split.nfolds = a.integer("cvfolds", 0);
+    split.nheld = a.integer("cvheld", 1);
+    split.minkeep = a.integer("cvminkeep", 1);
+    split.seed = a.has("cvseed") ? std::strtoull(a.str("cvseed", "1").c_str(), nullptr, 10) : 1;
+    if (split.nfolds < (split.mode == SLIMGPU_SPLIT_FOLDS ? 2 : 1)) die("Invalid -cvfolds of " + a.str("cvfolds", "") + ".");
+    if (split.nheld < 1) die("Invalid -cvheld of " + a.str("cvheld", "") + ".");
+    if (split.minkeep < 1) die("Invalid -cvminkeep of " + a.str("cvminkeep", "") + ".");
+    if (split.mode == SLIMGPU_SPLIT_LEAVE_OUT && (long long)split.nfolds * split.nheld > SLIMGPU_SPLIT_MAX_HELD)
+      die("-cvfolds times -cvheld is above " + std::to_string(SLIMGPU_SPLIT_MAX_HELD) + ".");
+  }
+  Csr trn = read_matrix(a.pos[0], fmt), tst = cv ? Csr() : read_matrix(a.pos[1], fmt);
   if (a.has("binarize")) trn.has_val = false;
   // the group of every user row of the training matrix: the file's, or the band of the row's length
   std::vector<int32_t> group_of_user;
@@ -114,9 +145,14 @@ int main(int argc, char** argv) {
         std::to_string(ngroups - 1) + ".");
   const std::string sim = a.str("simtype", "cos");
   banner();
-  std::printf("  trnfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[0].c_str(), trn.nrows, trn.ncols, trn.nnz());
-  std::printf("  tstfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[1].c_str(), tst.nrows, tst.ncols, tst.nnz());
-  std::printf("  l12file: %s\n", a.pos[2].c_str());
+  const std::string l12file = a.pos[cv ? 1 : 2];
+  if (cv) {
+    std::printf("  datafile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[0].c_str(), trn.nrows, trn.ncols, trn.nnz());
+  } else {
+    std::printf("  trnfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[0].c_str(), trn.nrows, trn.ncols, trn.nnz());
+    std::printf("  tstfile: %s, nrows: %d, ncols: %d, nnz: %zd\n", a.pos[1].c_str(), tst.nrows, tst.ncols, tst.nnz());
+  }
+  std::printf("  l12file: %s\n", l12file.c_str());
 
   int32_t io[SLIM_NOPTIONS];
   double dopt[SLIM_NOPTIONS];
@@ -141,7 +177,7 @@ int main(int argc, char** argv) {
   if (evalexposure) io[SLIM_OPTION_GPU_EVALEXPOSURE] = 1;
   io[SLIM_OPTION_NRCMDS] = nrcmds;
 
-  FILE* lf = std::fopen(a.pos[2].c_str(), "r");
+  FILE* lf = std::fopen(l12file.c_str(), "r");
   char line[256];
   int32_t npairs = 0;  // one R, as many solves as the file has pairs: the engine plans for that
   for (double l1, l2; std::fgets(line, sizeof line, lf);)
@@ -150,6 +186,27 @@ int main(int argc, char** argv) {
   // the filter is as wide as the resident models: the staged matrix's largest id + 1
   CliFilter flt;
   if (filtered) flt = read_filter(a, trn.ind.empty() ? 0 : *std::max_element(trn.ind.begin(), trn.ind.end()) + 1, fmt);
+  if (cv) {  // the library's cross-validated driver over the file's pairs: per fold a split and a grid
+    std::vector<double> pl1, pl2;
+    for (double l1, l2; std::fgets(line, sizeof line, lf);)
+      if (std::sscanf(line, "%lf %lf", &l1, &l2) == 2) {
+        pl1.push_back(l1);
+        pl2.push_back(l2);
+      }
+    std::fclose(lf);
+    if (pl1.empty()) die("The l12 file " + l12file + " holds no pair.");
+    slim_t* data = to_handle(trn);
+    double best[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::fflush(stdout);
+    if (SLIMGPU_MselectCVPairs(data, io, dopt, (int32_t)pl1.size(), pl1.data(), pl2.data(), &split, flt.handle, best,
+                               nullptr) != SLIM_OK)
+      die(std::string("cannot cross-validate this grid: ") + SLIMGPU_LastError());
+    std::printf("\nbest mean hr: %.4f at l1 %.4g l2 %.4g; best mean arhr: %.4f at l1 %.4g l2 %.4g\n", best[2], best[0],
+                best[1], best[7], best[4], best[5]);
+    SLIMGPU_FilterFree(flt.handle);
+    Py_csr_free(data);
+    return 0;
+  }
   // staging, residency, the eval set, the sampler and how a pair is evaluated: the library's grid (slim_gpu_grid.h),
   // which refuses here, before the first solve, what it cannot evaluate as asked
   slim_t* hold = to_handle(trn);

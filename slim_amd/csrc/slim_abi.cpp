@@ -357,6 +357,154 @@ int32_t Py_SLIM_Mselect(slim_t* trnhandle, slim_t* tsthandle, int32_t* ioptions,
                                  bestl2HR, bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR, bestARAR, nullptr);
 }
 
+// The cross-validated grid (slim_gpu_split.h): mselect_impl's loop once per fold, a pair judged by the mean of its
+// fold figures.  One route per call: the data staged once and every fold cut where it lies, the grid opened on the
+// train half; or, where that cannot serve, every fold split on the host and its grid opened from the host handles.
+// pl1 / pl2: the pairs in the order they are solved (Py_SLIM_MselectCV: the product of its two arrays, l1 outer; the
+// command-line program: the lines of its l12 file).
+static int32_t mselect_cv_impl(const char* who, slim_t* datahandle, int32_t* ioptions, double* doptions,
+                               const int32_t npairs, const double* pl1, const double* pl2, const slimgpu_split_t* split,
+                               slimgpu_filter_t* filter, double* bestl1HR, double* bestl2HR, double* bestHRHR,
+                               double* bestARHR, double* bestl1AR, double* bestl2AR, double* bestHRAR, double* bestARAR,
+                               double* cells) {
+  const slim_csr_t* data = as_csr(datahandle);
+  set_error("");
+  if (!data || !data->rowptr || !doptions || !pl1 || !pl2 || npairs < 1 || !bestl1HR || !bestl2HR || !bestHRHR ||
+      !bestARHR || !bestl1AR || !bestl2AR || !bestHRAR || !bestARAR) {
+    set_error(std::string(who) + ": bad arguments (a matrix, the options, the pairs, the eight outputs)");
+    return SLIM_ERROR_INPUT;
+  }
+  slimgpu_split_t sp = {};
+  if (split) sp = *split;
+  sp.fold = 0;  // (not read: every fold is run)
+  if (const int32_t rc = split_check(who, split ? &sp : nullptr); rc != SLIM_OK) return rc;
+  const int32_t F = sp.nfolds;
+  const LearnOptions base = decode_options(ioptions, doptions);
+  const bool on_device = grid_can_open_on(ioptions, doptions);
+  int32_t rc = SLIM_OK;
+  slimgpu_matrix_t* staged = nullptr;
+  if (on_device) {
+    staged = matrix_from_host(data->nrows, data->rowptr, data->rowind, data->rowval, base, &rc);
+    if (!staged) return rc;
+  }
+  std::printf("------------------------------------------------------------------\n");
+  std::printf("SLIM, version %s (MI355X engine)\n", SLIM_VERSION);
+  std::printf("------------------------------------------------------------------\n");
+  std::printf("  data matrix, nrows: %d, ncols: %d, nnz: %zd\n", data->nrows,
+              max_index_plus_one(data->rowptr[data->nrows], data->rowind), data->rowptr[data->nrows]);
+  std::printf("  cross-validation: %d folds, %s, ", F, sp.mode == SLIMGPU_SPLIT_LEAVE_OUT ? "leave-out" : "folds");
+  if (sp.mode == SLIMGPU_SPLIT_LEAVE_OUT) std::printf("nheld: %d, ", sp.nheld);
+  std::printf("minkeep: %d, seed: %llu, split on the %s\n", sp.minkeep, (unsigned long long)sp.seed,
+              on_device ? "device" : "host");
+  std::printf("  optTol: %.2le, niters: %d\n", base.optTol, base.maxniters);
+
+  struct PairSums {
+    double hr = 0, arhr = 0, hr_min = 0, hr_max = 0, arhr_min = 0, arhr_max = 0;
+  };
+  std::vector<PairSums> sums((size_t)npairs);
+  *bestHRHR = *bestARHR = *bestHRAR = *bestARAR = 0.0;
+  for (int32_t f = 0; f < F && rc == SLIM_OK; ++f) {
+    sp.fold = f;
+    // the fold's two halves and its grid; the grid owns a staged train half, the host halves are freed behind it
+    slim_csr_t *h_trn = nullptr, *h_tst = nullptr;
+    slimgpu_grid_t* grid = nullptr;
+    if (on_device) {
+      slimgpu_matrix_t* d_trn = nullptr;
+      rc = matrix_split(staged, &sp, &d_trn, &h_tst);
+      if (rc == SLIM_OK) {
+        rc = SLIMGPU_GridOpenOn(d_trn, h_tst, ioptions, doptions, 0, npairs, filter, &grid);
+        if (rc != SLIM_OK) matrix_free(d_trn);
+      }
+    } else {
+      rc = split_host(data, sp, &h_trn, &h_tst);
+      if (rc == SLIM_OK) rc = SLIMGPU_GridOpen(h_trn, h_tst, ioptions, doptions, 0, npairs, filter, &grid);
+    }
+    if (rc == SLIM_OK) {
+      std::printf("\nfold %d of %d: %zd held-out entries\n", f, F, h_tst->rowptr[h_tst->nrows]);
+      grid->describe();
+      std::printf("\n");
+    }
+    for (int32_t p = 0; p < npairs && rc == SLIM_OK; ++p) {
+      doptions[SLIM_OPTION_L1R] = pl1[p];  // (written through, as Py_SLIM_Mselect writes them)
+      doptions[SLIM_OPTION_L2R] = pl2[p];
+      slimgpu_grid_cell_t c;
+      rc = grid->solve(pl1[p], pl2[p], &c);
+      if (rc != SLIM_OK) break;
+      const double hr = c.metrics[0], arhr = c.metrics[3];
+      std::printf("l1r: %.2le l2r: %.2le nnz: %7zd hr: %.4f hr_head: %.4f hr_tail: %.4f "
+                  "arhr: %.4f time: %.2lf\n",
+                  c.l1r, c.l2r, (ssize_t)c.nnz, hr, c.metrics[1], c.metrics[2], arhr, c.solve_seconds);
+      if (cells) {
+        double* out = cells + (size_t)SLIMGPU_CV_CELL * ((size_t)f * (size_t)npairs + (size_t)p);
+        out[0] = f; out[1] = c.l1r; out[2] = c.l2r;
+        for (int k = 0; k < 4; ++k) out[3 + k] = c.metrics[k];
+        for (int k = 0; k < 3; ++k) out[7 + k] = c.nvalid[k];
+        out[10] = (double)c.nnz;
+      }
+      if (c.nvalid[0] < 1) {  // pyapi.c:377-381
+        *bestl1HR = c.l1r;
+        *bestl2HR = c.l2r;
+        rc = SLIM_ERROR;
+        break;
+      }
+      PairSums& s = sums[(size_t)p];
+      s.hr += hr;
+      s.arhr += arhr;
+      s.hr_min = f ? std::min(s.hr_min, hr) : hr;
+      s.hr_max = f ? std::max(s.hr_max, hr) : hr;
+      s.arhr_min = f ? std::min(s.arhr_min, arhr) : arhr;
+      s.arhr_max = f ? std::max(s.arhr_max, arhr) : arhr;
+    }
+    SLIMGPU_GridFree(&grid);
+    csr_free(h_trn);
+    csr_free(h_tst);
+  }
+  matrix_free(staged);
+  if (rc == SLIM_OK) {
+    std::printf("\nmeans over %d folds\n\n", F);
+    for (int32_t p = 0; p < npairs; ++p) {
+      const PairSums& s = sums[(size_t)p];
+      const double l1 = pl1[p], l2 = pl2[p], hr = s.hr / F, arhr = s.arhr / F;
+      std::printf("l1r: %.2le l2r: %.2le hr: %.4f (min %.4f max %.4f) arhr: %.4f (min %.4f max %.4f)\n", l1, l2, hr,
+                  s.hr_min, s.hr_max, arhr, s.arhr_min, s.arhr_max);
+      if (hr > *bestHRHR) {
+        *bestHRHR = hr; *bestARHR = arhr; *bestl1HR = l1; *bestl2HR = l2;
+      }
+      if (arhr > *bestARAR) {
+        *bestHRAR = hr; *bestARAR = arhr; *bestl1AR = l1; *bestl2AR = l2;
+      }
+    }
+  }
+  std::printf("\nDone.\n------------------------------------------------------------------\n");
+  return rc;
+}
+
+int32_t Py_SLIM_MselectCV(slim_t* datahandle, int32_t* ioptions, double* doptions, double* arrayl1, double* arrayl2,
+                          int32_t nl1, int32_t nl2, const slimgpu_split_t* split, slimgpu_filter_t* filter,
+                          double* bestl1HR, double* bestl2HR, double* bestHRHR, double* bestARHR, double* bestl1AR,
+                          double* bestl2AR, double* bestHRAR, double* bestARAR, double* cells) {
+  std::vector<double> pl1, pl2;
+  for (int32_t a = 0; arrayl1 && arrayl2 && a < nl1; ++a)
+    for (int32_t b = 0; b < nl2; ++b) {
+      pl1.push_back(arrayl1[a]);
+      pl2.push_back(arrayl2[b]);
+    }
+  return mselect_cv_impl("Py_SLIM_MselectCV", datahandle, ioptions, doptions, (int32_t)pl1.size(), pl1.data(),
+                         pl2.data(), split, filter, bestl1HR, bestl2HR, bestHRHR, bestARHR, bestl1AR, bestl2AR, bestHRAR,
+                         bestARAR, cells);
+}
+
+int32_t SLIMGPU_MselectCVPairs(slim_t* datahandle, int32_t* ioptions, double* doptions, int32_t npairs,
+                               const double* l1, const double* l2, const slimgpu_split_t* split,
+                               slimgpu_filter_t* filter, double* best, double* cells) {
+  if (!best) {
+    set_error("SLIMGPU_MselectCVPairs: bad arguments (the eight outputs)");
+    return SLIM_ERROR_INPUT;
+  }
+  return mselect_cv_impl("SLIMGPU_MselectCVPairs", datahandle, ioptions, doptions, npairs, l1, l2, split, filter,
+                         best, best + 1, best + 2, best + 3, best + 4, best + 5, best + 6, best + 7, cells);
+}
+
 int32_t Py_SLIM_GetTopN(slim_t* model, int32_t nratings, int32_t* itemids, float* ratings,
                         int32_t nrcmds, int32_t* rids, float* rscores, int32_t /*dbglvl*/) {
   return SLIM_GetTopN(model, nratings, itemids, ratings, nullptr, nrcmds, rids, rscores);

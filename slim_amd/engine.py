@@ -502,6 +502,60 @@ def _wrap_rows(lib, M):
     return h
 
 
+def _rows_to_scipy(lib, handle, ncols=None, free=True):
+    """The row view of a host handle (slim_csr_t) as a scipy CSR matrix; a handle without values gives ones.
+    ncols None: the handle's width (largest id + 1)."""
+    view = C.cast(handle, C.POINTER(_lib.CsrView)).contents
+    n = int(view.nrows)
+    ptr = np.ctypeslib.as_array(view.rowptr, shape=(n + 1,)).astype(np.int64)
+    nnz = int(ptr[-1])
+    ind = np.ctypeslib.as_array(view.rowind, shape=(nnz,)).copy() if nnz else np.zeros(0, np.int32)
+    if nnz and view.rowval:
+        val = np.ctypeslib.as_array(view.rowval, shape=(nnz,)).copy()
+    else:
+        val = np.ones(nnz, np.float32)
+    width = max(int(view.ncols), 0) if ncols is None else int(ncols)
+    if free:
+        lib.Py_csr_free(handle)
+    return sp.csr_matrix((val, ind, ptr), shape=(n, width))
+
+
+SPLIT_MODES = {"leave_out": _lib.SPLIT_LEAVE_OUT, "folds": _lib.SPLIT_FOLDS}
+
+
+def make_split(mode="leave_out", nfolds=1, fold=0, nheld=1, minkeep=1, seed=1):
+    """A slimgpu_split_t (include/slim_gpu_split.h, which states the rule).  mode: "leave_out" (every user that takes
+    part holds out `nheld` entries per fold) or "folds" (entry (u, i) belongs to one of `nfolds` folds by its hash)."""
+    if mode not in SPLIT_MODES and mode not in SPLIT_MODES.values():
+        raise ValueError("split: mode is 'leave_out' or 'folds', not %r" % (mode,))
+    return _lib.Split(SPLIT_MODES.get(mode, mode), int(nfolds), int(fold), int(nheld), int(minkeep),
+                      int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def split_host(R, mode="leave_out", nfolds=1, fold=0, nheld=1, minkeep=1, seed=1, binary=False, lib=None):
+    """SLIMGPU_SplitHost: one interactions matrix R (scipy, one row per user, entries as stored) split on the host
+    into (train, test), two scipy CSR matrices of R's shape with R's row order and values.  binary=True passes no
+    values (the halves then carry ones).  The rows equal those of DeviceMatrix.split for the same parameters."""
+    lib = lib or _lib.load()
+    R = sp.csr_matrix(R)
+    ptr = np.ascontiguousarray(R.indptr, dtype=np.intp)
+    ind = np.ascontiguousarray(R.indices, dtype=np.int32)
+    val = None if binary else np.ascontiguousarray(R.data, dtype=np.float32)
+    h = C.c_void_p()
+    st = lib.Py_csr_wrapper(R.shape[0], ptr, ind, _ptr(val), C.byref(h))
+    if st != SLIM_OK:
+        raise RuntimeError("Py_csr_wrapper failed (%d)" % st)
+    spec = make_split(mode, nfolds, fold, nheld, minkeep, seed)
+    trn, tst = C.c_void_p(), C.c_void_p()
+    try:
+        st = lib.SLIMGPU_SplitHost(h, C.byref(spec), C.byref(trn), C.byref(tst))
+    finally:
+        lib.Py_csr_free(h)
+    if st != SLIM_OK:
+        raise ValueError("SLIMGPU_SplitHost failed (%d): %s" % (st, _lib.last_error()))
+    return _rows_to_scipy(lib, trn, R.shape[1]), _rows_to_scipy(lib, tst, R.shape[1])
+
+
 class Evaluator(object):
     """The test set of a grid staged in HBM (SLIMGPU_EvalSetCreateAt): `evaluate(resident_model)` scores
     the model against the staged training matrix and brings down HR / ARHR only -- of the longest
@@ -755,6 +809,18 @@ class DeviceMatrix(object):
         self._host_rows = None
 
     __del__ = close
+
+    def split(self, mode="leave_out", nfolds=1, fold=0, nheld=1, minkeep=1, seed=1):
+        """SLIMGPU_MatrixSplit: this matrix split where it lies (include/slim_gpu_split.h states the rule).  Returns
+        (DeviceMatrix, test): the train half, staged on this matrix's device from arrays that never left it, and the
+        held-out entries as a scipy CSR matrix of this matrix's shape -- the only part that crosses to the host.
+        The rows equal split_host's for the same parameters, bit for bit; eval_stats() reports the call."""
+        spec = make_split(mode, nfolds, fold, nheld, minkeep, seed)
+        trn, tst = C.c_void_p(), C.c_void_p()
+        st = self._lib.SLIMGPU_MatrixSplit(self.handle, C.byref(spec), C.byref(trn), C.byref(tst))
+        if st != SLIM_OK:
+            raise ValueError("SLIMGPU_MatrixSplit failed (%d): %s" % (st, _lib.last_error()))
+        return DeviceMatrix(trn.value), _rows_to_scipy(self._lib, tst, self.ncols)
 
     def column_view(self):
         colptr = np.zeros(self.ncols + 1, np.int64)

@@ -222,6 +222,27 @@ class SLIMatrix(object):
         self.nItems = len(self.id2item)
         self._set_csr(sp.csr_matrix((vals, (rows, cols)), shape=(self.nUsers, self.nItems)))
 
+    def split(self, mode="leave_out", nfolds=1, fold=0, nheld=1, minkeep=1, seed=1):
+        """SLIMGPU_SplitHost (include/slim_gpu_split.h states the rule): this matrix split into (train, test), two
+        SLIMatrix objects with this matrix's id maps and shape.  mode "leave_out": every user with at least
+        nfolds * nheld + minkeep entries holds out nheld of them in each fold; "folds": every entry belongs to one of
+        nfolds folds.  The same parameters always give the same rows.  (An engine extension.)"""
+        from .engine import make_split
+        spec = make_split(mode, nfolds, fold, nheld, minkeep, seed)
+        halves = C.c_void_p(), C.c_void_p()
+        rc = self._lib.SLIMGPU_SplitHost(self.handle, C.byref(spec), C.byref(halves[0]), C.byref(halves[1]))
+        if rc != SLIM_OK:
+            raise TypeError("The matrix could not be split. [%s]" % _lib.last_error())
+        out = []
+        for h in halves:
+            m = SLIMatrix.__new__(SLIMatrix)
+            m._lib, m.handle = self._lib, h
+            m.nUsers, m.nItems = self.nUsers, self.nItems
+            m.id2item, m.item2id = self.id2item.copy(), self.item2id.copy()
+            m.id2user, m.user2id = self.id2user.copy(), self.user2id.copy()
+            out.append(m)
+        return tuple(out)
+
     def _set_csr(self, R):
         handle = C.c_void_p()
         indptr = np.ascontiguousarray(R.indptr, dtype=np.intp)
@@ -365,10 +386,81 @@ class SLIM(object):
                                % _lib.last_error())
         print("Learning takes %.3f secs." % elapsed)
 
+    @staticmethod
+    def split(data, mode="leave_out", nfolds=1, fold=0, nheld=1, minkeep=1, seed=1):
+        """SLIMatrix.split of `data`: (train, test) as two SLIMatrix with data's id maps."""
+        assert type(data) == SLIMatrix, "data must be a SLIMatrix object."
+        return data.split(mode=mode, nfolds=nfolds, fold=fold, nheld=nheld, minkeep=minkeep, seed=seed)
+
+    def _mselect_cv(self, params, data, arrayl1, arrayl2, nrcmds, allowed_items, blocked_items, exclude, nnegs,
+                    negseed, negpop, cv, cv_mode, cv_held, cv_minkeep, cv_seed):
+        """mselect(cv=F): Py_SLIM_MselectCV on one matrix (include/slim_gpu_split.h)."""
+        from .engine import make_split
+        assert type(data) == SLIMatrix, "trndata must be a SLIMatrix object."
+        if not (isinstance(cv, (int, np.integer)) and not isinstance(cv, bool) and cv >= 1):
+            raise TypeError("cv must be the number of folds, at least 1.")
+        assert type(arrayl1) in [list, np.ndarray], "Please provide a list of l1 values."
+        assert type(arrayl2) in [list, np.ndarray], "Please provide a list of l2 values."
+        if len(arrayl1) < 1:
+            raise TypeError("The l1 array must not be empty.")
+        if len(arrayl2) < 1:
+            raise TypeError("The l2 array must not be empty.")
+        view = _prepare(params)
+        view.set("nrcmds", nrcmds)
+        iopt, dopt = build_options(view)
+        if nnegs:
+            iopt[Opt.GPU_EVALNEGS], iopt[Opt.GPU_EVALSEED] = int(nnegs), int(negseed)
+        if negpop:
+            iopt[Opt.GPU_EVALNEGPOP] = 1
+        spec = make_split(cv_mode, cv, 0, cv_held, cv_minkeep, cv_seed)
+        flt = None
+        if not (allowed_items is None and blocked_items is None and exclude is None):
+            # (the train half of a fold is as wide as its largest item id + 1: in a fold that holds the widest item's
+            # only entries out it is narrower than the data, and the grid then refuses the filter)
+            ncols = max(int(C.cast(data.handle, C.POINTER(_lib.CsrView)).contents.ncols), 1)
+            flt = _candidate_filter(self._lib, data.item2id, data.nItems, ncols, data, allowed_items, blocked_items,
+                                    exclude)
+        l1 = np.ascontiguousarray(np.sort(arrayl1), dtype=np.float64)
+        l2 = np.ascontiguousarray(np.sort(arrayl2), dtype=np.float64)
+        best = [C.c_double(0.0) for _ in range(8)]
+        cells = np.zeros((int(cv), l1.size * l2.size, _lib.CV_CELL), np.float64)
+        t0 = time.time()
+        try:
+            rc = self._lib.Py_SLIM_MselectCV(data.handle, iopt, dopt, l1, l2, l1.size, l2.size, C.byref(spec),
+                                             None if flt is None else flt.handle,
+                                             *([C.byref(b) for b in best] + [cells.ctypes.data_as(C.c_void_p)]))
+        finally:
+            if flt is not None:
+                flt.close()
+        elapsed = time.time() - t0
+        l1hr, l2hr, hrhr, arhr, l1ar, l2ar, hrar, arar = [b.value for b in best]
+        if rc != SLIM_OK:
+            raise RuntimeError(
+                "Something went wrong with model estimation or evaluation when l1=%.4f, "
+                "l2=%.4f. Please check the input matrix. [%s]" % (l1hr, l2hr, _lib.last_error()))
+        print("Model selection takes %.3f secs." % elapsed)
+        print("The best mean HR over %d folds is achieved by, l1: %.4f, l2:%.4f, HR:%.4f, AR:%.4f."
+              % (cv, l1hr, l2hr, hrhr, arhr))
+        print("The best mean AR over %d folds is achieved by, l1: %.4f, l2:%.4f, HR:%.4f, AR:%.4f."
+              % (cv, l1ar, l2ar, hrar, arar))
+        self.mselect_result = dict(bestHR=(l1hr, l2hr, hrhr, arhr), bestAR=(l1ar, l2ar, hrar, arar))
+        names = ("fold", "l1", "l2", "hr", "hr_head", "hr_tail", "arhr", "nvalid", "nvalid_head", "nvalid_tail", "nnz")
+        ints = ("fold", "nvalid", "nvalid_head", "nvalid_tail", "nnz")
+        self.last_cv = [[{k: (int(v) if k in ints else float(v)) for k, v in zip(names, row)} for row in fold]
+                        for fold in cells]
+
     def mselect(self, params, trndata, tstdata, arrayl1, arrayl2, nrcmds, allowed_items=None, blocked_items=None,
                 exclude=None, nnegs=0, negseed=1, negpop=False, exposure=False, groups=None, history_bands=None,
-                select_group=None):
-        """groups / history_bands (at most one; include/slim_gpu_groups.h): every pair is also evaluated per user group,
+                select_group=None, cv=None, cv_mode="leave_out", cv_held=1, cv_minkeep=1, cv_seed=1):
+        """cv=F (include/slim_gpu_split.h): trndata is the ONE interactions matrix and tstdata must be None; the
+        library holds items out itself, reproducibly from cv_seed, and runs the grid once per fold.  cv_mode
+        "leave_out": every user with at least F * cv_held + cv_minkeep entries holds out cv_held of them in each
+        fold; "folds": every entry belongs to one of F folds, and a user takes part in a fold that leaves it
+        cv_minkeep entries.  A pair is judged by the mean of its fold figures; the table stays on the object as
+        last_cv: one list per fold of one dict per pair, in the order solved, with fold, l1, l2, hr, hr_head, hr_tail,
+        arhr, nvalid, nvalid_head, nvalid_tail, nnz.  It combines with the filter arguments, nnegs and negpop, and not
+        with exposure=True, groups or history_bands.
+        groups / history_bands (at most one; include/slim_gpu_groups.h): every pair is also evaluated per user group,
         from the same scoring pass.  groups: an integer array over trndata's user rows (0 .. ngroups-1, or -1 for no
         group), or a dict {ORIGINAL user id: group} mapped through trndata's user map -- users the map does not know
         are ignored, users the dict does not name are in no group.  history_bands: ascending bounds >= 1; the group of
@@ -396,6 +488,14 @@ class SLIM(object):
         filter removes counts as a miss.  (An engine extension; it needs the evaluation in HBM.)"""
         if not isinstance(exposure, (bool, np.bool_)):
             raise TypeError("exposure must be True or False.")
+        self.last_cv = None
+        if cv is not None:
+            if tstdata is not None:
+                raise TypeError("cv holds items out of trndata itself: pass tstdata=None, or no cv.")
+            if exposure or groups is not None or history_bands is not None or select_group is not None:
+                raise TypeError("cv does not combine with exposure=True, groups, history_bands or select_group.")
+            return self._mselect_cv(params, trndata, arrayl1, arrayl2, nrcmds, allowed_items, blocked_items, exclude,
+                                    nnegs, negseed, negpop, cv, cv_mode, cv_held, cv_minkeep, cv_seed)
         if exposure and nnegs:
             raise TypeError("exposure=True does not combine with nnegs: the exposure of sampled lists is not built.")
         assert type(trndata) == SLIMatrix, "trndata must be a SLIMatrix object."
